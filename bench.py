@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- keyframe-pairs/sec of the LT-removert / LT-map hot path (BASELINE.json metric) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a torch.distributed environment re-launches itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU over RCCL); when
@@ -14,7 +14,9 @@ Default workload = BASELINE.json configs[1]: "ParkingLot 01 vs 02, 500 keyframes
 restated on the synthetic `lot` scene (tools/synth.py; no dataset is reachable offline).  `lot-cascade-6x500` is
 configs[2]: five chained pair runs 01 -> 02..06 (lt-mapper_amd/cascade.py), 2500 keyframe pairs per step.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...) and the workload's configuration.  --dump-outputs DIR writes what
+the last timed step computed (dump_outputs).  With --full the run goes on after the timed steps and the line also carries
   roofline     -- the dominant kernel (k_vote_map_cull).  Its binding resource is VALU ISSUE, not HBM (the ~110 MB map stays in
                   the 256 MiB Infinity Cache and a tile is re-used from L2 by eight keyframes): `bound` = "valu", `achieved` /
                   `peak` / `frac` = VALU lane-instructions per second against the vector pipes' nominal peak (SQ_INSTS_VALU from
@@ -29,7 +31,8 @@ Prints ONE JSON line (rank 0).  Besides the contract fields it carries
                   exactly the sources this run measures;
   cpu_baseline -- the CPU oracle (a port of the reference; the reference itself cannot be built here) timed on this
                   box on a bounded keyframe sample of the same workload: single thread (the north-star denominator) and
-                  all cores; the committed full, unsampled runs are quoted next to it.
+                  all cores; the committed full, unsampled runs are quoted next to it;
+and the whole record goes to a sidecar file (--extra-out, default profiles/bench_extra_latest.json).
 """
 import argparse
 import json
@@ -62,6 +65,11 @@ WORKLOADS = {
 }
 CASCADE_SESSIONS = {"lot-cascade-6x500": 6, "lot-cascade-4x50-small": 4}
 
+# --dump-outputs: rows kept per output cloud (larger clouds: a sample drawn with a fixed seed) and the cap on all files together
+DUMP_ROWS = 1 << 16
+DUMP_SEED = 20250224
+DUMP_MAX_BYTES = 64 << 20
+
 VALU_CLASSES = ("vote_map_cull", "vote_map_exact", "reproject_map")      # projection kernels: bound by VALU issue, not HBM
 DOMINANT_KERNEL = {"vote_map_cull": "k_vote_map_cull", "vote_map_exact": "k_map_rimg_blockmin", "reproject_map": "k_map_rimg_blockmin", "knn_query": "k_knn_fast",
                    "knn_query_p2": "k_knn_slow_sorted", "voxel": "rocprim onesweep + k_voxel_centroids_packed", "merge": "k_transform_scans"}
@@ -78,12 +86,17 @@ CLASS_KERNELS = {
 }
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure everything beside the headline figure: the one-lane profiling pass, "
+                    "kernel-class rooflines, the CPU baseline, t_total through ltm_run, the parity-record check and the sidecar file.  Without it the run sets up, "
+                    "warms up, times the steps and prints the contract fields only; the options below that name those figures take effect with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 points, float64 "
+                    "sizes and keyframe offsets; outputs larger than %d points as a fixed, seeded sample of rows)" % DUMP_ROWS)
     ap.add_argument("--cpu-stride", type=int, default=50, help="cpu_baseline, single thread: visit every s-th keyframe in per-keyframe loops (50 = 10 of 500 "
                                                                "keyframes per session: ~50 s on the GPU box's host; round 4 ran stride 10 = 165 s of a 187 s driver run)")
     ap.add_argument("--cpu-stride-allcore", type=int, default=10, help="cpu_baseline, all cores: keyframe stride")
@@ -104,7 +117,7 @@ def parse_args():
     ap.add_argument("--overlap-sessions", action="store_true", help="EXPERIMENT (one GPU, pair workloads): merge + grid and Step 1 of the query session on a second "
                     "context / stream / host thread beside the central session's (removerter.Removerter query_side).  Kernel times of overlapping launches "
                     "are inflated by each other, so the roofline figures of such a line describe the overlap, not the kernels")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def relaunch_under_torchrun(n):
@@ -256,6 +269,42 @@ def main():
     if two_lanes:
         lane_ops.ctx.synchronize()
     elapsed = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(last, args.dump_outputs, write=rank == 0)
+
+    pairs_per_step = n_kf * (n_sessions - 1)   # min(N_c, N_q) keyframe pairs per session pair (SURVEY.md 8d), one pair run per query session
+    value = pairs_per_step * args.steps / elapsed
+    ms_per_step = 1e3 * elapsed / args.steps
+    head = {
+        "metric": "keyframe-pairs/sec (removert+diff)", "value": round(value, 3), "unit": "keyframe-pairs/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "strong" if world > 1 else "weak", "vs_baseline": None,
+        "dtype": "f32", "dtype_detail": "f32 (+f64 rigid transforms, u64 range|index atomics)", "data": "synthetic (tools/synth.py synth-v1, seed 20250224)",
+        "config": {"workload": args.workload, "sessions": f"{scene} 01 vs 02" if n_sessions == 2 else f"{scene} cascade 01 -> 02..{n_sessions:02d} ({n_sessions - 1} chained pair runs)",
+                   "keyframes_per_session": n_kf, "keyframe_pairs_per_step": pairs_per_step, "sensor": sensor,
+                   "remove_resolution_list": P.remove_resolution_list if three_res else [2.5], "self_removert": three_res,
+                   "knn": {"k": knn_k, "thr": knn_thr}, "voxel": voxel,
+                   "map_points_last_pair": [len(last.outputs["OriginalNoisyCentralMapGlobal"]), len(last.outputs["OriginalNoisyQueryMapGlobal"])],
+                   "scan_points": [int(s["offsets"][-1]) for s in sess_t],
+                   "parallelism": (f"keyframe-sharded x{world} (label all-reduce, key-range all-to-all for the merges" + (", one rank group per session in Step 1" if dist_session_groups(world) else "") + ")") if world > 1 else
+                                  ("single GPU, the two sessions' merge + Step-1 chains side by side on two contexts (--overlap-sessions experiment)" if args.overlap_sessions else
+                                   ("single GPU, two lanes (independent chains of run() side by side on two streams / host threads)" if two_lanes else "single GPU, one lane")),
+                   "step": "makeGlobalMap + Removerter::run Steps 1-3 per pair run, inputs resident in HBM"},
+        "lanes": 2 if two_lanes else 1,
+    }
+    if not args.full:
+        # a plain run: the headline figure and nothing that needs runs of its own
+        if rank == 0:
+            print(json.dumps(head_line(head)))
+            sys.stdout.flush()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     psteps = args.steps          # the steps the kernel-class profile covers
     one_lane_ms = None
     timed_stage_ms = {k: round(1e3 * v, 2) for k, v in last.timings.items()}
@@ -289,14 +338,6 @@ def main():
                 prof[k] = dict(v)
     cull_surv, cull_pts = ctx.cull_stats()
     vox_grids, vox_identity = ctx.voxel_stats()
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    pairs_per_step = n_kf * (n_sessions - 1)   # min(N_c, N_q) keyframe pairs per session pair (SURVEY.md 8d), one pair run per query session
-    value = pairs_per_step * args.steps / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
 
     clock_hz = 1e3 * float(getattr(torch.cuda.get_device_properties(local_rank), "clock_rate", 2.4e6))
     valu_peak = N_CU * SIMD_PER_CU * LANES_PER_SIMD * clock_hz      # VALU lane-instructions per second
@@ -383,11 +424,7 @@ def main():
         t_total = run_t_total(sess_t, n_kf)
 
     if rank == 0:
-        M_c = len(last.outputs["OriginalNoisyCentralMapGlobal"])
-        M_q = len(last.outputs["OriginalNoisyQueryMapGlobal"])
-        full = {
-            "metric": "keyframe-pairs/sec (removert+diff)", "value": round(value, 3), "unit": "keyframe-pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        full = dict(head, **{
             # the same region -- makeGlobalMap + Steps 1-3, loaded sessions resident, no output files, warm -- timed by the C++ host itself
             # (`ltm_run --bench`, the north-star boundary) in this very invocation; its kernel-class launch counts are in t_total.cxx_host_bench and
             # tests/test_gpu_cli.py requires them to equal the Python host's: one pipeline, two drivers.  `..._one_shot_...` is the cold files -> files run
@@ -395,20 +432,8 @@ def main():
                                      if t_total and isinstance(t_total.get("cxx_host_bench"), dict) and t_total["cxx_host_bench"].get("ms_per_step") else None),
             "cxx_host_one_shot_steps123_ms": (round(1e3 * t_total["configs[1] 2x500 3-res"]["T_steps123_s"], 1)
                                               if t_total and isinstance(t_total.get("configs[1] 2x500 3-res"), dict) and t_total["configs[1] 2x500 3-res"].get("T_steps123_s") else None),
-            "higher_is_better": True, "scaling": "strong" if world > 1 else "weak", "vs_baseline": None,
-            "dtype": "f32", "dtype_detail": "f32 (+f64 rigid transforms, u64 range|index atomics)", "data": "synthetic (tools/synth.py synth-v1, seed 20250224)",
-            "config": {"workload": args.workload, "sessions": f"{scene} 01 vs 02" if n_sessions == 2 else f"{scene} cascade 01 -> 02..{n_sessions:02d} ({n_sessions - 1} chained pair runs)",
-                       "keyframes_per_session": n_kf, "keyframe_pairs_per_step": pairs_per_step, "sensor": sensor,
-                       "remove_resolution_list": P.remove_resolution_list if three_res else [2.5], "self_removert": three_res,
-                       "knn": {"k": knn_k, "thr": knn_thr}, "voxel": voxel, "map_points_last_pair": [M_c, M_q],
-                       "scan_points": [int(s["offsets"][-1]) for s in sess_t],
-                       "parallelism": (f"keyframe-sharded x{world} (label all-reduce, key-range all-to-all for the merges" + (", one rank group per session in Step 1" if dist_session_groups(world) else "") + ")") if world > 1 else
-                                      ("single GPU, the two sessions' merge + Step-1 chains side by side on two contexts (--overlap-sessions experiment)" if args.overlap_sessions else
-                                       ("single GPU, two lanes (independent chains of run() side by side on two streams / host threads)" if two_lanes else "single GPU, one lane")),
-                       "step": "makeGlobalMap + Removerter::run Steps 1-3 per pair run, inputs resident in HBM"},
             "roofline": roofline, "cpu_baseline": cpu_baseline, "rooflines": rooflines, "traffic_groups": groups or None,
             "t_total": t_total, "parity_fullsize": parity_fullsize_status(),
-            "lanes": 2 if two_lanes else 1,
             "one_lane_ms_per_step": round(one_lane_ms, 3) if one_lane_ms else None,
             "class_times_from": (f"a one-lane profiling pass of {psteps} steps after the two-lane timed region (HIP events of overlapping launches would count the other lane's work)"
                                  if two_lanes else "the timed region"),
@@ -426,7 +451,7 @@ def main():
                             "what": "voxel grids of clouds per step and how many of them the bounding-box pass recognised as the identity (DESIGN.md 4.2)"},
             "vote_cull": {"points_tested": cull_pts, "needed_exact_path": cull_surv, "fraction": round(cull_surv / max(cull_pts, 1), 4)},
             "synth_generation_s": round(t_gen, 2),
-        }
+        })
         extra_path = write_extra(full, args)
         print(json.dumps(slim_line(full, extra_path)))
         sys.stdout.flush()
@@ -461,9 +486,8 @@ def _num(d, *keys):
     return {k: d.get(k) for k in keys if k in d} if isinstance(d, dict) else None
 
 
-def slim_line(full, extra_path):
-    """the ONE printed JSON line: contract fields, the dominant kernel's roofline (numbers only), the CPU baseline (numbers + one short sentence),
-    a per-class table of numbers, and the path of the sidecar.  Stays well below 6000 bytes (tests/test_bench_line.py)"""
+def head_line(full):
+    """contract fields and the workload's configuration: the whole printed line of a plain run, the start of a --full run's"""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "cxx_host_ms_per_step", "lanes", "one_lane_ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     out = {k: full.get(k) for k in keep}
     cfg = full.get("config") or {}
@@ -471,6 +495,13 @@ def slim_line(full, extra_path):
                                              "map_points_last_pair", "parallelism") if k in cfg}
     if isinstance(out["config"].get("parallelism"), str):
         out["config"]["parallelism"] = out["config"]["parallelism"][:120]
+    return out
+
+
+def slim_line(full, extra_path):
+    """the ONE printed JSON line of a --full run: contract fields, the dominant kernel's roofline (numbers only), the CPU baseline (numbers + one short sentence),
+    a per-class table of numbers, and the path of the sidecar.  Stays well below 6000 bytes (tests/test_bench_line.py)"""
+    out = head_line(full)
     out["roofline"] = _num(full.get("roofline"), "kernel", "class", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "launches_per_step",
                            "share_of_step", "valu_frac", "hbm_algorithmic_frac", "hbm_compulsory_frac", "hbm_measured_frac", "traffic_over_compulsory", "pmc")
     cb = full.get("cpu_baseline")
@@ -503,6 +534,45 @@ def slim_line(full, extra_path):
         out["parity_fullsize_matches_sources"] = pf.get("matches_sources")
     out["extra"] = extra_path
     return out
+
+
+def dump_outputs(rm, out_dir, write=True):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the maps of rm.outputs and the five per-keyframe scan sets of
+    rm.scan_outputs() -- as out_dir/<name>.npy.  A cloud of n points gives <name>.npy (float32 rows x, y, z, intensity: all of them if n <= DUMP_ROWS,
+    else the rows at DUMP_ROWS sorted indices drawn with DUMP_SEED, gathered on the device) and <name>.size.npy (float64 [n]); a scan set also gives
+    <name>.offsets.npy (float64 keyframe offsets, exact below 2^53).  Keyframe-sharded scan sets are all-gathered on every rank; only `write` ranks write."""
+    import numpy as np
+    items = [("map_" + k, v) for k, v in sorted(rm.outputs.items()) if v is not None]
+    items += [("scans_" + k, v) for k, v in sorted(rm.scan_outputs().items()) if v is not None]
+    arrays = {}
+    for name, obj in items:
+        if hasattr(obj, "full"):        # dist.LazyScans: this rank holds a keyframe range; the all-gather is collective
+            obj = obj.full()
+        if not write:
+            continue
+        whole = None
+        if hasattr(obj, "as_cloud"):    # capi.ScanSet
+            arrays[name + ".offsets"] = obj.offsets().astype(np.float64)
+            obj = whole = obj.as_cloud()
+        n = len(obj)
+        if n <= DUMP_ROWS:
+            pts = obj.download()
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+            sample = obj.ctx.select(obj, idx)
+            pts = sample.download()
+            sample.free()
+        if whole is not None:
+            whole.free()
+        arrays[name] = pts.astype(np.float32, copy=False)
+        arrays[name + ".size"] = np.array([n], dtype=np.float64)
+    if not write:
+        return
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def kernels_sha():

@@ -67,3 +67,96 @@ def test_the_committed_round4_record_also_slims_down():
     assert len(json.dumps(full)) > 15000
     line = json.dumps(bench.slim_line(full, None))
     assert len(line) < 6000 and json.loads(line)["value"] == full["value"]
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_plain_line_carries_the_contract_fields():
+    import bench
+    full = _synthetic_full()
+    head = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                                 "dtype_detail", "data", "config")}
+    got = json.loads(json.dumps(bench.head_line(head)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert got[k] == full[k], k
+    assert got["config"]["workload"] == "lot-2x500-os1-64-3res" and len(got["config"]["parallelism"]) <= 120
+
+
+class _FakeCtx:
+    def select(self, cloud, idx):
+        assert (idx >= 0).all() and (idx < len(cloud)).all() and (idx[1:] > idx[:-1]).all()
+        return _FakeCloud(cloud.pts[idx])
+
+
+class _FakeCloud:
+    """stands in for capi.Cloud: rows of float32 (x, y, z, intensity)"""
+    ctx = _FakeCtx()
+
+    def __init__(self, pts):
+        self.pts, self.freed = pts, False
+
+    def __len__(self):
+        return len(self.pts)
+
+    def download(self):
+        return self.pts.copy()
+
+    def free(self):
+        self.freed = True
+
+
+class _FakeScans:
+    def __init__(self, pts, offsets):
+        self.pts, self.off = pts, offsets
+
+    def offsets(self):
+        return self.off
+
+    def as_cloud(self):
+        return _FakeCloud(self.pts)
+
+
+class _FakeRun:
+    def __init__(self, outputs, scans):
+        self.outputs, self._scans = outputs, scans
+
+    def scan_outputs(self):
+        return self._scans
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(1)
+    big = rng.standard_normal((bench.DUMP_ROWS * 3 + 5, 4)).astype(np.float32)
+    small = rng.standard_normal((100, 4)).astype(np.float32)
+    off = np.array([0, 10, 10, bench.DUMP_ROWS + 7], dtype=np.uint64)
+    scans = rng.standard_normal((int(off[-1]), 4)).astype(np.float32)
+    run = _FakeRun({"updated_map": _FakeCloud(big), "nd_map": _FakeCloud(small), "strong_nd_map": None}, {"scans_updated": _FakeScans(scans, off)})
+    dirs = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        bench.dump_outputs(run, str(d))
+        dirs.append(d)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(["map_nd_map.npy", "map_nd_map.size.npy", "map_updated_map.npy", "map_updated_map.size.npy",
+                            "scans_scans_updated.npy", "scans_scans_updated.size.npy", "scans_scans_updated.offsets.npy"])
+    total = 0
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), n
+        total += a.nbytes
+    assert total <= bench.DUMP_MAX_BYTES
+    assert (np.load(dirs[0] / "map_nd_map.npy") == small).all()
+    sample = np.load(dirs[0] / "map_updated_map.npy")
+    assert sample.shape == (bench.DUMP_ROWS, 4) and np.load(dirs[0] / "map_updated_map.size.npy").tolist() == [len(big)]
+    rows = {r.tobytes() for r in big}
+    assert all(r.tobytes() in rows for r in sample[:1000])
+    assert np.load(dirs[0] / "scans_scans_updated.offsets.npy").tolist() == off.tolist()
+    assert np.load(dirs[0] / "scans_scans_updated.npy").shape == (bench.DUMP_ROWS, 4)

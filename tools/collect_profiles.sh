@@ -22,7 +22,7 @@ COMMIT=$(cat "$ROOT/.commit_for_profiles" 2>/dev/null || echo unknown)
 kernel_trace() {   # $1 = workload, $2 = output stem
   rm -rf /tmp/prof_kt
   # round 6: --lanes 1 -- per-kernel durations and counters are taken from the ONE-lane order (launches that overlap count each other's time); the bench line itself runs two lanes
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o bench -- $BENCH --workload $1 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-t-total \
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o bench -- $BENCH --workload $1 --steps 1 --warmup 0 --lanes 1 --full --no-cpu-baseline --no-t-total \
       --extra-out "$OUT/${2}_bench_under_rocprof_extra.json" 2>/dev/null | tail -1 > "$OUT/${2}_bench_under_rocprof.json"
   f=$(find /tmp/prof_kt -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$OUT/${2}_rocprofv3_kernel_stats.csv" <<'PY'
@@ -76,7 +76,7 @@ for PART in $PARTS; do
       cp "$OUT/pmc_latest.json" "$ROOT/profiles/pmc_latest.json" ;;
     line)
       # the default bench line exactly as the driver runs it, after the counter passes so that it carries `traffic` and the VALU figures of THIS kernel source
-      ( cd "$ROOT" && python3 bench.py --gpus 1 --steps 20 --warmup 5 --extra-out "$OUT/${TAG}_bench_extra.json" ) > /tmp/bench_stdout.txt 2>/tmp/bench_stderr.txt
+      ( cd "$ROOT" && python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --extra-out "$OUT/${TAG}_bench_extra.json" ) > /tmp/bench_stdout.txt 2>/tmp/bench_stderr.txt
       tail -c 8000 /tmp/bench_stdout.txt | tail -1 > "$OUT/${TAG}_bench_as_driver_runs_it.json"
       python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read()); print('line bytes', len(json.dumps(d)), 'value', d['value'], 'frac', d['roofline']['frac'])" "$OUT/${TAG}_bench_as_driver_runs_it.json" ;;
     sq)
@@ -87,7 +87,7 @@ for PART in $PARTS; do
       kernel_trace "$W" "${TAG}_${W}"
       pmc_passes "$W" "$OUT/pmc_${W}.json"
       cp "$OUT/pmc_${W}.json" "$ROOT/profiles/pmc_${W}.json"
-      ( cd "$ROOT" && python3 bench.py --workload "$W" --steps 2 --warmup 1 --extra-out "$OUT/${TAG}_bench_${W}_extra.json" ) 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_${W}.json" ;;
+      ( cd "$ROOT" && python3 bench.py --workload "$W" --steps 2 --warmup 1 --full --extra-out "$OUT/${TAG}_bench_${W}_extra.json" ) 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_${W}.json" ;;
   esac
 done
 ls -la "$OUT"

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_wl
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_wl -o bench -- python $ROOT/bench.py --workload "$WL" --steps 1 --warmup 1 --no-cpu-baseline --no-t-total 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_under_rocprof.json"
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_wl -o bench -- python $ROOT/bench.py --workload "$WL" --steps 1 --warmup 1 --full --no-cpu-baseline --no-t-total 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_under_rocprof.json"
 f=$(find /tmp/prof_wl -name "*kernel_stats.csv" | head -1)
 python3 - "$f" "$OUT/${TAG}_rocprofv3_kernel_stats.csv" <<'PY'
 import csv, sys
