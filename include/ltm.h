@@ -265,6 +265,40 @@ int ltm_knn_partition(ltm_ctx*, ltm_cloud target, ltm_scanset scans, ltm_poses p
 /* removeWeakNDMapPointsHavingStrongNDInNear (Session.cpp:452-484): split `query` by k-NN distance to `target` */
 int ltm_knn_split_cloud(ltm_ctx*, ltm_cloud target, ltm_cloud query, int k, float thr, ltm_cloud* near, ltm_cloud* far);
 
+/* ----------------------------------------------------------- search index ---- */
+/* The reference's pcl::KdTreeFLANN<PointType> members (Session.cpp:18-23; setInputCloud at :404, :457, :489; nearestKSearch at :471, :592, :627)
+ * as a device-resident index with exact queries.  What this library takes KdTreeFLANN to do:
+ *  - distance: squared L2 in float, evaluated as FLANN's L2_Simple, ((dx*dx)+dy*dy)+dz*dz, without fused multiply-adds;
+ *  - kNN: the k smallest distances in ascending order; EQUAL DISTANCES ARE ORDERED BY THE SMALLER TARGET INDEX (FLANN leaves this unspecified);
+ *    k is clamped to the number of (finite) target points as nearestKSearch clamps it, the rest of the row is index -1, distance +inf;
+ *    1 <= k <= 64, anything else is LTM_E_INVALID;
+ *  - radius: every target point with d2 < r2, r2 = (float)((double)radius * radius) (PCL's static_cast<float>(radius * radius), FLANN's strict <),
+ *    ordered as for kNN; max_nn > 0 keeps only the max_nn nearest;
+ *  - indices: int32 positions in the target cloud as it was given (the target must have fewer than 2^31 points);
+ *  - target points with a non-finite coordinate are never returned; a query with one gets an empty row (all -1 for kNN, length 0 for radius);
+ *    an empty target is valid and gives empty rows.
+ * The result is exact for any distribution of points (the index is a tree of boxes over the target in Morton order, see ltm_k_search.hip).
+ * Everything is asynchronous on the context's stream except ltm_radius_search, which reads the total hit count back.  The index and the
+ * results come from the context's pool; the index keeps its own copy of the target (the cloud may be freed or changed afterwards).  Handles
+ * belong to the context that made them (another context, a lane included, gets LTM_E_INVALID); ltm_destroy releases whatever is still open. */
+typedef struct ltm_search ltm_search;
+typedef struct ltm_search_result ltm_search_result;
+/* kdtree->setInputCloud(target) (Session.cpp:404, :457, :489) */
+int ltm_search_build(ltm_ctx*, ltm_cloud target, ltm_search** out);
+int ltm_search_free(ltm_ctx*, ltm_search*);
+/* number of target points the index was built over, and how many of them are finite (searchable) */
+int ltm_search_info(ltm_ctx*, ltm_search*, size_t* n_target, size_t* n_finite);
+/* kdtree->nearestKSearch(query[i], k, idx, d2) for every point of `query` (Session.cpp:471, :592, :627): n_query x k rows, row-major, in the
+ * caller's device buffers idx_dev (int32) and d2_dev (float) */
+int ltm_knn_search(ltm_ctx*, ltm_search*, ltm_cloud query, int k, int32_t* idx_dev, float* d2_dev);
+/* kdtree->radiusSearch(query[i], radius, idx, d2, max_nn) for every point of `query` (no call site in the reference; LT-SLAM's loop search):
+ * CSR result, row i = [offsets[i], offsets[i+1]) of idx / d2 */
+int ltm_radius_search(ltm_ctx*, ltm_search*, ltm_cloud query, float radius, int max_nn, ltm_search_result** out);
+/* the result's device arrays (offsets: n_query + 1 entries), borrowed until ltm_search_result_free */
+int ltm_search_result_info(ltm_ctx*, ltm_search_result*, size_t* n_query, size_t* total,
+                           const uint64_t** offsets_dev, const int32_t** idx_dev, const float** d2_dev);
+int ltm_search_result_free(ltm_ctx*, ltm_search_result*);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections
@@ -352,6 +386,8 @@ int ltm_debug_occlusion_stats(ltm_ctx*, uint64_t* pairs, uint64_t* first_shell, 
 int ltm_debug_voxel_stats(ltm_ctx*, uint64_t* grids, uint64_t* identity_hits, int reset);
 /* diagnostic counters of the range-culled vote kernel since the last reset: points tested / points that needed the exact path */
 int ltm_debug_cull_stats(ltm_ctx*, uint64_t* survivors, uint64_t* points, int reset);
+/* blocks of the context's device pool that are handed out (live) and the bytes they hold: what a caller's handles and open tickets own */
+int ltm_debug_pool_live(ltm_ctx*, uint64_t* live_blocks, uint64_t* live_bytes);
 
 /* ----------------------------------------------------------- measurement ---- */
 /* Per-kernel-class HIP-event timing on the context's stream.  Classes: "vote_map", "vote_scan",

@@ -111,6 +111,14 @@ SIGNATURES = {
     "ltm_reproject": (_i, [_vp, _u64, _u64, _sz, _sz, _f, _pu64]),
     "ltm_knn_partition": (_i, [_vp, _u64, _u64, _u64, _sz, _sz, _i, _f, _pu64, _pu64]),
     "ltm_knn_split_cloud": (_i, [_vp, _u64, _u64, _i, _f, _pu64, _pu64]),
+    "ltm_search_build": (_i, [_vp, _u64, C.POINTER(_vp)]),
+    "ltm_search_free": (_i, [_vp, _vp]),
+    "ltm_search_info": (_i, [_vp, _vp, _psz, _psz]),
+    "ltm_knn_search": (_i, [_vp, _vp, _u64, _i, _vp, _vp]),
+    "ltm_radius_search": (_i, [_vp, _vp, _u64, _f, _i, C.POINTER(_vp)]),
+    "ltm_search_result_info": (_i, [_vp, _vp, _psz, _psz, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_search_result_free": (_i, [_vp, _vp]),
+    "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "ltm_debug_project": (_i, [_vp, _vp, _sz, _f, _vp, _vp]),
@@ -461,7 +469,22 @@ class Context:
         self._ck(self.lib.ltm_knn_split_cloud(self.h, target.h, query.h, k, thr, C.byref(near), C.byref(far)))
         return Cloud(self, near.value), Cloud(self, far.value)
 
+    def search_index(self, cloud):
+        """ltm_search_build: exact k-NN / radius search index over `cloud` (a Cloud of this context or an (n, 4) / (n, 3) array), the
+        counterpart of pcl::KdTreeFLANN::setInputCloud"""
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(_xyzi(cloud))
+        h = _vp()
+        self._ck(self.lib.ltm_search_build(self.h, cloud.h, C.byref(h)))
+        return SearchIndex(self, h.value)
+
     # ---- debug / parity
+    def pool_live(self):
+        """ltm_debug_pool_live: (blocks, bytes) of the device pool that are handed out"""
+        b, n = _u64(), _u64()
+        self._ck(self.lib.ltm_debug_pool_live(self.h, C.byref(b), C.byref(n)))
+        return b.value, n.value
+
     def rimg_size(self, alpha):
         r, c = _i(), _i()
         self.lib.ltm_rimg_size(self.vfov, self.hfov, alpha, C.byref(r), C.byref(c))
@@ -548,6 +571,99 @@ class Context:
         nb_c = (C.c_double * cap)()
         self._ck(min(self.lib.ltm_profile_read_compulsory(self.h, nb_c, cap), 0))
         return {names[i].decode(): dict(ms=ms[i], launches=int(launches[i]), units=units[i], bytes=nbytes[i], bytes_c=nb_c[i]) for i in range(min(n, cap))}
+
+
+def _xyzi(a):
+    """(n, 3) or (n, 4) points -> packed float32 XYZI"""
+    a = np.asarray(a, dtype=np.float32)
+    if a.ndim == 2 and a.shape[1] == 3:
+        a = np.concatenate([a, np.zeros((a.shape[0], 1), np.float32)], axis=1)
+    return _np_pts(a)
+
+
+class SearchIndex:
+    """ltm_search: device-resident exact k-NN / radius search over one cloud (pcl::KdTreeFLANN's queries, semantics in include/ltm.h).
+    Queries are Clouds of the same context or (n, 3) / (n, 4) arrays.  Results are numpy arrays, or with as_torch=True CUDA tensors that
+    torch allocated and owns (the library's buffers are copied into them device to device)."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+
+    def _query(self, query):
+        return query if isinstance(query, Cloud) else self.ctx.upload(_xyzi(query))
+
+    def info(self):
+        """(target points, finite target points)"""
+        a, b = C.c_size_t(), C.c_size_t()
+        self.ctx._ck(self.ctx.lib.ltm_search_info(self.ctx.h, self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _out(self, dev, n, dtype, as_torch):
+        """n elements of a library device array -> numpy array or torch CUDA tensor (a copy either way)"""
+        if as_torch:
+            import torch
+            t = torch.empty(n, dtype={np.int32: torch.int32, np.float32: torch.float32, np.uint64: torch.int64}[dtype],
+                            device=f"cuda:{self.ctx.device}")
+            if n:
+                torch.cuda.synchronize(t.device)
+                self.ctx._ck(self.ctx.lib.ltm_buffer_copy(self.ctx.h, t.data_ptr(), dev, n * t.element_size(), 2))
+            return t
+        a = np.empty(n, dtype=dtype)
+        if n:
+            self.ctx._ck(self.ctx.lib.ltm_buffer_copy(self.ctx.h, a.ctypes.data, dev, a.nbytes, 1))
+        return a
+
+    def knn(self, query, k, as_torch=False):
+        """nearestKSearch for every query point: (idx int32 [n, k], d2 float32 [n, k]); padding -1 / +inf"""
+        q = self._query(query)
+        n = len(q)
+        nb = max(n * int(k), 1) * 4
+        pi, pd = _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_buffer_alloc(self.ctx.h, nb, C.byref(pi)))
+        try:
+            self.ctx._ck(self.ctx.lib.ltm_buffer_alloc(self.ctx.h, nb, C.byref(pd)))
+            try:
+                self.ctx._ck(self.ctx.lib.ltm_knn_search(self.ctx.h, self.h, q.h, int(k), pi, pd))
+                idx = self._out(pi.value, n * int(k), np.int32, as_torch)
+                d2 = self._out(pd.value, n * int(k), np.float32, as_torch)
+            finally:
+                self.ctx.lib.ltm_buffer_free(self.ctx.h, pd)
+        finally:
+            self.ctx.lib.ltm_buffer_free(self.ctx.h, pi)
+        return idx.reshape(n, int(k)), d2.reshape(n, int(k))
+
+    def radius(self, query, r, max_nn=0, as_torch=False):
+        """radiusSearch for every query point, CSR: (offsets uint64 [n+1] (int64 as torch), idx int32 [total], d2 float32 [total])"""
+        q = self._query(query)
+        res = _vp()
+        self.ctx._ck(self.ctx.lib.ltm_radius_search(self.ctx.h, self.h, q.h, float(r), int(max_nn), C.byref(res)))
+        try:
+            nq, tot = C.c_size_t(), C.c_size_t()
+            po, pi, pd = _vp(), _vp(), _vp()
+            self.ctx._ck(self.ctx.lib.ltm_search_result_info(self.ctx.h, res, C.byref(nq), C.byref(tot), C.byref(po), C.byref(pi), C.byref(pd)))
+            off = self._out(po.value, nq.value + 1, np.uint64, as_torch)
+            idx = self._out(pi.value, tot.value, np.int32, as_torch)
+            d2 = self._out(pd.value, tot.value, np.float32, as_torch)
+        finally:
+            self.ctx.lib.ltm_search_result_free(self.ctx.h, res)
+        return off, idx, d2
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ltm_search_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class VgsTicket:

@@ -1,0 +1,245 @@
+// ltm_api_search.cpp -- C ABI: device-resident search index with exact k-NN and radius queries, the counterpart of the reference's
+// pcl::KdTreeFLANN members (Session.cpp:18-23, :404, :457, :471, :489, :592, :627).  Kernels in ltm_k_search.hip.
+#include "ltm_internal.h"
+
+struct ltm_search {
+    ltm_ctx* owner = nullptr;
+    size_t n_target = 0;
+    uint32_t Mf = 0, L = 0, P = 0;      // finite points, leaves, leaves rounded up to a power of two
+    SearchFrame f{};
+    float4* pts = nullptr;              // finite target points in Morton order
+    uint32_t* idx = nullptr;            // their positions in the target as given
+    uint64_t* keys = nullptr;           // their codes (the kNN seed looks the query's code up)
+    float4* box = nullptr;              // 2 x 2P float4: (lo, hi) of nodes 1 .. 2P-1
+    SearchTree tree() const { return SearchTree{pts, idx, keys, box, Mf, L, P}; }
+};
+struct ltm_search_result {
+    ltm_ctx* owner = nullptr;
+    size_t n_query = 0, total = 0;
+    uint64_t* off = nullptr; int32_t* idx = nullptr; float* d2 = nullptr;
+};
+
+namespace {
+
+void search_release(ltm_ctx* c, ltm_search* s)
+{
+    c->pool.free(s->pts); c->pool.free(s->idx); c->pool.free(s->keys); c->pool.free(s->box);
+    delete s;
+}
+void result_release(ltm_ctx* c, ltm_search_result* r)
+{
+    c->pool.free(r->off); c->pool.free(r->idx); c->pool.free(r->d2);
+    delete r;
+}
+// a handle of THIS context (a freed one, one of another context or a lane's is refused before it is dereferenced)
+ltm_search* get_search(ltm_ctx* c, ltm_search* s)
+{
+    LTM_REQUIRE(s && std::find(c->search_open.begin(), c->search_open.end(), s) != c->search_open.end(), "not a search index of this context");
+    return s;
+}
+ltm_search_result* get_result(ltm_ctx* c, ltm_search_result* r)
+{
+    LTM_REQUIRE(r && std::find(c->result_open.begin(), c->result_open.end(), r) != c->result_open.end(), "not a search result of this context");
+    return r;
+}
+
+void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
+{
+    const size_t n = target.n;
+    s->n_target = n;
+    LTM_REQUIRE(n < 0x80000000ull, "the target must have fewer than 2^31 points");
+    if (!n) return;
+    ProfScope p(c, "search_build", (double)n, 48.0 * n);
+    DevBuf bb(c, 8 * sizeof(uint32_t));
+    const uint32_t init[8] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u};
+    h2d(c, bb.p, init, sizeof(init));
+    LTM_HIP(search_bbox(target.d, n, bb.as<uint32_t>(), c->stream));
+    uint32_t got[8];
+    d2h(c, got, bb.p, sizeof(got));
+    s->Mf = got[6];
+    if (!s->Mf) return;
+    double mn[3], ext = 0.0;
+    for (int d = 0; d < 3; ++d) {
+        mn[d] = (double)search_bbox_decode(got[d]);
+        ext = std::max(ext, (double)search_bbox_decode(got[3 + d]) - mn[d]);
+    }
+    s->f = SearchFrame{mn[0], mn[1], mn[2], ext > 0.0 ? 2097151.0 / ext : 0.0};
+    // codes of every point (non-finite: ~0, sorted behind the finite ones) -> the first Mf entries of the sorted arrays are the index
+    DevBuf keys(c, n * 8), idx(c, n * 4);
+    s->keys = reinterpret_cast<uint64_t*>(c->pool.alloc(n * 8));
+    s->idx = reinterpret_cast<uint32_t*>(c->pool.alloc(n * 4));
+    LTM_HIP(search_keys(target.d, n, s->f, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
+    {
+        const size_t tb = sort_temp_bytes(n);
+        DevBuf temp(c, tb);
+        LTM_HIP(sort_pairs_u64(keys.as<uint64_t>(), s->keys, idx.as<uint32_t>(), s->idx, n, 64, temp.p, tb, c->stream));
+    }
+    s->pts = reinterpret_cast<float4*>(c->pool.alloc((size_t)s->Mf * sizeof(float4)));
+    LTM_HIP(gather_points(target.d, s->idx, s->Mf, s->pts, c->stream));
+    s->L = (s->Mf + kSearchLeaf - 1) / kSearchLeaf;
+    s->P = 1;
+    while (s->P < s->L) s->P <<= 1;
+    s->box = reinterpret_cast<float4*>(c->pool.alloc((size_t)4 * s->P * sizeof(float4)));
+    LTM_HIP(search_tree_boxes(s->pts, s->Mf, s->L, s->P, s->box, c->stream));
+}
+
+// the queries in code order under the index's frame
+struct QueryOrder {
+    DevBuf keys, keys_sorted, idx, order;
+    QueryOrder(ltm_ctx* c, const ltm_search* s, const Cloud& q)
+        : keys(c, q.n * 8), keys_sorted(c, q.n * 8), idx(c, q.n * 4), order(c, q.n * 4)
+    {
+        const size_t tb = sort_temp_bytes(q.n);
+        DevBuf temp(c, tb);
+        LTM_HIP(search_query_order(q.d, q.n, s->f, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), idx.as<uint32_t>(), order.as<uint32_t>(), temp.p, tb, c->stream));
+    }
+};
+
+} // namespace
+
+void ltm_detail::search_release_all(ltm_ctx* c)      // ltm_destroy: indices and results nobody freed
+{
+    for (ltm_search* s : c->search_open) search_release(c, s);
+    for (ltm_search_result* r : c->result_open) result_release(c, r);
+    c->search_open.clear();
+    c->result_open.clear();
+}
+
+extern "C" {
+
+int ltm_search_build(ltm_ctx* c, ltm_cloud htarget, ltm_search** out)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(out, "null argument");
+        const Cloud target = get_cloud(c, htarget);
+        std::unique_ptr<ltm_search> s(new ltm_search);
+        s->owner = c;
+        try {
+            build_index(c, s.get(), target);
+        } catch (...) {
+            search_release(c, s.release());
+            throw;
+        }
+        c->search_open.push_back(s.get());
+        *out = s.release();
+    });
+}
+
+int ltm_search_free(ltm_ctx* c, ltm_search* s)
+{
+    return guarded(c, [&] {
+        get_search(c, s);
+        c->search_open.erase(std::remove(c->search_open.begin(), c->search_open.end(), s), c->search_open.end());
+        search_release(c, s);
+    });
+}
+
+int ltm_search_info(ltm_ctx* c, ltm_search* s, size_t* n_target, size_t* n_finite)
+{
+    return guarded(c, [&] {
+        get_search(c, s);
+        if (n_target) *n_target = s->n_target;
+        if (n_finite) *n_finite = s->Mf;
+    });
+}
+
+int ltm_knn_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, int k, int32_t* idx_dev, float* d2_dev)
+{
+    return guarded(c, [&] {
+        const ltm_search* s = get_search(c, hs);
+        LTM_REQUIRE(k >= 1 && k <= 64, "k must be in [1, 64]");
+        const Cloud q = get_cloud(c, hquery);
+        if (!q.n) return;
+        LTM_REQUIRE(idx_dev && d2_dev, "null output buffer");
+        LTM_REQUIRE(q.n < 0x80000000ull, "too many queries");
+        ProfScope ps(c, "knn_search", (double)q.n, (double)q.n * (16.0 + 8.0 * k));
+        if (!s->Mf) { LTM_HIP(knn_empty_rows(q.n * (size_t)k, idx_dev, d2_dev, c->stream)); return; }
+        QueryOrder qo(c, s, q);
+        LTM_HIP(knn_search(q.d, q.n, qo.order.as<uint32_t>(), qo.keys_sorted.as<uint64_t>(), s->tree(), k, idx_dev, d2_dev, c->stream));
+    });
+}
+
+int ltm_radius_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, float radius, int max_nn, ltm_search_result** out)
+{
+    return guarded(c, [&] {
+        const ltm_search* s = get_search(c, hs);
+        LTM_REQUIRE(out, "null argument");
+        LTM_REQUIRE(!std::isnan(radius), "radius is NaN");
+        LTM_REQUIRE(max_nn >= 0, "max_nn must be >= 0 (0: no limit)");
+        const Cloud q = get_cloud(c, hquery);
+        LTM_REQUIRE(q.n < 0x80000000ull, "too many queries");
+        const float r2 = (float)((double)radius * (double)radius);
+        std::unique_ptr<ltm_search_result, void (*)(ltm_search_result*)> r(new ltm_search_result, [](ltm_search_result* p) { result_release(p->owner, p); });
+        r->owner = c;
+        r->n_query = q.n;
+        r->off = reinterpret_cast<uint64_t*>(c->pool.alloc((q.n + 1) * sizeof(uint64_t)));
+        uint64_t tot[2] = {0, 0};      // all hits, hits kept (max_nn)
+        if (q.n && s->Mf) {
+            QueryOrder qo(c, s, q);
+            DevBuf count(c, q.n * 4), full(c, (q.n + 1) * 8), tb2(c, 16);
+            {
+                ProfScope ps(c, "radius_count", (double)q.n, (double)q.n * 20.0);
+                LTM_HIP(radius_count(q.d, q.n, qo.order.as<uint32_t>(), s->tree(), r2, count.as<uint32_t>(), c->stream));
+                const size_t tb = radius_scan_temp_bytes(q.n);
+                DevBuf temp(c, tb);
+                LTM_HIP(radius_offsets(count.as<uint32_t>(), q.n, 0, full.as<uint64_t>(), temp.p, tb, c->stream));
+                LTM_HIP(radius_offsets(count.as<uint32_t>(), q.n, (uint32_t)max_nn, r->off, temp.p, tb, c->stream));
+            }
+            d2d(c, tb2.as<uint64_t>(), full.as<uint64_t>() + q.n, 8);
+            d2d(c, tb2.as<uint64_t>() + 1, r->off + q.n, 8);
+            d2h(c, tot, tb2.p, 16);      // the one host round trip: the sizes of the outputs
+            LTM_REQUIRE(tot[0] < 0x100000000ull, "more than 2^32 hits in one radius search");
+            r->total = tot[1];
+            r->idx = reinterpret_cast<int32_t*>(c->pool.alloc(std::max<size_t>(tot[1], 1) * 4));
+            r->d2 = reinterpret_cast<float*>(c->pool.alloc(std::max<size_t>(tot[1], 1) * 4));
+            if (tot[0]) {
+                ProfScope ps(c, "radius_fill", (double)tot[0], (double)q.n * 20.0 + 16.0 * (double)tot[0] + 8.0 * (double)tot[1]);
+                DevBuf pairs(c, tot[0] * 8), sorted(c, tot[0] * 8);
+                const size_t tb = radius_sort_temp_bytes(tot[0], q.n);
+                DevBuf temp(c, tb);
+                LTM_HIP(radius_fill(q.d, q.n, qo.order.as<uint32_t>(), s->tree(), r2, full.as<uint64_t>(), tot[0], r->off, pairs.as<uint64_t>(), sorted.as<uint64_t>(),
+                                    r->idx, r->d2, temp.p, tb, c->stream));
+            }
+        } else {
+            LTM_HIP(hipMemsetAsync(r->off, 0, (q.n + 1) * sizeof(uint64_t), c->stream));
+            r->idx = reinterpret_cast<int32_t*>(c->pool.alloc(4));
+            r->d2 = reinterpret_cast<float*>(c->pool.alloc(4));
+        }
+        c->result_open.push_back(r.get());
+        *out = r.release();
+    });
+}
+
+int ltm_search_result_info(ltm_ctx* c, ltm_search_result* hr, size_t* n_query, size_t* total, const uint64_t** offsets_dev, const int32_t** idx_dev,
+                           const float** d2_dev)
+{
+    return guarded(c, [&] {
+        const ltm_search_result* r = get_result(c, hr);
+        if (n_query) *n_query = r->n_query;
+        if (total) *total = r->total;
+        if (offsets_dev) *offsets_dev = r->off;
+        if (idx_dev) *idx_dev = r->idx;
+        if (d2_dev) *d2_dev = r->d2;
+    });
+}
+
+int ltm_search_result_free(ltm_ctx* c, ltm_search_result* r)
+{
+    return guarded(c, [&] {
+        get_result(c, r);
+        c->result_open.erase(std::remove(c->result_open.begin(), c->result_open.end(), r), c->result_open.end());
+        result_release(c, r);
+    });
+}
+
+int ltm_debug_pool_live(ltm_ctx* c, uint64_t* live_blocks, uint64_t* live_bytes)
+{
+    return guarded(c, [&] {
+        size_t b = 0;
+        for (const auto& kv : c->pool.live) b += kv.second;
+        if (live_blocks) *live_blocks = c->pool.live.size();
+        if (live_bytes) *live_bytes = b;
+    });
+}
+
+} // extern "C"

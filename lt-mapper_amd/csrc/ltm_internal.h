@@ -325,6 +325,8 @@ struct ltm_ctx {
     std::vector<PinnedBlock> pinned;
     std::unordered_map<uint64_t, UploadState> uploads;
     std::vector<struct ltm_vgs*> vgs_open;      // ltm_voxel_grid_scanset_begin tickets not ended yet: joined and released by ltm_destroy at the latest
+    std::vector<struct ltm_search*> search_open;            // search indices and radius results not freed yet: released by ltm_destroy at the latest
+    std::vector<struct ltm_search_result*> result_open;
 };
 
 namespace ltm_detail {
@@ -634,6 +636,7 @@ void scan_cache_drop(ltm_ctx* c, uint64_t ss_handle);                           
 void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud* kept, ltm_cloud* flagged);   // ltm_api_vote.cpp
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
 void vgs_release_all(ltm_ctx* c);                                                 // ltm_api_voxel.cpp: open ltm_voxel_grid_scanset tickets, at ltm_destroy
+void search_release_all(ltm_ctx* c);                                              // ltm_api_search.cpp: open search indices and results, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp
 

@@ -1,0 +1,449 @@
+// ltm_k_search.hip -- exact k-nearest-neighbour and radius search over a device-resident cloud: the counterpart of the reference's
+// pcl::KdTreeFLANN members (Session.cpp:18-23, built at :404,457,489, queried at :471,592,627).
+// (gfx950 / CDNA4, wave64; part of libltm_hip.so -- shared definitions in ltm_kernels_common.h, launch wrappers declared in ltm_kernels.h)
+//
+// Index: the finite target points sorted by a 63-bit Morton code (21 bits per axis over their bounding box), cut into leaves of kSearchLeaf
+// consecutive points, and an IMPLICIT complete binary tree of axis-aligned boxes over the leaves (node 1 is the root, node v has children 2v and
+// 2v+1, leaf l is node P + l with P the leaf count rounded up to a power of two; padding leaves hold an empty box).  Built with one radix sort
+// and log2(P) + 1 box passes, traversed without a stack (the implicit layout gives the next node by bit arithmetic).  A uniform grid walked in
+// Chebyshev shells was the first plan; its cost grows with the number of empty shells between a query and its k-th neighbour, which is
+// unbounded for clusters kilometres apart or queries far outside the map -- the box tree's is not.
+//
+// Exactness: the distance of a returned pair is FLANN's L2_Simple in float, ((dx*dx)+dy*dy)+dz*dz without contraction (sqdist_l2simple);
+// a box is skipped only when the lower bound of the distance to it, computed in double and shrunk by a relative 1e-6 (the float
+// evaluation is within 3e-7 relative of the exact value), is STRICTLY above the current k-th distance (kNN) or not below r2 (radius): no
+// point that could enter the result, a tie included, is ever skipped.  Ties are ordered by the smaller target index.
+#include "ltm_kernels_common.h"
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+#include <climits>
+namespace ltm {
+
+namespace {
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+// order-preserving float -> uint32 (min / max with integer atomics)
+__device__ __forceinline__ uint32_t ord_f32(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint64_t spread21(uint32_t v)
+{
+    uint64_t x = v & 0x1fffffu;
+    x = (x | (x << 32)) & 0x1f00000000ffffull;
+    x = (x | (x << 16)) & 0x1f0000ff0000ffull;
+    x = (x | (x << 8)) & 0x100f00f00f00f00full;
+    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
+    x = (x | (x << 2)) & 0x1249249249249249ull;
+    return x;
+}
+__device__ __forceinline__ uint32_t quant21(float v, double o, double scale)
+{
+    const double t = floor(((double)v - o) * scale);
+    return (uint32_t)fmin(fmax(t, 0.0), 2097151.0);
+}
+__device__ __forceinline__ uint64_t search_key(const SearchFrame& f, float x, float y, float z)
+{
+    if (!finite3(x, y, z)) return ~0ull;
+    return (spread21(quant21(x, f.ox, f.scale)) << 2) | (spread21(quant21(y, f.oy, f.scale)) << 1) | spread21(quant21(z, f.oz, f.scale));
+}
+// (d, i) goes before (bd, bi): smaller distance, then smaller target index
+__device__ __forceinline__ bool pair_less(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
+
+// lower bound of the squared distance from q to the node's box (double; +inf for an empty box)
+__device__ __forceinline__ double box_lb(const float4* __restrict__ box, uint32_t node, float qx, float qy, float qz)
+{
+    const float4 lo = box[2 * node], hi = box[2 * node + 1];
+    const double gx = fmax(fmax((double)lo.x - (double)qx, (double)qx - (double)hi.x), 0.0);
+    const double gy = fmax(fmax((double)lo.y - (double)qy, (double)qy - (double)hi.y), 0.0);
+    const double gz = fmax(fmax((double)lo.z - (double)qz, (double)qz - (double)hi.z), 0.0);
+    return (gx * gx + gy * gy + gz * gz) * (1.0 - 1.0e-6);
+}
+
+// Stackless depth-first walk of the implicit tree.  skip(lb) decides with the CURRENT state of the caller's result; leaves in
+// [skip_a, skip_b] were visited already (the kNN seed) and are not visited again.
+template <class Skip, class Visit>
+__device__ __forceinline__ void walk(const SearchTree& t, float qx, float qy, float qz, uint32_t skip_a, uint32_t skip_b, Skip skip, Visit visit)
+{
+    uint32_t node = 1;
+    while (true) {
+        if (node < t.P) {
+            if (!skip(box_lb(t.box, node, qx, qy, qz))) { node <<= 1; continue; }
+        } else {
+            const uint32_t l = node - t.P;
+            if (l < t.L && !(l >= skip_a && l <= skip_b) && !skip(box_lb(t.box, node, qx, qy, qz))) visit(l);
+        }
+        while (node & 1u) node >>= 1;      // a right child: climb until a left child (the root climbs to 0: done)
+        if (node == 0) break;
+        ++node;
+    }
+}
+
+// first position in the sorted codes whose code is >= key
+__device__ __forceinline__ uint32_t lower_bound_key(const uint64_t* __restrict__ keys, uint32_t n, uint64_t key)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// kNN seed: the leaves around the query's position in Morton order that hold at least kk points
+__device__ __forceinline__ void seed_leaves(const SearchTree& t, uint64_t qkey, uint32_t kk, uint32_t& a, uint32_t& b)
+{
+    const uint32_t p = lower_bound_key(t.keys, t.Mf, qkey);
+    const uint32_t half = kk / 2;
+    uint32_t start = p > half ? p - half : 0u;
+    if (start + kk > t.Mf) start = t.Mf - kk;
+    a = start / kSearchLeaf;
+    b = (start + kk - 1) / kSearchLeaf;
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------------------- build
+__global__ void __launch_bounds__(kBlock)
+k_search_bbox(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ out)      // out[0..6) ordered min xyz, max xyz; out[6] finite count
+{
+    uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u}, cnt = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float4 p = pts[i];
+        if (!finite3(p.x, p.y, p.z)) continue;
+        const uint32_t e[3] = {ord_f32(p.x), ord_f32(p.y), ord_f32(p.z)};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], e[d]); mx[d] = max(mx[d], e[d]); }
+        ++cnt;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], off)); mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], off)); }
+        cnt += (uint32_t)__shfl_xor((int)cnt, off);
+    }
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { atomicMin(&out[d], mn[d]); atomicMax(&out[3 + d], mx[d]); }
+        atomicAdd(&out[6], cnt);
+    }
+}
+hipError_t search_bbox(const float4* pts, size_t n, uint32_t* out7, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_search_bbox<<<dim3((unsigned)std::min<size_t>(grid_for(n, kBlock * 8), 1024)), dim3(kBlock), 0, s>>>(pts, n, out7);
+    return hipGetLastError();
+}
+float search_bbox_decode(uint32_t e)
+{
+    const uint32_t u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+__global__ void __launch_bounds__(kBlock)
+k_search_keys(const float4* __restrict__ pts, size_t n, SearchFrame f, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    keys[i] = search_key(f, p.x, p.y, p.z);
+    idx[i] = (uint32_t)i;
+}
+hipError_t search_keys(const float4* pts, size_t n, SearchFrame f, uint64_t* keys, uint32_t* idx, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_search_keys<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(pts, n, f, keys, idx);
+    return hipGetLastError();
+}
+
+// leaf boxes (node P + l); padding leaves get the empty box (+inf, -inf)
+__global__ void __launch_bounds__(kBlock)
+k_search_leaf_boxes(const float4* __restrict__ pts, uint32_t Mf, uint32_t L, uint32_t P, float4* __restrict__ box)
+{
+    const uint32_t l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= P) return;
+    const float inf = __builtin_inff();
+    float4 lo = make_float4(inf, inf, inf, 0.0f), hi = make_float4(-inf, -inf, -inf, 0.0f);
+    if (l < L) {
+        const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, Mf);
+        for (uint32_t j = a; j < b; ++j) {
+            const float4 p = pts[j];
+            lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
+            hi.x = fmaxf(hi.x, p.x); hi.y = fmaxf(hi.y, p.y); hi.z = fmaxf(hi.z, p.z);
+        }
+    }
+    box[2 * (P + l)] = lo;
+    box[2 * (P + l) + 1] = hi;
+}
+// one level of inner nodes [lvl, 2 lvl): union of the children's boxes
+__global__ void __launch_bounds__(kBlock)
+k_search_inner_boxes(uint32_t lvl, float4* __restrict__ box)
+{
+    const uint32_t v = lvl + blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= 2 * lvl) return;
+    const float4 l0 = box[4 * v], h0 = box[4 * v + 1], l1 = box[4 * v + 2], h1 = box[4 * v + 3];
+    box[2 * v] = make_float4(fminf(l0.x, l1.x), fminf(l0.y, l1.y), fminf(l0.z, l1.z), 0.0f);
+    box[2 * v + 1] = make_float4(fmaxf(h0.x, h1.x), fmaxf(h0.y, h1.y), fmaxf(h0.z, h1.z), 0.0f);
+}
+hipError_t search_tree_boxes(const float4* sorted_pts, uint32_t Mf, uint32_t L, uint32_t P, float4* box, hipStream_t s)
+{
+    if (!P) return hipSuccess;
+    k_search_leaf_boxes<<<dim3(grid_for(P)), dim3(kBlock), 0, s>>>(sorted_pts, Mf, L, P, box);
+    for (uint32_t lvl = P >> 1; lvl >= 1; lvl >>= 1) k_search_inner_boxes<<<dim3(grid_for(lvl)), dim3(kBlock), 0, s>>>(lvl, box);
+    return hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------------------- query order
+// queries sorted by their code under the index's frame: the lanes of a wavefront then walk the same part of the tree (temp: sort_temp_bytes(n))
+hipError_t search_query_order(const float4* query, size_t n, SearchFrame f, uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order,
+                              void* temp, size_t temp_bytes, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    hipError_t e = search_keys(query, n, f, keys, idx, s);
+    if (e != hipSuccess) return e;
+    return sort_pairs_u64(keys, keys_sorted, idx, order, n, 64, temp, temp_bytes, s);
+}
+
+// ----------------------------------------------------------------------------------------------------------- kNN
+// KT in {1, 2, 4, 8, 16}: the KT best (d2, index) pairs live in registers, kept sorted by an insertion network.  For kk < KT the first
+// KT - kk slots hold a sentinel of distance -1 that every candidate sorts after, so slot KT-1 is always the kk-th distance.
+template <int KT>
+__global__ void __launch_bounds__(kBlock)
+k_knn_search_reg(const float4* __restrict__ query, size_t n, const uint32_t* __restrict__ order, const uint64_t* __restrict__ qkeys_sorted,
+                 SearchTree t, int k, int kk, int32_t* __restrict__ out_idx, float* __restrict__ out_d2)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t qi = order[q];
+    const float4 qp = query[qi];
+    float bd[KT];
+    int bi[KT];
+#pragma unroll
+    for (int j = 0; j < KT; ++j) { const bool sent = j < KT - kk; bd[j] = sent ? -1.0f : __builtin_inff(); bi[j] = sent ? -1 : INT_MAX; }
+    const bool ok = kk > 0 && finite3(qp.x, qp.y, qp.z);
+    if (ok) {
+        auto push = [&](float d, int i) {
+            if (!pair_less(d, i, bd[KT - 1], bi[KT - 1])) return;
+#pragma unroll
+            for (int j = KT - 1; j > 0; --j) {
+                const bool before_prev = pair_less(d, i, bd[j - 1], bi[j - 1]);
+                const bool before_this = pair_less(d, i, bd[j], bi[j]);
+                const float nd = before_prev ? bd[j - 1] : (before_this ? d : bd[j]);
+                const int ni = before_prev ? bi[j - 1] : (before_this ? i : bi[j]);
+                bd[j] = nd; bi[j] = ni;
+            }
+            if (pair_less(d, i, bd[0], bi[0])) { bd[0] = d; bi[0] = i; }
+        };
+        auto visit = [&](uint32_t l) {
+            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
+            for (uint32_t j = a; j < b; ++j) {
+                const float4 p = t.pts[j];
+                push(sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z), (int)t.idx[j]);
+            }
+        };
+        uint32_t sa, sb;
+        seed_leaves(t, qkeys_sorted[q], (uint32_t)kk, sa, sb);
+        for (uint32_t l = sa; l <= sb; ++l) visit(l);
+        walk(t, qp.x, qp.y, qp.z, sa, sb, [&](double lb) { return lb > (double)bd[KT - 1]; }, visit);
+    }
+    int32_t* oi = out_idx + (size_t)qi * (size_t)k;
+    float* od = out_d2 + (size_t)qi * (size_t)k;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) {
+        const int r = j - (KT - kk);      // row position of slot j
+        if (r >= 0) { oi[r] = ok ? bi[j] : -1; od[r] = ok ? bd[j] : __builtin_inff(); }
+    }
+    for (int r = ok ? kk : 0; r < k; ++r) { oi[r] = -1; od[r] = __builtin_inff(); }
+}
+
+// 16 < k <= 64: the lists in LDS, [slot][lane] (one wavefront per workgroup: 64 x 64 x 8 B = 32 KB)
+static constexpr int kLdsBlock = 64;
+static constexpr int kMaxSearchK = 64;
+__global__ void __launch_bounds__(kLdsBlock)
+k_knn_search_lds(const float4* __restrict__ query, size_t n, const uint32_t* __restrict__ order, const uint64_t* __restrict__ qkeys_sorted,
+                 SearchTree t, int k, int kk, int32_t* __restrict__ out_idx, float* __restrict__ out_d2)
+{
+    __shared__ float sd[kMaxSearchK][kLdsBlock];
+    __shared__ int si[kMaxSearchK][kLdsBlock];
+    const int lane = (int)threadIdx.x;
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t qi = order[q];
+    const float4 qp = query[qi];
+    const bool ok = kk > 0 && finite3(qp.x, qp.y, qp.z);
+    int cnt = 0;
+    if (ok) {
+        float kth = __builtin_inff();
+        auto push = [&](float d, int i) {
+            int j;
+            if (cnt < kk) j = cnt++;
+            else if (pair_less(d, i, sd[kk - 1][lane], si[kk - 1][lane])) j = kk - 1;
+            else return;
+            while (j > 0 && pair_less(d, i, sd[j - 1][lane], si[j - 1][lane])) { sd[j][lane] = sd[j - 1][lane]; si[j][lane] = si[j - 1][lane]; --j; }
+            sd[j][lane] = d; si[j][lane] = i;
+            if (cnt == kk) kth = sd[kk - 1][lane];
+        };
+        auto visit = [&](uint32_t l) {
+            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
+            for (uint32_t j = a; j < b; ++j) {
+                const float4 p = t.pts[j];
+                push(sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z), (int)t.idx[j]);
+            }
+        };
+        uint32_t sa, sb;
+        seed_leaves(t, qkeys_sorted[q], (uint32_t)kk, sa, sb);
+        for (uint32_t l = sa; l <= sb; ++l) visit(l);
+        walk(t, qp.x, qp.y, qp.z, sa, sb, [&](double lb) { return lb > (double)kth; }, visit);
+    }
+    int32_t* oi = out_idx + (size_t)qi * (size_t)k;
+    float* od = out_d2 + (size_t)qi * (size_t)k;
+    for (int r = 0; r < cnt; ++r) { oi[r] = si[r][lane]; od[r] = sd[r][lane]; }
+    for (int r = cnt; r < k; ++r) { oi[r] = -1; od[r] = __builtin_inff(); }
+}
+
+hipError_t knn_search(const float4* query, size_t n, const uint32_t* order, const uint64_t* qkeys_sorted, SearchTree t, int k,
+                      int32_t* out_idx, float* out_d2, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    if (k < 1 || k > kMaxSearchK) return hipErrorInvalidValue;
+    const int kk = (int)std::min<size_t>((size_t)k, t.Mf);
+    if (k > 16) {
+        k_knn_search_lds<<<dim3(grid_for(n, kLdsBlock)), dim3(kLdsBlock), 0, s>>>(query, n, order, qkeys_sorted, t, k, kk, out_idx, out_d2);
+        return hipGetLastError();
+    }
+    auto launch = [&](auto kt) {
+        k_knn_search_reg<decltype(kt)::value><<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(query, n, order, qkeys_sorted, t, k, kk, out_idx, out_d2);
+    };
+    if (k == 1) launch(std::integral_constant<int, 1>{});
+    else if (k == 2) launch(std::integral_constant<int, 2>{});
+    else if (k <= 4) launch(std::integral_constant<int, 4>{});
+    else if (k <= 8) launch(std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 16>{});
+    return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------------------- radius
+// count pass: count[qi] = number of target points with d2 < r2 (0 for a non-finite query)
+__global__ void __launch_bounds__(kBlock)
+k_radius_count(const float4* __restrict__ query, size_t n, const uint32_t* __restrict__ order, SearchTree t, float r2, uint32_t* __restrict__ count)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t qi = order[q];
+    const float4 qp = query[qi];
+    uint32_t c = 0;
+    if (t.Mf && finite3(qp.x, qp.y, qp.z)) {
+        walk(t, qp.x, qp.y, qp.z, 1u, 0u, [&](double lb) { return lb >= (double)r2; }, [&](uint32_t l) {
+            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
+            for (uint32_t j = a; j < b; ++j) {
+                const float4 p = t.pts[j];
+                c += sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z) < r2 ? 1u : 0u;
+            }
+        });
+    }
+    count[qi] = c;
+}
+// fill pass: the same walk writes (d2 bits << 32 | index) of every hit at offsets[qi] (d2 >= 0: the bits order as the floats)
+__global__ void __launch_bounds__(kBlock)
+k_radius_fill(const float4* __restrict__ query, size_t n, const uint32_t* __restrict__ order, SearchTree t, float r2, const uint64_t* __restrict__ offsets,
+              uint64_t* __restrict__ pairs)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t qi = order[q];
+    const float4 qp = query[qi];
+    uint64_t o = offsets[qi];
+    const uint64_t end = offsets[qi + 1];
+    if (o == end) return;
+    walk(t, qp.x, qp.y, qp.z, 1u, 0u, [&](double lb) { return lb >= (double)r2; }, [&](uint32_t l) {
+        const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
+        for (uint32_t j = a; j < b; ++j) {
+            const float4 p = t.pts[j];
+            const float d = sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z);
+            if (d < r2 && o < end) pairs[o++] = ((uint64_t)__float_as_uint(d) << 32) | t.idx[j];
+        }
+    });
+}
+// row q: the first min(count, max_nn) pairs of the sorted row -> idx / d2 at out_off[q]
+__global__ void __launch_bounds__(kBlock)
+k_radius_split(size_t n, const uint64_t* __restrict__ full_off, const uint64_t* __restrict__ out_off, const uint64_t* __restrict__ sorted,
+               int32_t* __restrict__ out_idx, float* __restrict__ out_d2)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint64_t a = full_off[q], o = out_off[q], m = out_off[q + 1] - o;
+    for (uint64_t j = 0; j < m; ++j) {
+        const uint64_t v = sorted[a + j];
+        out_idx[o + j] = (int32_t)(uint32_t)v;
+        out_d2[o + j] = __uint_as_float((uint32_t)(v >> 32));
+    }
+}
+// off[0..n] = exclusive scan of min(count, cap) (cap 0 = no cap), total in off[n]
+struct CapCount {
+    uint32_t cap;
+    __host__ __device__ uint64_t operator()(uint32_t c) const { return (uint64_t)(cap && c > cap ? cap : c); }
+};
+__global__ void k_scan_tail(const uint32_t* __restrict__ count, size_t n, uint32_t cap, uint64_t* __restrict__ off)
+{
+    const uint32_t c = count[n - 1];
+    off[n] = off[n - 1] + (uint64_t)(cap && c > cap ? cap : c);
+}
+size_t radius_scan_temp_bytes(size_t n)
+{
+    size_t b = 0;
+    auto it = rocprim::make_transform_iterator((const uint32_t*)nullptr, CapCount{0});
+    (void)rocprim::exclusive_scan(nullptr, b, it, (uint64_t*)nullptr, (uint64_t)0, n, rocprim::plus<uint64_t>());
+    return std::max<size_t>(b, 16);
+}
+hipError_t radius_offsets(const uint32_t* count, size_t n, uint32_t cap, uint64_t* off, void* temp, size_t temp_bytes, hipStream_t s)
+{
+    if (!n) return hipMemsetAsync(off, 0, sizeof(uint64_t), s);
+    auto it = rocprim::make_transform_iterator(count, CapCount{cap});
+    hipError_t e = rocprim::exclusive_scan(temp, temp_bytes, it, off, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
+    if (e != hipSuccess) return e;
+    k_scan_tail<<<1, 1, 0, s>>>(count, n, cap, off);
+    return hipGetLastError();
+}
+hipError_t radius_count(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, uint32_t* count, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_radius_count<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(query, n, order, t, r2, count);
+    return hipGetLastError();
+}
+size_t radius_sort_temp_bytes(size_t total, size_t n)
+{
+    size_t b = 0;
+    (void)rocprim::segmented_radix_sort_keys(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned)total, (unsigned)n, (const uint64_t*)nullptr,
+                                             (const uint64_t*)nullptr, 0, 64);
+    return std::max<size_t>(b, 16);
+}
+hipError_t radius_fill(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, const uint64_t* full_off, uint64_t total_full,
+                       const uint64_t* out_off, uint64_t* pairs, uint64_t* pairs_sorted, int32_t* out_idx, float* out_d2, void* temp, size_t temp_bytes, hipStream_t s)
+{
+    if (!n || !total_full) return hipSuccess;
+    k_radius_fill<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(query, n, order, t, r2, full_off, pairs);
+    hipError_t e = rocprim::segmented_radix_sort_keys(temp, temp_bytes, pairs, pairs_sorted, (unsigned)total_full, (unsigned)n, full_off, full_off + 1, 0, 64, s);
+    if (e != hipSuccess) return e;
+    k_radius_split<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(n, full_off, out_off, pairs_sorted, out_idx, out_d2);
+    return hipGetLastError();
+}
+
+// rows of an empty target / of no query at all: index -1, distance +inf
+__global__ void __launch_bounds__(kBlock)
+k_knn_empty_rows(size_t n, int32_t* __restrict__ idx, float* __restrict__ d2)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { idx[i] = -1; d2[i] = __builtin_inff(); }
+}
+hipError_t knn_empty_rows(size_t n, int32_t* idx, float* d2, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_knn_empty_rows<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(n, idx, d2);
+    return hipGetLastError();
+}
+
+} // namespace ltm

@@ -220,4 +220,32 @@ hipError_t knn_query_cloud(const float4* query, size_t Q, const float4* sorted_t
                            const HashEntry* table, uint32_t table_mask, int k, float thr, float cell2_lo,
                            uint8_t* near, hipStream_t s);
 
+// ---- exact k-NN / radius search index (ltm_k_search.hip) ----
+static constexpr int kSearchLeaf = 32;          // target points per leaf of the box tree
+// Morton frame of the index: 21 bits per axis, q = floor((v - o) * scale) clamped to [0, 2^21)
+struct SearchFrame { double ox, oy, oz, scale; };
+// finite target points in Morton order (pts, their input indices idx, their codes keys), Mf of them, L = ceil(Mf / kSearchLeaf) leaves,
+// P = L rounded up to a power of two; box: 2 float4 (lo, hi) per node of the implicit tree, nodes 1 .. 2P-1, leaf l = node P + l
+struct SearchTree { const float4* pts; const uint32_t* idx; const uint64_t* keys; const float4* box; uint32_t Mf, L, P; };
+// out7: {ordered-uint min xyz, max xyz, finite count}, initialised by the caller to {~0 x3, 0 x3, 0}; non-finite points are left out
+hipError_t search_bbox(const float4* pts, size_t n, uint32_t* out7, hipStream_t s);
+float      search_bbox_decode(uint32_t enc);
+hipError_t search_keys(const float4* pts, size_t n, SearchFrame f, uint64_t* keys, uint32_t* idx, hipStream_t s);    // non-finite: key ~0
+hipError_t search_tree_boxes(const float4* sorted_pts, uint32_t Mf, uint32_t L, uint32_t P, float4* box, hipStream_t s);
+// queries in code order (temp: sort_temp_bytes(n)): order[j] = input index of the j-th query, keys_sorted[j] its code
+hipError_t search_query_order(const float4* query, size_t n, SearchFrame f, uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order,
+                              void* temp, size_t temp_bytes, hipStream_t s);
+// rows of k (1 <= k <= 64) at idx / d2 + input index * k
+hipError_t knn_search(const float4* query, size_t n, const uint32_t* order, const uint64_t* qkeys_sorted, SearchTree t, int k,
+                      int32_t* out_idx, float* out_d2, hipStream_t s);
+hipError_t knn_empty_rows(size_t n, int32_t* idx, float* d2, hipStream_t s);
+hipError_t radius_count(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, uint32_t* count, hipStream_t s);
+size_t     radius_scan_temp_bytes(size_t n);
+// off[0..n]: exclusive scan of min(count, cap) (cap 0: no cap) and the total
+hipError_t radius_offsets(const uint32_t* count, size_t n, uint32_t cap, uint64_t* off, void* temp, size_t temp_bytes, hipStream_t s);
+size_t     radius_sort_temp_bytes(size_t total, size_t n);
+// every hit into pairs (rows at full_off), rows sorted by (d2, index), the first out_off[q+1] - out_off[q] of each row into out_idx / out_d2
+hipError_t radius_fill(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, const uint64_t* full_off, uint64_t total_full,
+                       const uint64_t* out_off, uint64_t* pairs, uint64_t* pairs_sorted, int32_t* out_idx, float* out_d2, void* temp, size_t temp_bytes, hipStream_t s);
+
 } // namespace ltm
