@@ -299,6 +299,67 @@ int ltm_search_result_info(ltm_ctx*, ltm_search_result*, size_t* n_query, size_t
                            const uint64_t** offsets_dev, const int32_t** idx_dev, const float** d2_dev);
 int ltm_search_result_free(ltm_ctx*, ltm_search_result*);
 
+/* ----------------------------------------------------------- scan context ---- */
+/* Scan Context place recognition, the step of the reference that decides which keyframes of two sessions see the same place before LT-removert diffs
+ * them: SCManager (ltslam/src/Scancontext.cpp:69-324, ltslam/include/ltslam/Scancontext.h:58-121) as LTslam::detectInterSessionSCloops drives it
+ * (ltslam/src/LTslam.cpp:304-333).  A descriptor set holds N descriptors (num_ring x num_sector doubles, row-major [ring][sector]) with their ring keys
+ * (float), sector keys (double) and column norms on the device.  What this library takes the reference to do:
+ *  - bin of a point (:166-179): r = (float)sqrt(x*x + y*y), the sum in float without fused multiply-add (a float sqrtf and a double sqrt rounded to float
+ *    agree here); theta = xy2theta (:23-36) with the quotient in float, atan in DOUBLE, the four quadrant forms in double, the result rounded to float.
+ *    (An unqualified atan of a float could also resolve to the float overload, depending on what the reference's includes pull in; the two readings differ
+ *    only for points within rounding of a sector edge.  The device's double atan may differ from glibc's in the last bits, which moves the float theta of
+ *    about one point in 10^8.)  ring = clamp(int(ceil(r / max_radius * num_ring)), 1, num_ring) in double, sector likewise from theta / 360.0.  Points with
+ *    r > max_radius are skipped.
+ *  - quirks, mirrored as x86 gives them: x == 0 && y == 0 has a NaN quotient whose int conversion is INT_MIN, so the point lands in sector 1, ring 1;
+ *    x == -0.0f takes the x >= 0 branches.  A point with a non-finite coordinate is SKIPPED (undefined behaviour in the reference: its bin index is garbage).
+ *  - height (:168, :182-190): value = (float)((double)z + lidar_height), stored as a double; a bin holds the maximum over its points starting from -1000, and
+ *    a bin still at -1000 at the end becomes 0 -- bins whose every point had a value <= -1000 included.  Negative heights are legal and win against -1000.
+ *    (-0.0 and +0.0 compare equal in the reference and the first in point order stays; here +0.0 stays.)
+ *  - keys (:198-246): ring key = row mean in double, stored as float (eig2stdvec); sector key = column mean in double.  Sums run in index order; Eigen's
+ *    order is not specified, so the last bits of a mean may differ.
+ *  - distDirectSC (:69-90): all in double; a column pair is skipped when either norm is 0; if no column counts the distance is NaN, as the reference gives.
+ *  - distanceBtnScanContext (:116-148): the FIRST minimal sector-key shift wins (strict <, ascending shift); search radius = round(0.5 * search_ratio *
+ *    num_sector) around it (search_ratio >= 1: every shift); the shift set is visited in ascending order and the first minimum wins; if every distance is NaN
+ *    the result is (10000000, 0).
+ *  - detect (:263-324): candidates are the num_candidates nearest ring keys under nanoflann's L2_Adaptor in float -- groups of four,
+ *    result += d0*d0 + d1*d1 + d2*d2 + d3*d3, then the tail -- found by brute force; TIES GO TO THE SMALLER INDEX (nanoflann leaves this unspecified; a NaN
+ *    key distance sorts last).  num_candidates is clamped to the database size (the reference reads uninitialised indices there); 0 = every database entry.
+ *    Candidates are visited in ascending (key distance, index) order and the first minimal distance wins.  loop_id = nn_idx if min_dist < dist_thres, else -1.
+ *    yaw_diff_rad = deg2rad(nn_align * (360.0 / num_sector)) as :17-20 and :319 compute it: the degrees rounded to float (deg2rad's parameter), times M_PI,
+ *    divided by 180.0 in double, rounded to float.  An empty database gives loop_id -1, nn_idx 0, min_dist 10000000, nn_align 0 for every query.
+ * Domain: 1 <= num_ring <= 64, 1 <= num_sector <= 256, num_candidates <= 64 unless it reaches the database size, and in one ltm_sc_detect
+ * n_query x n_database < 2^31 (the ring-key distances of all of them are held at once, 4 bytes each) (LTM_E_UNSUPPORTED beyond; LTM_E_INVALID for
+ * values that make no sense: counts < 1, max_radius <= 0, negative search_ratio, non-finite values).  A NULL parameter pointer means the defaults.  In
+ * ltm_sc_distance / ltm_sc_detect the parameters' num_ring / num_sector must be those of the handles, and two handles with different counts are
+ * LTM_E_INVALID.  Handles belong to the context that made them (another context, a lane included, gets LTM_E_INVALID); memory comes from the context's pool;
+ * ltm_destroy releases whatever is still open.  ltm_sc_from_scanset is asynchronous on the context's stream; the calls that read or write host arrays return
+ * when those are done. */
+typedef struct ltm_sc ltm_sc;
+typedef struct {
+    double lidar_height;    /* 2.0   LIDAR_HEIGHT, Scancontext.h:84 */
+    int    num_ring;        /* 20    PC_NUM_RING, 1..64 */
+    int    num_sector;      /* 60    PC_NUM_SECTOR, 1..256 */
+    double max_radius;      /* 80.0  PC_MAX_RADIUS */
+    int    num_candidates;  /* 3     NUM_CANDIDATES_FROM_TREE; 0 = every database entry (exhaustive) */
+    double search_ratio;    /* 0.1   SEARCH_RATIO; >= 1.0 = every shift */
+    double dist_thres;      /* 0.3   SC_DIST_THRES */
+} ltm_sc_params;
+void ltm_sc_default_params(ltm_sc_params*);      /* host only, needs no device */
+/* makeAndSaveScancontextAndKeys (:249-260) for every keyframe of [kf_begin, kf_end) of a scan set */
+int  ltm_sc_from_scanset(ltm_ctx*, ltm_scanset, size_t kf_begin, size_t kf_end, const ltm_sc_params*, ltm_sc** out);
+/* saveScancontextAndKeys (:236-246) for n descriptors read elsewhere (the SCD files of LTslam.cpp): desc_host is n x num_ring x num_sector, row-major */
+int  ltm_sc_from_descriptors(ltm_ctx*, const double* desc_host, size_t n, const ltm_sc_params*, ltm_sc** out);
+int  ltm_sc_info(ltm_ctx*, ltm_sc*, size_t* n, int* num_ring, int* num_sector);
+/* descriptors (n x ring x sector), ring keys (n x ring), sector keys (n x sector) into host arrays; any may be NULL */
+int  ltm_sc_download(ltm_ctx*, ltm_sc*, double* desc, float* ring_keys, double* sector_keys);
+/* distanceBtnScanContext(a[i], b[j]) (:116-148) for n_pairs pairs (i, j) = pairs_host[2k], pairs_host[2k + 1]; reads search_ratio; outputs may be NULL */
+int  ltm_sc_distance(ltm_ctx*, ltm_sc* a, ltm_sc* b, const int32_t* pairs_host, size_t n_pairs, const ltm_sc_params*, double* dist_host, int32_t* shift_host);
+/* detectLoopClosureIDBetweenSession (:263-324) for every descriptor of `queries` against `database`; reads num_candidates, search_ratio, dist_thres; host
+ * outputs of n_query entries each, any may be NULL */
+int  ltm_sc_detect(ltm_ctx*, ltm_sc* database, ltm_sc* queries, const ltm_sc_params*, int32_t* loop_id, int32_t* nn_idx, double* min_dist, int32_t* nn_align,
+                   float* yaw_diff_rad);
+int  ltm_sc_free(ltm_ctx*, ltm_sc*);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections

@@ -28,6 +28,12 @@ class LtmConfig(C.Structure):
                 ("device", C.c_int), ("max_kf_batch", C.c_int)]
 
 
+class ScParams(C.Structure):
+    """ltm_sc_params (Scancontext.h:84-99)"""
+    _fields_ = [("lidar_height", C.c_double), ("num_ring", C.c_int), ("num_sector", C.c_int), ("max_radius", C.c_double),
+                ("num_candidates", C.c_int), ("search_ratio", C.c_double), ("dist_thres", C.c_double)]
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/ltm.h
 _vp, _sz, _u64, _i, _f = C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_float
 _pu64 = C.POINTER(C.c_uint64)
@@ -118,6 +124,14 @@ SIGNATURES = {
     "ltm_radius_search": (_i, [_vp, _vp, _u64, _f, _i, C.POINTER(_vp)]),
     "ltm_search_result_info": (_i, [_vp, _vp, _psz, _psz, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "ltm_search_result_free": (_i, [_vp, _vp]),
+    "ltm_sc_default_params": (None, [C.POINTER(ScParams)]),
+    "ltm_sc_from_scanset": (_i, [_vp, _u64, _sz, _sz, C.POINTER(ScParams), C.POINTER(_vp)]),
+    "ltm_sc_from_descriptors": (_i, [_vp, _vp, _sz, C.POINTER(ScParams), C.POINTER(_vp)]),
+    "ltm_sc_info": (_i, [_vp, _vp, _psz, C.POINTER(_i), C.POINTER(_i)]),
+    "ltm_sc_download": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "ltm_sc_distance": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(ScParams), _vp, _vp]),
+    "ltm_sc_detect": (_i, [_vp, _vp, _vp, C.POINTER(ScParams), _vp, _vp, _vp, _vp, _vp]),
+    "ltm_sc_free": (_i, [_vp, _vp]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -478,6 +492,24 @@ class Context:
         self._ck(self.lib.ltm_search_build(self.h, cloud.h, C.byref(h)))
         return SearchIndex(self, h.value)
 
+    # ---- scan context
+    def scan_contexts(self, scans, kf_begin=0, kf_end=None, **params):
+        """ltm_sc_from_scanset: Scan Context descriptors and keys of keyframes [kf_begin, kf_end) of a ScanSet (makeAndSaveScancontextAndKeys per
+        keyframe); params: the fields of ltm_sc_params, the reference's values by default"""
+        p = sc_params(**params)
+        h = _vp()
+        ke = scans.n_kf if kf_end is None else kf_end
+        self._ck(self.lib.ltm_sc_from_scanset(self.h, scans.h, kf_begin, ke, C.byref(p), C.byref(h)))
+        return ScanContexts(self, h.value, p)
+
+    def scan_contexts_from(self, desc, **params):
+        """ltm_sc_from_descriptors: a descriptor set from (n, num_ring, num_sector) float64 descriptors made elsewhere (saveScancontextAndKeys)"""
+        p = sc_params(**params)
+        d = np.ascontiguousarray(desc, dtype=np.float64).reshape(-1, p.num_ring, p.num_sector)
+        h = _vp()
+        self._ck(self.lib.ltm_sc_from_descriptors(self.h, d.ctypes.data, d.shape[0], C.byref(p), C.byref(h)))
+        return ScanContexts(self, h.value, p)
+
     # ---- debug / parity
     def pool_live(self):
         """ltm_debug_pool_live: (blocks, bytes) of the device pool that are handed out"""
@@ -651,6 +683,85 @@ class SearchIndex:
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.ltm_search_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sc_params(**over):
+    """ltm_sc_params: ltm_sc_default_params with the given fields replaced"""
+    p = ScParams()
+    load_library().ltm_sc_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in dict(ScParams._fields_):
+            raise TypeError(f"ltm_sc_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+class ScanContexts:
+    """ltm_sc: N device-resident Scan Context descriptors with their ring and sector keys (semantics in include/ltm.h, "scan context").  The
+    parameters it was made with are the defaults of distance() / detect(); keyword arguments replace single fields for one call."""
+
+    def __init__(self, ctx, h, params):
+        self.ctx, self.h, self.params = ctx, h, params
+
+    def _params(self, over):
+        p = ScParams.from_buffer_copy(self.params)
+        for k, v in over.items():
+            if k not in dict(ScParams._fields_):
+                raise TypeError(f"ltm_sc_params has no field {k!r}")
+            setattr(p, k, v)
+        return p
+
+    def info(self):
+        """(descriptors, num_ring, num_sector)"""
+        n, r, s = C.c_size_t(), _i(), _i()
+        self.ctx._ck(self.ctx.lib.ltm_sc_info(self.ctx.h, self.h, C.byref(n), C.byref(r), C.byref(s)))
+        return n.value, r.value, s.value
+
+    def __len__(self):
+        return self.info()[0]
+
+    def download(self):
+        """(descriptors float64 [n, ring, sector], ring keys float32 [n, ring], sector keys float64 [n, sector])"""
+        n, r, s = self.info()
+        desc, rk, sk = np.empty((n, r, s), np.float64), np.empty((n, r), np.float32), np.empty((n, s), np.float64)
+        self.ctx._ck(self.ctx.lib.ltm_sc_download(self.ctx.h, self.h, desc.ctypes.data, rk.ctypes.data, sk.ctypes.data))
+        return desc, rk, sk
+
+    def distance(self, other, pairs, **params):
+        """distanceBtnScanContext(self[i], other[j]) for every row (i, j) of `pairs`: (dist float64 [n], shift int32 [n])"""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        p = self._params(params)
+        dist, shift = np.empty(len(pr), np.float64), np.empty(len(pr), np.int32)
+        self.ctx._ck(self.ctx.lib.ltm_sc_distance(self.ctx.h, self.h, other.h, pr.ctypes.data, len(pr), C.byref(p), dist.ctypes.data, shift.ctypes.data))
+        return dist, shift
+
+    def detect(self, queries, **params):
+        """detectLoopClosureIDBetweenSession of every descriptor of `queries` against this set (the database): dict of arrays with one entry per
+        query -- loop_id, nn_idx, nn_align (int32), min_dist (float64), yaw_diff_rad (float32)"""
+        p = self._params(params)
+        n = len(queries)
+        out = {"loop_id": np.empty(n, np.int32), "nn_idx": np.empty(n, np.int32), "min_dist": np.empty(n, np.float64),
+               "nn_align": np.empty(n, np.int32), "yaw_diff_rad": np.empty(n, np.float32)}
+        self.ctx._ck(self.ctx.lib.ltm_sc_detect(self.ctx.h, self.h, queries.h, C.byref(p), *[out[k].ctypes.data for k in
+                                                                                             ("loop_id", "nn_idx", "min_dist", "nn_align", "yaw_diff_rad")]))
+        return out
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ltm_sc_free(self.ctx.h, self.h)
         self.h = None
 
     def __enter__(self):

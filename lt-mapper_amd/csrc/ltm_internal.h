@@ -327,6 +327,7 @@ struct ltm_ctx {
     std::vector<struct ltm_vgs*> vgs_open;      // ltm_voxel_grid_scanset_begin tickets not ended yet: joined and released by ltm_destroy at the latest
     std::vector<struct ltm_search*> search_open;            // search indices and radius results not freed yet: released by ltm_destroy at the latest
     std::vector<struct ltm_search_result*> result_open;
+    std::vector<struct ltm_sc*> sc_open;                    // scan-context descriptor sets not freed yet: released by ltm_destroy at the latest
 };
 
 namespace ltm_detail {
@@ -637,6 +638,7 @@ void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
 void vgs_release_all(ltm_ctx* c);                                                 // ltm_api_voxel.cpp: open ltm_voxel_grid_scanset tickets, at ltm_destroy
 void search_release_all(ltm_ctx* c);                                              // ltm_api_search.cpp: open search indices and results, at ltm_destroy
+void sc_release_all(ltm_ctx* c);                                                  // ltm_api_scancontext.cpp: open descriptor sets, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp
 

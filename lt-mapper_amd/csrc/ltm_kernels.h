@@ -248,4 +248,23 @@ size_t     radius_sort_temp_bytes(size_t total, size_t n);
 hipError_t radius_fill(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, const uint64_t* full_off, uint64_t total_full,
                        const uint64_t* out_off, uint64_t* pairs, uint64_t* pairs_sorted, int32_t* out_idx, float* out_d2, void* temp, size_t temp_bytes, hipStream_t s);
 
+// ---- scan context (ltm_k_scancontext.hip; Scancontext.cpp:69-324) ----
+struct ScGeom { double lidar_height, max_radius; int R, S; };      // rings x sectors
+// makeScancontext for keyframes [kb, kb + nb): bins (zeroed by the caller, R * S uint32 per keyframe) receive the order-preserving key of the largest
+// height of every bin; sc_finish turns them into the descriptor
+hipError_t sc_scatter(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t max_kf_pts, ScGeom g, uint32_t* bins, hipStream_t s);
+// n descriptors (row-major R x S doubles): heights from `bins` (nullptr: desc is given), ring keys (n x R float), sector keys and column norms (n x S double)
+hipError_t sc_finish(const uint32_t* bins, size_t n, int R, int S, double* desc, float* ring_keys, double* sector_keys, double* norms, hipStream_t s);
+// rd[q * nd + j] = nanoflann L2 distance (float) between ring key q of the queries and ring key j of the database
+hipError_t sc_ring_distances(const float* qk, size_t nq, const float* dbk, size_t nd, int R, float* rd, hipStream_t s);
+// pairs[(q * K + k) * 2] = {q, the k-th nearest database entry of query q by (rd, index)}; 1 <= K <= nd
+hipError_t sc_candidates(const float* rd, size_t nq, size_t nd, int K, int32_t* pairs, hipStream_t s);
+// (distance, shift) of distanceBtnScanContext(A[i], B[j]) for n_pairs (< 2^31) pairs (i, j) = pairs[2p], pairs[2p + 1], or (p / nd, p % nd) if pairs is null;
+// radius: half-width of the shift search space around the sector-key alignment (>= S / 2: every shift)
+hipError_t sc_pair_distance(const double* descA, const double* skA, const double* nrmA, const double* descB, const double* skB, const double* nrmB, int R, int S,
+                            const int32_t* pairs, size_t nd, size_t n_pairs, int radius, double* dist, int32_t* shift, hipStream_t s);
+// per query the best of its K consecutive pairs (candidate index pairs[2p + 1], or k if pairs is null): smallest distance, then (rd, index)
+hipError_t sc_detect_reduce(const double* dist, const int32_t* shift, const int32_t* pairs, const float* rd, size_t nq, size_t nd, size_t K,
+                            int32_t* nn_idx, double* min_dist, int32_t* nn_align, hipStream_t s);
+
 } // namespace ltm
