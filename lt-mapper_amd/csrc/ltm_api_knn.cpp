@@ -46,10 +46,7 @@ struct KnnIndex {
         LTM_HIP(gather_points(target.d, idx2.as<uint32_t>(), Mt, sorted, c->stream));
         DevBuf heads(c, Mt), pos(c, Mt * 4);
         LTM_HIP(head_flags(keys2.as<uint64_t>(), Mt, heads.as<uint8_t>(), c->stream));
-        const size_t tb = scan_temp_bytes(Mt);
-        DevBuf temp(c, tb);
-        LTM_HIP(exclusive_scan_u8(heads.as<uint8_t>(), pos.as<uint32_t>(), Mt, temp.p, tb, c->stream));
-        const size_t ncell = scan_total_u8(c, heads.as<uint8_t>(), pos.as<uint32_t>(), Mt);
+        const size_t ncell = count_flags(c, heads.as<uint8_t>(), Mt, pos);
         DevBuf starts(c, ncell * 4);
         LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), Mt, starts.as<uint32_t>(), c->stream));
         size_t tsize = 1024;
@@ -87,9 +84,7 @@ void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n,
     size_t nset = 0;
     if (n) {
         DevBuf pos(c, n * 4);
-        const size_t tb = scan_temp_bytes(n);
-        DevBuf temp(c, tb);
-        LTM_HIP(exclusive_scan_u8(flag, pos.as<uint32_t>(), n, temp.p, tb, c->stream));
+        scan_flags(c, flag, n, pos);
         DevBuf bout(c, (nb + 1) * 4);      // per-keyframe boundaries and the total in one small array: one host round trip
         LTM_HIP(flag_bounds(pos.as<uint32_t>(), flag, n, offsets_dev, kf0, first, nb, bout.as<uint32_t>(), c->stream));
         std::vector<uint32_t> b(nb + 1);

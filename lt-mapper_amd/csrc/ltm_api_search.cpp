@@ -50,20 +50,12 @@ void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
     LTM_REQUIRE(n < 0x80000000ull, "the target must have fewer than 2^31 points");
     if (!n) return;
     ProfScope p(c, "search_build", (double)n, 48.0 * n);
-    DevBuf bb(c, 8 * sizeof(uint32_t));
-    const uint32_t init[8] = {~0u, ~0u, ~0u, 0u, 0u, 0u, 0u, 0u};
-    h2d(c, bb.p, init, sizeof(init));
-    LTM_HIP(search_bbox(target.d, n, bb.as<uint32_t>(), c->stream));
-    uint32_t got[8];
-    d2h(c, got, bb.p, sizeof(got));
-    s->Mf = got[6];
+    float mn[3], mx[3];
+    s->Mf = read_box(c, mn, mx, [&](uint32_t* bb) { return search_bbox(target.d, n, bb, c->stream); });
     if (!s->Mf) return;
-    double mn[3], ext = 0.0;
-    for (int d = 0; d < 3; ++d) {
-        mn[d] = (double)search_bbox_decode(got[d]);
-        ext = std::max(ext, (double)search_bbox_decode(got[3 + d]) - mn[d]);
-    }
-    s->f = SearchFrame{mn[0], mn[1], mn[2], ext > 0.0 ? 2097151.0 / ext : 0.0};
+    double ext = 0.0;
+    for (int d = 0; d < 3; ++d) ext = std::max(ext, (double)mx[d] - (double)mn[d]);
+    s->f = SearchFrame{(double)mn[0], (double)mn[1], (double)mn[2], ext > 0.0 ? 2097151.0 / ext : 0.0};
     // codes of every point (non-finite: ~0, sorted behind the finite ones) -> the first Mf entries of the sorted arrays are the index
     DevBuf keys(c, n * 8), idx(c, n * 4);
     s->keys = reinterpret_cast<uint64_t*>(c->pool.alloc(n * 8));

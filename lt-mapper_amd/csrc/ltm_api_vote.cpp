@@ -339,11 +339,8 @@ void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud
         return;
     }
     DevBuf pos(c, n * sizeof(uint32_t));
-    const size_t tb = scan_temp_bytes(n);
-    DevBuf temp(c, tb);
     ProfScope p(c, "partition", (double)n, (double)n * (16 + 1 + 4 + 4 + 16));
-    LTM_HIP(exclusive_scan_u8(labels, pos.as<uint32_t>(), n, temp.p, tb, c->stream));
-    const size_t nf = scan_total_u8(c, labels, pos.as<uint32_t>(), n);
+    const size_t nf = count_flags(c, labels, n, pos);
     float4 *dk = nullptr, *df = nullptr;
     ltm_cloud hk = 0, hf = 0;
     if (kept) hk = alloc_cloud(c, n - nf, &dk);

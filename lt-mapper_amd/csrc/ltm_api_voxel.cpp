@@ -72,12 +72,7 @@ KeyCompress key_compress_for(const float mn[3], const float mx[3], const OctreeF
 
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3])
 {
-    DevBuf bb(c, 8 * sizeof(uint32_t));
-    LTM_HIP(bbox_init(bb.as<uint32_t>(), c->stream));
-    LTM_HIP(bbox_reduce(pts, n, bb.as<uint32_t>(), c->stream));
-    uint32_t enc[8];
-    d2h(c, enc, bb.p, sizeof enc);
-    for (int d = 0; d < 3; ++d) { mn[d] = bbox_decode(enc[d]); mx[d] = bbox_decode(enc[3 + d]); }
+    read_box(c, mn, mx, [&](uint32_t* bb) { return bbox_reduce(pts, n, bb, c->stream); });
 }
 bool same_frame(const OctreeFrame& a, const OctreeFrame& b)
 {
@@ -95,9 +90,7 @@ void voxel_segments(ltm_ctx* c, const uint64_t* keys2, size_t n, unsigned kshift
     }
     DevBuf heads(c, n), pos(c, n * 4);
     LTM_HIP(head_flags(keys2, n, heads.as<uint8_t>(), c->stream, kshift));
-    const size_t tb = scan_temp_bytes(n);
-    DevBuf temp(c, tb);
-    LTM_HIP(exclusive_scan_u8(heads.as<uint8_t>(), pos.as<uint32_t>(), n, temp.p, tb, c->stream));
+    scan_flags(c, heads.as<uint8_t>(), n, pos);
     LTM_HIP(scan_total_to(heads.as<uint8_t>(), pos.as<uint32_t>(), n, count_dev, c->stream));
     LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), n, starts, c->stream));
 }
@@ -121,13 +114,7 @@ size_t voxel_centroid_raw(ltm_ctx* c, const float4* pts, size_t n_in, float leaf
     float mn[3], mx[3];
     bool untouched = false;
     if (cached && c->voxel_identity && n_shards == 1) {
-        DevBuf bb(c, 8 * sizeof(uint32_t));
-        LTM_HIP(bbox_init(bb.as<uint32_t>(), c->stream));
-        LTM_HIP(bbox_reduce_check(pts, n_in, *cached, bb.as<uint32_t>(), c->stream));
-        uint32_t enc[8];
-        d2h(c, enc, bb.p, sizeof enc);
-        for (int d = 0; d < 3; ++d) { mn[d] = bbox_decode(enc[d]); mx[d] = bbox_decode(enc[3 + d]); }
-        untouched = enc[6] == 0;
+        untouched = read_box(c, mn, mx, [&](uint32_t* bb) { return bbox_reduce_check(pts, n_in, *cached, bb, c->stream); }) == 0;
     } else if (box_mn && box_mx) {      // the bounding box of a LARGER cloud this one is a part of (key-range exchange, ltm_voxel_centroid_box)
         for (int d = 0; d < 3; ++d) { mn[d] = box_mn[d]; mx[d] = box_mx[d]; }
     } else bbox_of(c, pts, n_in, mn, mx);
@@ -179,10 +166,7 @@ size_t voxel_centroid_raw(ltm_ctx* c, const float4* pts, size_t n_in, float leaf
         const uint64_t hi = (shard + 1 >= n_shards) ? ~0ull : bound(cut(shard + 1));
         DevBuf flags(c, n), pos(c, n * 4);
         LTM_HIP(key_range_flags(keys.as<uint64_t>(), n, lo, hi, flags.as<uint8_t>(), c->stream));
-        const size_t tb = scan_temp_bytes(n);
-        DevBuf temp(c, tb);
-        LTM_HIP(exclusive_scan_u8(flags.as<uint8_t>(), pos.as<uint32_t>(), n, temp.p, tb, c->stream));
-        const size_t nsel = scan_total_u8(c, flags.as<uint8_t>(), pos.as<uint32_t>(), n);
+        const size_t nsel = count_flags(c, flags.as<uint8_t>(), n, pos);
         if (nsel == 0) return 0;
         DevBuf ck(c, nsel * 8), ci(c, packed ? 8 : nsel * 4);
         if (packed) LTM_HIP(compact_keys(keys.as<uint64_t>(), flags.as<uint8_t>(), pos.as<uint32_t>(), n, ck.as<uint64_t>(), c->stream));
@@ -260,7 +244,7 @@ void voxel_centroid_batch_impl(ltm_ctx* c, std::vector<VoxelJob>& jobs)
         if (j.n == 0) { LTM_HIP(hipMemsetAsync(counts.as<uint32_t>() + k, 0, 4, c->stream)); continue; }
         ++c->voxel_calls;
         float mn[3], mx[3];
-        for (int d = 0; d < 3; ++d) { mn[d] = bbox_decode(enc[8 * k + d]); mx[d] = bbox_decode(enc[8 * k + 3 + d]); }
+        decode_box(&enc[8 * k], mn, mx);
         if (!octree_frame_from_bbox(mn, mx, j.leaf, &j.f)) throw Err{LTM_E_UNSUPPORTED, "octree depth > 21 (extent / leaf too large)"};
         if (j.has_cached && c->voxel_identity && enc[8 * k + 6] == 0 && same_frame(j.f, j.cached)) {      // see voxel_centroid_raw
             j.identity = true;
@@ -514,7 +498,7 @@ int ltm_voxel_centroid_scanset(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_scan
             frames[k] = OctreeFrame{0, 0, 0, (double)leaf, 1};
             if (s.off[k + 1] == s.off[k]) continue;
             float mn[3], mx[3];
-            for (int d = 0; d < 3; ++d) { mn[d] = bbox_decode(enc[6 * k + d]); mx[d] = bbox_decode(enc[6 * k + 3 + d]); }
+            decode_box(&enc[6 * k], mn, mx);
             if (!octree_frame_from_bbox(mn, mx, leaf, &frames[k])) throw Err{LTM_E_UNSUPPORTED, "octree depth > 21 (extent / leaf too large)"};
             dmax = std::max(dmax, frames[k].depth);
         }
@@ -533,10 +517,7 @@ int ltm_voxel_centroid_scanset(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_scan
         }
         DevBuf heads(c, n), pos(c, n * 4);
         LTM_HIP(head_flags(keys2.as<uint64_t>(), n, heads.as<uint8_t>(), c->stream));
-        const size_t tb = scan_temp_bytes(n);
-        DevBuf temp(c, tb);
-        LTM_HIP(exclusive_scan_u8(heads.as<uint8_t>(), pos.as<uint32_t>(), n, temp.p, tb, c->stream));
-        const size_t nvox = scan_total_u8(c, heads.as<uint8_t>(), pos.as<uint32_t>(), n);
+        const size_t nvox = count_flags(c, heads.as<uint8_t>(), n, pos);
         // the sort key leads with the keyframe id, so keyframe k still occupies sorted positions [off[k], off[k+1])
         DevBuf bout(c, (nk + 1) * 4);
         LTM_HIP(gather_u32(pos.as<uint32_t>(), s.off_dev, nk + 1, n, (uint32_t)nvox, bout.as<uint32_t>(), c->stream));
@@ -616,9 +597,9 @@ void vgs_begin(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_vgs** ticket)
         for (int d = 0; d < 3; ++d) { f.min_b[d] = 0; f.div_b[d] = 1; }
         if (s.off[k + 1] == s.off[k]) continue;
         float mn[3], mx[3];
+        decode_box(&enc[6 * k], mn, mx);
         int64_t cells = 1;
         for (int d = 0; d < 3; ++d) {
-            mn[d] = bbox_decode(enc[6 * k + d]); mx[d] = bbox_decode(enc[6 * k + 3 + d]);
             const float ext = (mx[d] - mn[d]) * inv;
             cells *= (int64_t)ext + 1;
         }
@@ -717,7 +698,7 @@ void vgs_end(ltm_ctx* c, ltm_vgs* v, ltm_scanset* out)
         if (v->failed) throw Err{LTM_E_DEVICE, "voxel_grid_scanset: the host order of the keys failed (keys transfer or worker threads)"};
         const auto t_joined = std::chrono::steady_clock::now();
         LTM_HIP(hipMemcpyAsync(idx2.p, v->hi, n * 4, hipMemcpyHostToDevice, c->stream));
-        LTM_HIP(gather_u64_by_u32(v->keys->as<uint64_t>(), idx2.as<uint32_t>(), n, keys2.as<uint64_t>(), c->stream));
+        LTM_HIP(gather_u64(v->keys->as<uint64_t>(), idx2.as<uint32_t>(), n, keys2.as<uint64_t>(), c->stream));
         sync(c);
         if (getenv("LTM_VOXELGRID_TIMING"))
             fprintf(stderr, "[ltm] voxel_grid_scanset (PCL order): %zu points, %zu keyframes: begin -> order ready %.1f ms (keys down on the copy stream + the sort on host threads), "
@@ -730,10 +711,7 @@ void vgs_end(ltm_ctx* c, ltm_vgs* v, ltm_scanset* out)
     }
     DevBuf heads(c, n), pos(c, n * 4);
     LTM_HIP(head_flags(keys2.as<uint64_t>(), n, heads.as<uint8_t>(), c->stream));
-    const size_t tb = scan_temp_bytes(n);
-    DevBuf temp(c, tb);
-    LTM_HIP(exclusive_scan_u8(heads.as<uint8_t>(), pos.as<uint32_t>(), n, temp.p, tb, c->stream));
-    const size_t nvox = scan_total_u8(c, heads.as<uint8_t>(), pos.as<uint32_t>(), n);
+    const size_t nvox = count_flags(c, heads.as<uint8_t>(), n, pos);
     // the keys lead with the keyframe id (and the host order works keyframe by keyframe), so keyframe k still occupies positions [off[k], off[k+1])
     DevBuf bout(c, (nk + 1) * 4);
     LTM_HIP(gather_u32(pos.as<uint32_t>(), s.off_dev, nk + 1, n, (uint32_t)nvox, bout.as<uint32_t>(), c->stream));

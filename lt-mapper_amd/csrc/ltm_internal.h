@@ -7,6 +7,7 @@
 #include "ltm.h"
 #include "ltm_pclsort.h"
 #include "ltm_kernels.h"
+#include "ltm_device_prims.h"      // ordered_unkey: the host reads boxes with the function the kernels wrote them with
 
 #include <hip/hip_runtime_api.h>
 
@@ -456,6 +457,24 @@ inline void d2d(ltm_ctx* c, void* dst, const void* src, size_t bytes)
     LTM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
 }
 
+// min / max corners of a box of six ordered keys
+inline void decode_box(const uint32_t* enc, float mn[3], float mx[3])
+{
+    for (int d = 0; d < 3; ++d) { mn[d] = ordered_unkey(enc[d]); mx[d] = ordered_unkey(enc[3 + d]); }
+}
+// One box in one host round trip: bbox_init, the reduction that launch(bbox8) enqueues, one copy down.  Returns word 6 (the reduction's own: check flag / count).
+template <class Launch>
+inline uint32_t read_box(ltm_ctx* c, float mn[3], float mx[3], Launch&& launch)
+{
+    DevBuf bb(c, 8 * sizeof(uint32_t));
+    LTM_HIP(bbox_init(bb.as<uint32_t>(), c->stream));
+    LTM_HIP(launch(bb.as<uint32_t>()));
+    uint32_t enc[8];
+    d2h(c, enc, bb.p, sizeof enc);
+    decode_box(enc, mn, mx);
+    return enc[6];
+}
+
 inline Cloud& get_cloud(ltm_ctx* c, ltm_cloud h)
 {
     auto it = c->clouds.find(h);
@@ -632,7 +651,19 @@ int elevation_fit_for(float vfov, float c4[4], double* err);                    
 void pack_from_host(const void* src, size_t n, size_t stride, std::vector<float>& out);
 void unpack_to_host(const float* packed, size_t n, size_t stride, void* dst);
 Geom geom_for(const ltm_ctx* c, float alpha);                                     // ltm_api_vote.cpp (utility.cpp:222-236 resetRimgSize)
-size_t scan_total_u8(ltm_ctx* c, const uint8_t* labels, const uint32_t* pos, size_t n);
+size_t scan_total_u8(ltm_ctx* c, const uint8_t* labels, const uint32_t* pos, size_t n);   // ltm_api_vote.cpp
+// exclusive scan of (flags[i] != 0) into pos (n > 0 uint32); count_flags: and the number of set flags, read by the host (one round trip)
+inline void scan_flags(ltm_ctx* c, const uint8_t* flags, size_t n, DevBuf& pos)
+{
+    const size_t tb = scan_temp_bytes(n);
+    DevBuf temp(c, tb);
+    LTM_HIP(exclusive_scan_u8(flags, pos.as<uint32_t>(), n, temp.p, tb, c->stream));
+}
+inline size_t count_flags(ltm_ctx* c, const uint8_t* flags, size_t n, DevBuf& pos)
+{
+    scan_flags(c, flags, n, pos);
+    return scan_total_u8(c, flags, pos.as<uint32_t>(), n);
+}
 void scan_cache_drop(ltm_ctx* c, uint64_t ss_handle);                             // ltm_api_vote.cpp
 void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud* kept, ltm_cloud* flagged);   // ltm_api_vote.cpp
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp

@@ -16,14 +16,6 @@ constexpr int kScLdsBins = 4096;            // descriptors up to this many bins 
 constexpr int kScPairBlock = 64;            // one wave per descriptor pair
 constexpr size_t kScPairLdsMax = 60 << 10;  // both descriptors of a pair are staged in LDS when they fit
 
-// order-preserving float -> uint32 for integer atomic max; 0 is below every finite value and both infinities: "no point"
-__device__ __forceinline__ uint32_t sc_key(float v)
-{
-    const uint32_t b = f2u(v);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float sc_unkey(uint32_t k) { return u2f((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
 // max(min(n, int(ceil(v))), 1) as x86 evaluates it: a NaN or out-of-range double converts to INT_MIN (cvttsd2si), which the clamp turns into cell 1
 __device__ __forceinline__ int sc_cell(double v, int n)
 {
@@ -79,7 +71,7 @@ k_sc_scatter(const float4* __restrict__ scans, const uint64_t* __restrict__ offs
         if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) continue;
         const int bin = sc_bin(p.x, p.y, g);
         if (bin < 0) continue;
-        const uint32_t key = sc_key((float)((double)p.z + g.lidar_height));
+        const uint32_t key = ordered_key((float)((double)p.z + g.lidar_height));      // integer atomic max; the zero-filled bins are below the key of every height: "no point"
         if (kLds) atomicMax(&sm[bin], key);
         else sc_max_u32(out + bin, key);
     }
@@ -103,7 +95,7 @@ k_sc_finish(const uint32_t* __restrict__ bins, int R, int S, double* __restrict_
     if (bins) {
         for (size_t i = threadIdx.x; i < nb; i += kBlock) {
             const uint32_t k = bins[d * nb + i];
-            const float v = k ? sc_unkey(k) : -1000.0f;
+            const float v = k ? ordered_unkey(k) : -1000.0f;
             D[i] = (v > -1000.0f) ? (double)v : 0.0;
         }
         __syncthreads();

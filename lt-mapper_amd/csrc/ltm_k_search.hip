@@ -24,22 +24,6 @@ namespace ltm {
 namespace {
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-// order-preserving float -> uint32 (min / max with integer atomics)
-__device__ __forceinline__ uint32_t ord_f32(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t spread21(uint32_t v)
-{
-    uint64_t x = v & 0x1fffffu;
-    x = (x | (x << 32)) & 0x1f00000000ffffull;
-    x = (x | (x << 16)) & 0x1f0000ff0000ffull;
-    x = (x | (x << 8)) & 0x100f00f00f00f00full;
-    x = (x | (x << 4)) & 0x10c30c30c30c30c3ull;
-    x = (x | (x << 2)) & 0x1249249249249249ull;
-    return x;
-}
 __device__ __forceinline__ uint32_t quant21(float v, double o, double scale)
 {
     const double t = floor(((double)v - o) * scale);
@@ -48,7 +32,7 @@ __device__ __forceinline__ uint32_t quant21(float v, double o, double scale)
 __device__ __forceinline__ uint64_t search_key(const SearchFrame& f, float x, float y, float z)
 {
     if (!finite3(x, y, z)) return ~0ull;
-    return (spread21(quant21(x, f.ox, f.scale)) << 2) | (spread21(quant21(y, f.oy, f.scale)) << 1) | spread21(quant21(z, f.oz, f.scale));
+    return morton3(quant21(x, f.ox, f.scale), quant21(y, f.oy, f.scale), quant21(z, f.oz, f.scale));
 }
 // (d, i) goes before (bd, bi): smaller distance, then smaller target index
 __device__ __forceinline__ bool pair_less(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
@@ -107,41 +91,27 @@ __device__ __forceinline__ void seed_leaves(const SearchTree& t, uint64_t qkey, 
 
 // ------------------------------------------------------------------------------------------------------------- build
 __global__ void __launch_bounds__(kBlock)
-k_search_bbox(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ out)      // out[0..6) ordered min xyz, max xyz; out[6] finite count
+k_search_bbox(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ out)      // out[0..6): box of the finite points (bbox_init), out[6]: their number
 {
-    uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u}, cnt = 0;
+    BoxAcc box;
+    uint32_t cnt = 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float4 p = pts[i];
         if (!finite3(p.x, p.y, p.z)) continue;
-        const uint32_t e[3] = {ord_f32(p.x), ord_f32(p.y), ord_f32(p.z)};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], e[d]); mx[d] = max(mx[d], e[d]); }
+        box.add(p);
         ++cnt;
     }
+    box.wave_reduce();
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], off)); mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], off)); }
-        cnt += (uint32_t)__shfl_xor((int)cnt, off);
-    }
-    if ((threadIdx.x & 63u) == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { atomicMin(&out[d], mn[d]); atomicMax(&out[3 + d], mx[d]); }
-        atomicAdd(&out[6], cnt);
-    }
+    for (int off = 32; off > 0; off >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, off, 64);
+    if ((threadIdx.x & 63u) == 0) atomicAdd(&out[6], cnt);
+    box.commit<kBlock / 64>(out);
 }
-hipError_t search_bbox(const float4* pts, size_t n, uint32_t* out7, hipStream_t s)
+hipError_t search_bbox(const float4* pts, size_t n, uint32_t* bbox8, hipStream_t s)
 {
     if (!n) return hipSuccess;
-    k_search_bbox<<<dim3((unsigned)std::min<size_t>(grid_for(n, kBlock * 8), 1024)), dim3(kBlock), 0, s>>>(pts, n, out7);
+    k_search_bbox<<<dim3((unsigned)std::min<size_t>(grid_for(n, kBlock * 8), 1024)), dim3(kBlock), 0, s>>>(pts, n, bbox8);
     return hipGetLastError();
-}
-float search_bbox_decode(uint32_t e)
-{
-    const uint32_t u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
 }
 
 __global__ void __launch_bounds__(kBlock)

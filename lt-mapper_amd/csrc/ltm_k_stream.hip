@@ -121,18 +121,6 @@ __global__ void k_gather_u32(const uint32_t* in, const uint64_t* idx, size_t m, 
     const uint64_t i = idx[j];
     out[j] = (i < n) ? in[i] : tail;
 }
-// out[j] = in[idx[j]] on 64-bit words (the host-ordered form of the loader's voxel grid permutes its keys with the point indices)
-__global__ void __launch_bounds__(kBlock) k_gather_u64_by_u32(const uint64_t* __restrict__ in, const uint32_t* __restrict__ idx, size_t n, uint64_t* __restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[idx[i]];
-}
-hipError_t gather_u64_by_u32(const uint64_t* in, const uint32_t* idx_dev, size_t n, uint64_t* out, hipStream_t s)
-{
-    if (!n) return hipSuccess;
-    k_gather_u64_by_u32<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(in, idx_dev, n, out);
-    return hipGetLastError();
-}
 hipError_t gather_u32(const uint32_t* in, const uint64_t* idx_dev, size_t m, size_t n, uint32_t tail, uint32_t* out, hipStream_t s)
 {
     if (!m) return hipSuccess;

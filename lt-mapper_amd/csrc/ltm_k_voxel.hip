@@ -6,19 +6,7 @@
 namespace ltm {
 
 // ----------------------------------------------------------------------------- voxel centroid
-// order-preserving float <-> uint32 encoding for atomic min/max
-__host__ __device__ inline uint32_t enc_f32(float f)
-{
-    const uint32_t u = __builtin_bit_cast(uint32_t, f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-float bbox_decode(uint32_t e)
-{
-    uint32_t u = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
-    float f; memcpy(&f, &u, 4);
-    return f;
-}
-__global__ void k_bbox_init(uint32_t* b)          // 8 words per box: min xyz, max xyz (order-preserving encoding), violation flag of the check form, pad
+__global__ void k_bbox_init(uint32_t* b)          // 8 words per box: min xyz, max xyz (ordered keys, ltm_device_prims.h), violation flag of the check form / finite count of the search form, pad
 {
     if (threadIdx.x < 3) b[threadIdx.x] = 0xffffffffu;
     else if (threadIdx.x < 8) b[threadIdx.x] = 0u;
@@ -31,8 +19,7 @@ hipError_t bbox_init(uint32_t* bbox, hipStream_t s)
 __global__ void __launch_bounds__(kBlock)
 k_bbox_reduce(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ bbox)
 {
-    __shared__ uint32_t smn[3][kBlock / 64], smx[3][kBlock / 64];
-    uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+    BoxAcc box;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     // four independent loads in flight per lane (round 5): with one, the 4096 resident waves of this grid kept 4 MB in flight against a ~2 us memory
@@ -42,38 +29,11 @@ k_bbox_reduce(const float4* __restrict__ pts, size_t n, uint32_t* __restrict__ b
 #pragma unroll
         for (int u = 0; u < 4; ++u) p[u] = pts[i + (size_t)u * stride];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t e[3] = {enc_f32(p[u].x), enc_f32(p[u].y), enc_f32(p[u].z)};
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], e[d]); mx[d] = max(mx[d], e[d]); }
-        }
+        for (int u = 0; u < 4; ++u) box.add(p[u]);
     }
-    for (; i < n; i += stride) {
-        const float4 p = pts[i];
-        const uint32_t e[3] = {enc_f32(p.x), enc_f32(p.y), enc_f32(p.z)};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], e[d]); mx[d] = max(mx[d], e[d]); }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], off, 64));
-            mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], off, 64));
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { smn[d][wave] = mn[d]; smx[d][wave] = mx[d]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {          // one set of 6 atomics per workgroup
-        const int d = threadIdx.x;
-        uint32_t a = smn[d][0], b = smx[d][0];
-        for (int w = 1; w < kBlock / 64; ++w) { a = min(a, smn[d][w]); b = max(b, smx[d][w]); }
-        atomicMin(bbox + d, a); atomicMax(bbox + 3 + d, b);
-    }
+    for (; i < n; i += stride) box.add(pts[i]);
+    box.wave_reduce();
+    box.commit<kBlock / 64>(bbox);
 }
 hipError_t bbox_reduce(const float4* pts, size_t n, uint32_t* bbox, hipStream_t s)
 {
@@ -82,14 +42,6 @@ hipError_t bbox_reduce(const float4* pts, size_t n, uint32_t* bbox, hipStream_t 
     return hipGetLastError();
 }
 
-__device__ __forceinline__ uint64_t spread3(uint32_t v);
-__device__ __forceinline__ uint64_t morton_code_of(const float4 p, const OctreeFrame& f)
-{
-    const uint32_t kx = (uint32_t)(((double)p.x - f.minx) / f.res);
-    const uint32_t ky = (uint32_t)(((double)p.y - f.miny) / f.res);
-    const uint32_t kz = (uint32_t)(((double)p.z - f.minz) / f.res);
-    return (spread3(kx) << 2) | (spread3(ky) << 1) | spread3(kz);
-}
 // The bounding-box pass of a voxel grid, with a speculation riding along (round 4).  Most clouds that get re-gridded are
 // order-preserving subsets of an earlier grid's output (the kept / flagged part of a map).  If such a cloud still has the octree frame
 // it was gridded under -- `f`, carried with the cloud -- and its points' Morton codes under that frame are STRICTLY INCREASING, then the
@@ -99,8 +51,7 @@ __device__ __forceinline__ uint64_t morton_code_of(const float4 p, const OctreeF
 __global__ void __launch_bounds__(kBlock)
 k_bbox_reduce_check(const float4* __restrict__ pts, size_t n, OctreeFrame f, uint32_t* __restrict__ bbox)
 {
-    __shared__ uint32_t smn[3][kBlock / 64], smx[3][kBlock / 64];
-    uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+    BoxAcc box;
     bool bad = false;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const int lane = threadIdx.x & 63;
@@ -108,39 +59,19 @@ k_bbox_reduce_check(const float4* __restrict__ pts, size_t n, OctreeFrame f, uin
         const size_t i = i0 + threadIdx.x;
         const bool in = i < n;
         const float4 p = in ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-        const uint64_t code = in ? morton_code_of(p, f) : ~0ull;
+        const uint64_t code = in ? octree_code(p, f) : ~0ull;
         uint64_t prev = __shfl_up(code, 1, 64);
-        if (lane == 0) prev = (in && i > 0) ? morton_code_of(pts[i - 1], f) : 0ull;
+        if (lane == 0) prev = (in && i > 0) ? octree_code(pts[i - 1], f) : 0ull;
         if (in) {
-            const uint32_t e[3] = {enc_f32(p.x), enc_f32(p.y), enc_f32(p.z)};
-#pragma unroll
-            for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], e[d]); mx[d] = max(mx[d], e[d]); }
+            box.add(p);
             bad |= (i > 0 && code <= prev);
             bad |= __builtin_bit_cast(uint32_t, p.x) == 0x80000000u || __builtin_bit_cast(uint32_t, p.y) == 0x80000000u ||
                    __builtin_bit_cast(uint32_t, p.z) == 0x80000000u || __builtin_bit_cast(uint32_t, p.w) == 0x80000000u;
         }
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], off, 64));
-            mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], off, 64));
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { smn[d][wave] = mn[d]; smx[d][wave] = mx[d]; }
-    }
+    box.wave_reduce();
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(bbox + 6, 1u);
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int d = threadIdx.x;
-        uint32_t a = smn[d][0], b = smx[d][0];
-        for (int w = 1; w < kBlock / 64; ++w) { a = min(a, smn[d][w]); b = max(b, smx[d][w]); }
-        atomicMin(bbox + d, a); atomicMax(bbox + 3 + d, b);
-    }
+    box.commit<kBlock / 64>(bbox);
 }
 hipError_t bbox_reduce_check(const float4* pts, size_t n, OctreeFrame f, uint32_t* bbox8, hipStream_t s)
 {
@@ -149,46 +80,22 @@ hipError_t bbox_reduce_check(const float4* pts, size_t n, OctreeFrame f, uint32_
     return hipGetLastError();
 }
 
-__device__ __forceinline__ uint64_t spread3(uint32_t v);
-
 // per-keyframe bounding boxes of a scan set: bbox[kf][6], same encoding
 __global__ void k_bbox_init_seg(uint32_t* b, size_t n_kf)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_kf * 6) b[i] = ((i % 6) < 3) ? 0xffffffffu : 0u;
 }
-// grid = (chunks, keyframes): every workgroup reduces points of ONE keyframe (wave shuffle, then LDS), 6 atomics per workgroup
+// grid = (chunks, keyframes): every workgroup reduces points of ONE keyframe; a workgroup that saw no point issues no atomics
 __global__ void __launch_bounds__(kBlock)
 k_bbox_reduce_seg(const float4* __restrict__ pts, const uint64_t* __restrict__ offsets, uint32_t* __restrict__ bbox)
 {
-    __shared__ uint32_t smn[3][kBlock / 64], smx[3][kBlock / 64];
     const size_t kf = blockIdx.y;
     const uint64_t a = offsets[kf], b = offsets[kf + 1];
-    uint32_t mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
-    for (uint64_t i = a + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < b; i += (uint64_t)gridDim.x * blockDim.x) {
-        const float4 p = pts[i];
-        const uint32_t e[3] = {enc_f32(p.x), enc_f32(p.y), enc_f32(p.z)};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { mn[d] = min(mn[d], e[d]); mx[d] = max(mx[d], e[d]); }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[d] = min(mn[d], (uint32_t)__shfl_xor((int)mn[d], off, 64));
-            mx[d] = max(mx[d], (uint32_t)__shfl_xor((int)mx[d], off, 64));
-        }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { smn[d][wave] = mn[d]; smx[d][wave] = mx[d]; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int d = threadIdx.x;
-        uint32_t lo = smn[d][0], hi = smx[d][0];
-        for (int w = 1; w < kBlock / 64; ++w) { lo = min(lo, smn[d][w]); hi = max(hi, smx[d][w]); }
-        if (lo != 0xffffffffu || hi != 0u) { atomicMin(bbox + 6 * kf + d, lo); atomicMax(bbox + 6 * kf + 3 + d, hi); }
-    }
+    BoxAcc box;
+    for (uint64_t i = a + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < b; i += (uint64_t)gridDim.x * blockDim.x) box.add(pts[i]);
+    box.wave_reduce();
+    box.commit<kBlock / 64>(bbox + 6 * kf, true);
 }
 hipError_t bbox_reduce_seg(const float4* pts, const uint64_t* offsets_dev, size_t n_kf, uint64_t n, uint32_t* bbox, hipStream_t s)
 {
@@ -209,14 +116,8 @@ k_morton_keys_seg(const float4* __restrict__ pts, const uint64_t* __restrict__ o
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    size_t lo = 0, hi = n_kf;
-    while (hi - lo > 1) { const size_t mid = (lo + hi) >> 1; if (offsets[mid] <= i) lo = mid; else hi = mid; }
-    const OctreeFrame f = frames[lo];
-    const float4 p = pts[i];
-    const uint32_t kx = (uint32_t)(((double)p.x - f.minx) / f.res);
-    const uint32_t ky = (uint32_t)(((double)p.y - f.miny) / f.res);
-    const uint32_t kz = (uint32_t)(((double)p.z - f.minz) / f.res);
-    keys[i] = ((uint64_t)lo << shift) | (spread3(kx) << 2) | (spread3(ky) << 1) | spread3(kz);
+    const size_t kf = find_kf(offsets, 0, n_kf, i);
+    keys[i] = ((uint64_t)kf << shift) | octree_code(pts[i], frames[kf]);
     idx[i] = (uint32_t)i;
 }
 hipError_t morton_keys_seg(const float4* pts, const uint64_t* offsets_dev, size_t n_kf, uint64_t n, const OctreeFrame* frames_dev,
@@ -237,11 +138,10 @@ k_voxelgrid_keys_seg(const float4* __restrict__ pts, const uint64_t* __restrict_
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    size_t lo = 0, hi = n_kf;
-    while (hi - lo > 1) { const size_t mid = (lo + hi) >> 1; if (offsets[mid] <= i) lo = mid; else hi = mid; }
-    const VoxelGridFrame f = frames[lo];
+    const size_t kf = find_kf(offsets, 0, n_kf, i);
+    const VoxelGridFrame f = frames[kf];
     uint32_t leaf;
-    if (f.passthrough) leaf = (uint32_t)(i - offsets[lo]);
+    if (f.passthrough) leaf = (uint32_t)(i - offsets[kf]);
     else {
         const float4 p = pts[i];
         const int i0 = (int)(floorf(p.x * f.inv) - (float)f.min_b[0]);
@@ -249,7 +149,7 @@ k_voxelgrid_keys_seg(const float4* __restrict__ pts, const uint64_t* __restrict_
         const int i2 = (int)(floorf(p.z * f.inv) - (float)f.min_b[2]);
         leaf = (uint32_t)i0 + (uint32_t)i1 * (uint32_t)f.div_b[0] + (uint32_t)i2 * (uint32_t)f.div_b[0] * (uint32_t)f.div_b[1];
     }
-    keys[i] = ((uint64_t)lo << 32) | leaf;
+    keys[i] = ((uint64_t)kf << 32) | leaf;
     idx[i] = (uint32_t)i;
 }
 hipError_t voxelgrid_keys_seg(const float4* pts, const uint64_t* offsets_dev, size_t n_kf, uint64_t n, const VoxelGridFrame* frames_dev,
@@ -259,8 +159,21 @@ hipError_t voxelgrid_keys_seg(const float4* pts, const uint64_t* offsets_dev, si
     k_voxelgrid_keys_seg<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(pts, offsets_dev, n_kf, n, frames_dev, keys, idx);
     return hipGetLastError();
 }
-// CentroidPoint accumulators of pcl::VoxelGrid: float sums over the voxel's points (input order: the sort is stable), divided by
-// the count; points of a pass-through keyframe are copied bit for bit (0 + x would turn a -0 into +0)
+// Centroid of the voxel at sorted positions [a, b), as PCL's OctreePointCloudVoxelCentroidContainer and pcl::VoxelGrid's CentroidPoint both form it:
+// float sums in the order of the (stably sorted => input-ordered) positions, divided by (float)count.  One lane walks the voxel sequentially so the sum is
+// the reference's left-to-right sum, bit for bit.  point_of(j) = index into pts of the j-th sorted element.
+template <class PointOf>
+__device__ __forceinline__ float4 centroid_of(const float4* __restrict__ pts, uint32_t a, uint32_t b, PointOf point_of)
+{
+    float sx = 0.0f, sy = 0.0f, sz = 0.0f, si = 0.0f;
+    for (uint32_t j = a; j < b; ++j) {
+        const float4 p = pts[point_of(j)];
+        sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; si = si + p.w;
+    }
+    const float cnt = (float)(b - a);
+    return make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+}
+// pcl::VoxelGrid: points of a pass-through keyframe are copied bit for bit (0 + x would turn a -0 into +0)
 __global__ void __launch_bounds__(kBlock)
 k_voxelgrid_centroids(const float4* __restrict__ pts, const uint64_t* __restrict__ sorted_keys, const uint32_t* __restrict__ sorted_idx,
                       const uint32_t* __restrict__ starts, const VoxelGridFrame* __restrict__ frames, size_t n_vox, size_t n, float4* __restrict__ out)
@@ -270,13 +183,7 @@ k_voxelgrid_centroids(const float4* __restrict__ pts, const uint64_t* __restrict
     const uint32_t a = starts[v];
     const uint32_t b = (v + 1 < n_vox) ? starts[v + 1] : (uint32_t)n;
     if (frames[sorted_keys[a] >> 32].passthrough) { out[v] = pts[sorted_idx[a]]; return; }
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, si = 0.0f;
-    for (uint32_t j = a; j < b; ++j) {
-        const float4 p = pts[sorted_idx[j]];
-        sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; si = si + p.w;
-    }
-    const float cnt = (float)(b - a);
-    out[v] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+    out[v] = centroid_of(pts, a, b, [&](uint32_t j) { return sorted_idx[j]; });
 }
 hipError_t voxelgrid_centroids(const float4* pts, const uint64_t* sorted_keys, const uint32_t* sorted_idx, const uint32_t* starts,
                                const VoxelGridFrame* frames_dev, size_t n_vox, size_t n, float4* out, hipStream_t s)
@@ -286,28 +193,12 @@ hipError_t voxelgrid_centroids(const float4* pts, const uint64_t* sorted_keys, c
     return hipGetLastError();
 }
 
-// PCL genOctreeKeyforPoint: key = (unsigned)(((double)p - min) / resolution); Morton code with x as the
-// most significant bit of each level triple (child index = x<<2 | y<<1 | z).
-__device__ __forceinline__ uint64_t spread3(uint32_t v)   // 21 bits -> every third bit
-{
-    uint64_t x = v & 0x1fffffu;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
 __global__ void __launch_bounds__(kBlock)
 k_morton_keys(const float4* __restrict__ pts, size_t n, OctreeFrame f, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float4 p = pts[i];
-    const uint32_t kx = (uint32_t)(((double)p.x - f.minx) / f.res);
-    const uint32_t ky = (uint32_t)(((double)p.y - f.miny) / f.res);
-    const uint32_t kz = (uint32_t)(((double)p.z - f.minz) / f.res);
-    keys[i] = (spread3(kx) << 2) | (spread3(ky) << 1) | spread3(kz);
+    keys[i] = octree_code(pts[i], f);
     idx[i] = (uint32_t)i;
 }
 hipError_t morton_keys(const float4* pts, size_t n, OctreeFrame f, uint64_t* keys, uint32_t* idx, hipStream_t s)
@@ -323,11 +214,7 @@ k_morton_keys_packed(const float4* __restrict__ pts, size_t n, OctreeFrame f, Ke
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float4 p = pts[i];
-    const uint32_t kx = (uint32_t)(((double)p.x - f.minx) / f.res);
-    const uint32_t ky = (uint32_t)(((double)p.y - f.miny) / f.res);
-    const uint32_t kz = (uint32_t)(((double)p.z - f.minz) / f.res);
-    const uint64_t code = (spread3(kx) << 2) | (spread3(ky) << 1) | spread3(kz);
+    const uint64_t code = octree_code(pts[i], f);
     uint64_t c = 0;
     for (int r = 0; r < kc.n_runs; ++r) c |= ((code >> kc.src[r]) & kc.mask[r]) << kc.dst[r];      // uniform trip count, scalar operands
     keys[i] = (c << idx_bits) | (uint64_t)i;
@@ -571,9 +458,7 @@ hipError_t voxel_heads_starts(const uint64_t* sorted_keys, size_t n, unsigned sh
     return hipGetLastError();
 }
 
-// PCL OctreePointCloudVoxelCentroidContainer: float sums in input order, divided by (float)count.
-// One lane per voxel walks its (stably sorted => input-ordered) points sequentially so the float sum is
-// the reference's left-to-right sum, bit for bit.
+// octreeDownsampling's centroids: one lane per voxel (centroid_of)
 __global__ void __launch_bounds__(kBlock)
 k_voxel_centroids(const float4* __restrict__ pts, const uint32_t* __restrict__ sorted_idx, const uint32_t* __restrict__ starts,
                   size_t n_vox, size_t n, float4* __restrict__ out)
@@ -582,13 +467,7 @@ k_voxel_centroids(const float4* __restrict__ pts, const uint32_t* __restrict__ s
     if (v >= n_vox) return;
     const uint32_t a = starts[v];
     const uint32_t b = (v + 1 < n_vox) ? starts[v + 1] : (uint32_t)n;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, si = 0.0f;
-    for (uint32_t j = a; j < b; ++j) {
-        const float4 p = pts[sorted_idx[j]];
-        sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; si = si + p.w;
-    }
-    const float cnt = (float)(b - a);
-    out[v] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+    out[v] = centroid_of(pts, a, b, [&](uint32_t j) { return sorted_idx[j]; });
 }
 __global__ void __launch_bounds__(kBlock)
 k_voxel_centroids_packed(const float4* __restrict__ pts, const uint64_t* __restrict__ sorted_keys, uint64_t idx_mask,
@@ -598,13 +477,7 @@ k_voxel_centroids_packed(const float4* __restrict__ pts, const uint64_t* __restr
     if (v >= n_vox) return;
     const uint32_t a = starts[v];
     const uint32_t b = (v + 1 < n_vox) ? starts[v + 1] : (uint32_t)n;
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f, si = 0.0f;
-    for (uint32_t j = a; j < b; ++j) {
-        const float4 p = pts[sorted_keys[j] & idx_mask];
-        sx = sx + p.x; sy = sy + p.y; sz = sz + p.z; si = si + p.w;
-    }
-    const float cnt = (float)(b - a);
-    out[v] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+    out[v] = centroid_of(pts, a, b, [&](uint32_t j) { return sorted_keys[j] & idx_mask; });
 }
 hipError_t voxel_centroids_packed(const float4* pts, const uint64_t* sorted_keys, uint64_t idx_mask, const uint32_t* starts, size_t n_vox,
                                   size_t n, float4* out, hipStream_t s)
@@ -620,6 +493,5 @@ hipError_t voxel_centroids(const float4* pts, const uint32_t* sorted_idx, const 
     k_voxel_centroids<<<dim3(grid_for(n_vox)), dim3(kBlock), 0, s>>>(pts, sorted_idx, starts, n_vox, n, out);
     return hipGetLastError();
 }
-
 
 } // namespace ltm

@@ -1,4 +1,4 @@
-// ltm_kernels.h -- host-callable launchers of the gfx950 kernels (definitions in ltm_kernels.hip).
+// ltm_kernels.h -- host-callable launchers of the gfx950 kernels (definitions in the ltm_k_*.hip unit of their stage).
 // All launchers enqueue on the given stream and return the hipError_t of the launch.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -113,7 +113,6 @@ hipError_t reproject_gather(const uint64_t* img, const uint32_t* pos, size_t npx
 hipError_t image_bounds(const uint32_t* pos, const uint64_t* img, size_t npx, size_t nb, uint32_t* out, hipStream_t s);
 hipError_t flag_bounds(const uint32_t* pos, const uint8_t* flag, size_t n, const uint64_t* offsets_dev, size_t kf0, uint64_t first, size_t nb,
                        uint32_t* out, hipStream_t s);
-hipError_t gather_u64_by_u32(const uint64_t* in, const uint32_t* idx_dev, size_t n, uint64_t* out, hipStream_t s);
 hipError_t gather_u32(const uint32_t* in, const uint64_t* idx_dev, size_t m, size_t n, uint32_t tail_value_index_n,
                       uint32_t* out, hipStream_t s);
 
@@ -128,10 +127,9 @@ hipError_t zip_concat(const float4* a, const uint64_t* oa, const float4* b, cons
 hipError_t preclean_flags(const float4* in, uint64_t n, float radius, uint8_t* keep, hipStream_t s);
 
 // ---- voxel centroid ----
-// bbox[6] device floats encoded as ordered uint32: minx,miny,minz,maxx,maxy,maxz (init by bbox_init)
+// bbox: 8 device words, initialised by bbox_init: min xyz, max xyz as ordered keys (ordered_unkey of ltm_device_prims.h gives the floats back), two extra words
 hipError_t bbox_init(uint32_t* bbox, hipStream_t s);
 hipError_t bbox_reduce(const float4* pts, size_t n, uint32_t* bbox, hipStream_t s);
-float      bbox_decode(uint32_t enc);
 struct OctreeFrame { double minx, miny, minz, res; unsigned depth; };
 hipError_t bbox_reduce_check(const float4* pts, size_t n, OctreeFrame cached_frame, uint32_t* bbox8, hipStream_t s);   // box + "strictly increasing codes under cached_frame" (bbox8[6] = 1 if not)
 size_t voxel_heads_starts_temp_bytes(size_t n);
@@ -181,7 +179,7 @@ hipError_t voxel_centroids(const float4* pts, const uint32_t* sorted_idx, const 
 struct KnnGrid { double ox, oy, oz, inv_cell; long long nx, ny, nz; };
 hipError_t cell_keys(const float4* pts, size_t n, KnnGrid g, uint64_t* keys, uint32_t* idx, hipStream_t s);
 hipError_t gather_points(const float4* in, const uint32_t* idx, size_t n, float4* out, hipStream_t s);
-hipError_t gather_u64(const uint64_t* in, const uint32_t* idx, size_t n, uint64_t* out, hipStream_t s);
+hipError_t gather_u64(const uint64_t* in, const uint32_t* idx, size_t n, uint64_t* out, hipStream_t s);      // out[i] = in[idx[i]]
 struct HashEntry { uint64_t key; uint32_t start, end; };
 hipError_t hash_build(const uint64_t* sorted_keys, const uint32_t* starts, size_t n_cells, size_t n_pts,
                       HashEntry* table, uint32_t table_mask, hipStream_t s);
@@ -227,9 +225,8 @@ struct SearchFrame { double ox, oy, oz, scale; };
 // finite target points in Morton order (pts, their input indices idx, their codes keys), Mf of them, L = ceil(Mf / kSearchLeaf) leaves,
 // P = L rounded up to a power of two; box: 2 float4 (lo, hi) per node of the implicit tree, nodes 1 .. 2P-1, leaf l = node P + l
 struct SearchTree { const float4* pts; const uint32_t* idx; const uint64_t* keys; const float4* box; uint32_t Mf, L, P; };
-// out7: {ordered-uint min xyz, max xyz, finite count}, initialised by the caller to {~0 x3, 0 x3, 0}; non-finite points are left out
-hipError_t search_bbox(const float4* pts, size_t n, uint32_t* out7, hipStream_t s);
-float      search_bbox_decode(uint32_t enc);
+// bbox8 (bbox_init): box of the finite points, bbox8[6] their number
+hipError_t search_bbox(const float4* pts, size_t n, uint32_t* bbox8, hipStream_t s);
 hipError_t search_keys(const float4* pts, size_t n, SearchFrame f, uint64_t* keys, uint32_t* idx, hipStream_t s);    // non-finite: key ~0
 hipError_t search_tree_boxes(const float4* sorted_pts, uint32_t Mf, uint32_t L, uint32_t P, float4* box, hipStream_t s);
 // queries in code order (temp: sort_temp_bytes(n)): order[j] = input index of the j-th query, keys_sorted[j] its code

@@ -9,6 +9,7 @@
 #pragma once
 #include "ltm_kernels.h"
 #include "ltm_device_math.h"
+#include "ltm_device_prims.h"
 
 #include <algorithm>
 #include <cstring>

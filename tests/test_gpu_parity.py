@@ -671,3 +671,48 @@ def test_key_range_exchange_pieces_reassemble_the_single_gpu_grid(gpu_ctx, orc, 
                 got = np.concatenate([parts[src][dst].download() for src in range(world)])      # arrival order = source order = input order
                 outs.append(gpu_ctx.voxel_centroid_box(gpu_ctx.upload(got), mn, mx, 0.05).download())
             assert_clouds_equal(np.concatenate(outs), want, f"world {world} cuts {cuts[:4]}...")
+
+
+def _bbox_cloud(n, seed, roll):
+    """n points for the box test.  roll < 0: ordinary values of both signs only.  Otherwise the three axes take three roles, rotated by `roll` so
+    that every axis of the kernel sees each: +-inf among ordinary values; +-FLT_MAX among ordinary values; non-negative values with +0.0, -0.0 and
+    a denormal among them, so that the minimum is a zero.  The special values sit at seeded positions (as many as the cloud has room for)."""
+    rng = np.random.default_rng(seed)
+    p = rng.normal(0, 40.0, size=(n, 4)).astype(np.float32)
+    if roll < 0:
+        return p
+    fmax = np.finfo(np.float32).max
+    p[:, 2] = np.abs(p[:, 2]) + np.float32(1.0)
+    specials = ([np.inf, -np.inf], [fmax, -fmax], [0.0, -0.0, 1e-45])
+    for axis, vals in enumerate(specials):
+        at = rng.choice(n, size=min(n, len(vals)), replace=False)
+        p[at, axis] = np.array(vals[:len(at)], np.float32)
+    p[:, :3] = np.roll(p[:, :3], roll, axis=1)
+    return p
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 769, 1025, 2049])
+def test_cloud_bbox_is_the_exact_min_max_and_ragged_scanset_grid(gpu_ctx, orc, n):
+    """ltm_cloud_bbox against numpy min / max, bit for bit.  Sizes: one lane, around a wave boundary, the first size at which the four-loads loop
+    of k_bbox_reduce runs (one 256-thread block, stride 256: i + 768 < n), its remainder loop, the first two-block grid.  Values: both signs, +-0.0,
+    a denormal, +-FLT_MAX, +-inf (no NaN: its place in the order is a property of the key that no caller relies on).  The ordered key puts -0.0
+    below +0.0 and numpy does not tell them apart, so an extremum that is a zero may come back with either sign; everything else is compared as bits.
+    test_empty_and_ragged_inputs does not grid a scan set, and test_voxel_centroid_scanset_matches_per_keyframe_oracle has an empty FIRST keyframe
+    only: the scan set here has an empty first, middle and last one."""
+    for roll in (-1, 0, 1, 2):
+        p = _bbox_cloud(n, 1000 + 10 * n + roll, roll)
+        mn, mx = gpu_ctx.bbox(gpu_ctx.upload(p))
+        for got, want, what in ((mn, p[:, :3].min(0), "min"), (mx, p[:, :3].max(0), "max")):
+            zero = want == 0.0
+            same = np.where(zero, got == 0.0, got.view(np.uint32) == want.view(np.uint32))
+            assert same.all(), f"n {n} roll {roll} {what}: got {got} ({got.view(np.uint32)}), want {want} ({want.view(np.uint32)})"
+    pts = _random_points(3 * n, 77 + n)
+    off = np.array([0, 0, n, n, 3 * n, 3 * n], dtype=np.uint64)
+    g_pts, g_off = gpu_ctx.voxel_centroid_scanset(gpu_ctx.upload_scans(pts, off), 5.0).download()
+    at = 0
+    for k in range(len(off) - 1):
+        want = orc.voxel_centroid(pts[int(off[k]):int(off[k + 1])], 5.0)
+        assert int(g_off[k]) == at and int(g_off[k + 1]) == at + len(want)
+        assert_clouds_equal(g_pts[at:at + len(want)], want, f"ragged scan set, n {n}, kf {k}")
+        at += len(want)
+    assert at == len(g_pts)

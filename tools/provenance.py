@@ -5,9 +5,11 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lt-mapper_amd", "csrc")
-# round 6: the two monolithic sources were split by stage
-KERNEL_SOURCES = ("ltm_kernels_common.h", "ltm_k_projection.hip", "ltm_k_stream.hip", "ltm_k_voxel.hip", "ltm_k_knn.hip", "ltm_device_math.h", "ltm_kernels.h")
-API_SOURCES = ("ltm_internal.h", "ltm_api_core.cpp", "ltm_api_vote.cpp", "ltm_api_voxel.cpp", "ltm_api_knn.cpp", "ltm_pclsort.h")
+# Listed from the directory, not by hand: a new kernel unit, C ABI unit or shared header is hashed without anyone having to remember it.
+_API_HEADERS = ("ltm_internal.h", "ltm_pclsort.h")
+_ALL = sorted(os.listdir(CSRC))
+KERNEL_SOURCES = tuple(f for f in _ALL if (f.startswith("ltm_k_") and f.endswith(".hip")) or (f.endswith(".h") and f not in _API_HEADERS))
+API_SOURCES = tuple(f for f in _ALL if (f.startswith("ltm_api_") and f.endswith(".cpp")) or f in _API_HEADERS)
 
 
 def _sha(files):
