@@ -360,6 +360,69 @@ int  ltm_sc_detect(ltm_ctx*, ltm_sc* database, ltm_sc* queries, const ltm_sc_par
                    float* yaw_diff_rad);
 int  ltm_sc_free(ltm_ctx*, ltm_sc*);
 
+/* -------------------------------------------------------------------- icp ---- */
+/* Batched point-to-point ICP of source clouds against search indices: the step of the reference that verifies the loop pairs Scan Context proposes.
+ * LTslam::addSCloops / addRSloops (ltslam/src/LTslam.cpp:370-416, :508-560) run pcl::IterativeClosestPoint for up to kNumSCLoopsUpperBound = 1000 pairs
+ * (doICPVirtualRelative / doICPGlobalRelative, :187-301) and accept a pair only if hasConverged() and getFitnessScore() <= loopFitnessScoreThreshold.
+ * Here all pairs of one call advance together, two kernel launches per iteration for the whole batch.  PCL is not available to compare against; this is
+ * the arithmetic this library takes PCL 1.10's IterativeClosestPoint (TransformationEstimationSVD, DefaultConvergenceCriteria) to do.  tools/icp_numpy.py
+ * restates it in numpy and the tests compare against that.
+ *  Iteration, per pair, with T the accumulated source->target transform (T = init at the start):
+ *   1. every source point with three finite coordinates is transformed by T in double, x' = ((T00 x + T01 y) + T02 z) + T03 and likewise y', z', without
+ *      fused multiply-adds, and rounded to float: the query.  (A query that overflows float is skipped like a non-finite point.)
+ *   2. its nearest target point is found exactly as ltm_knn_search with k = 1 finds it: FLANN's L2_Simple in float, ties to the smaller target index;
+ *   3. the pair (query, target point) is kept iff (double)d2 <= max_corr_dist * max_corr_dist;
+ *   4. fewer than 3 kept pairs: the pair stops, converged = 0, state = 0; T and `iterations` stay as they are, n_corr / last_mse / the trace row record
+ *      what was found;
+ *   5. otherwise the rigid transform from the queries p onto their target points q (both as doubles) by SVD, Umeyama without scale:
+ *      H = mean((p - pm)(q - qm)^T), H = U S V^T, R = V diag(1, 1, det(V U^T)) U^T, t = qm - R pm, all in double;
+ *   6. T <- T_iter T with T_iter = [R t]; iterations += 1; then the stop tests.
+ *  DEPARTURES from PCL: PCL keeps Matrix4f transforms and re-transforms the already transformed cloud in float every iteration, so its rounding errors
+ *  accumulate over the iterations; this library keeps T in double and always transforms the ORIGINAL source.  Sums run in a fixed order (source points in
+ *  the code order of the target's frame, 256 per partial sum, partial sums in order) and about the corner of the target's bounding box, so a run is
+ *  bit-reproducible, a pair's result does not depend on the rest of the batch, and map coordinates kilometres from zero lose nothing.  Eigen's JacobiSVD
+ *  is replaced by a one-sided Jacobi SVD; the two agree to rounding when H has rank >= 2.
+ *  Stop tests after step 6, in PCL's order (DefaultConvergenceCriteria with max_iterations_similar_transforms_ = 0), mse = mean of the kept float d2 summed
+ *  in double, prev_mse = DBL_MAX at the start and the previous iteration's mse afterwards:
+ *   1. iterations >= max_iterations                                                                   -> state 1
+ *   2. 0.5 * (trace(R) - 1) >= 1 - transformation_epsilon and |t|^2 <= transformation_epsilon         -> state 2
+ *   3. |mse - prev_mse| < 1e-12                                                                       -> state 3
+ *   4. |mse - prev_mse| / prev_mse < euclidean_fitness_epsilon                                        -> state 4
+ *  each with converged = 1.  (PCL evaluates the mse only when tests 1 and 2 fail; here last_mse and the trace always hold it.)
+ *  Fitness (getFitnessScore() with its default, unlimited max_range): after the loop, the mean over the finite source points, transformed by the final T
+ *  as in step 1, of the d2 to their nearest target point; DBL_MAX if no point counts.
+ *  Edge cases: an empty source, a target without a finite point, or max_iterations < 1: T = init, iterations = 0, converged = 0, state = 0, n_corr = 0,
+ *  fitness = last_mse = DBL_MAX.  Non-finite source points are skipped everywhere.  last_mse is DBL_MAX when the last iteration kept no pair.  When H has
+ *  rank < 2 (all kept target points on one line, or one point) the rotation is not unique: the result is then only promised to be finite, orthonormal with
+ *  det +1, and reproducible.
+ *  trace (n_pairs x max_iterations x 2 doubles, may be NULL): row i of a pair = (n_corr, mse) of its iteration i, counted from 0, the iteration that stopped
+ *  in step 4 included (mse NaN if it kept nothing); rows that never ran are NaN.
+ *  targets[i] is an index from ltm_search_build (the same index may serve many pairs), sources[i] a cloud; both belong to this context (a handle of
+ *  another context is LTM_E_INVALID).  init16_or_null: n_pairs row-major 4x4 doubles whose last row is taken to be 0 0 0 1, NULL = identity.  A NULL
+ *  parameter pointer means the defaults.  Each source (< 2^31 points, < 2^31 in all) is copied in sorted order for the call; all device memory comes from
+ *  the context's pool and is back when the call returns, on every error path too.  The call returns when the host arrays are written.
+ *  Out of scope: assembling the submaps (loopFindNearKeyframesCloud and its float Affine3f transformPointCloud), Euler / gtsam::Pose3 conversions,
+ *  point-to-plane and generalized ICP. */
+typedef struct {
+    double max_corr_dist;             /* 150.0  setMaxCorrespondenceDistance, LTslam.cpp:207 */
+    int    max_iterations;            /* 100    :208 */
+    double transformation_epsilon;    /* 1e-6   :209 */
+    double euclidean_fitness_epsilon; /* 1e-6   :210 */
+} ltm_icp_params;
+typedef struct {
+    double   T[16];          /* final source->target transform, row-major */
+    double   fitness;        /* getFitnessScore(): mean squared 1-NN distance of the transformed source; DBL_MAX if no point counts */
+    double   last_mse;       /* mean squared correspondence distance of the last iteration */
+    int32_t  converged;      /* hasConverged() */
+    int32_t  iterations;
+    int32_t  state;          /* why it stopped: 0 too few correspondences / nothing to do, 1 iterations, 2 transform, 3 absolute MSE, 4 relative MSE */
+    uint32_t n_corr;         /* correspondences of the last iteration */
+} ltm_icp_result;
+void ltm_icp_default_params(ltm_icp_params*);     /* host only, needs no device */
+int  ltm_icp_align(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources,
+                   const double* init16_or_null /* n_pairs x 16, NULL = identity */, const ltm_icp_params*,
+                   ltm_icp_result* results_host, double* trace_host_or_null /* n_pairs x max_iterations x 2: (n_corr, mse) per iteration, rest NaN */);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections

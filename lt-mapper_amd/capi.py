@@ -34,6 +34,18 @@ class ScParams(C.Structure):
                 ("num_candidates", C.c_int), ("search_ratio", C.c_double), ("dist_thres", C.c_double)]
 
 
+class IcpParams(C.Structure):
+    """ltm_icp_params (LTslam.cpp:207-210)"""
+    _fields_ = [("max_corr_dist", C.c_double), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double)]
+
+
+# ltm_icp_result as a numpy record (the C layout: 160 bytes)
+ICP_RESULT = np.dtype([("T", np.float64, (4, 4)), ("fitness", np.float64), ("last_mse", np.float64), ("converged", np.int32),
+                       ("iterations", np.int32), ("state", np.int32), ("n_corr", np.uint32)], align=True)
+ICP_STATES = ("too few correspondences", "iterations", "transform", "absolute mse", "relative mse")
+
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/ltm.h
 _vp, _sz, _u64, _i, _f = C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.c_float
 _pu64 = C.POINTER(C.c_uint64)
@@ -132,6 +144,8 @@ SIGNATURES = {
     "ltm_sc_distance": (_i, [_vp, _vp, _vp, _vp, _sz, C.POINTER(ScParams), _vp, _vp]),
     "ltm_sc_detect": (_i, [_vp, _vp, _vp, C.POINTER(ScParams), _vp, _vp, _vp, _vp, _vp]),
     "ltm_sc_free": (_i, [_vp, _vp]),
+    "ltm_icp_default_params": (None, [C.POINTER(IcpParams)]),
+    "ltm_icp_align": (_i, [_vp, _sz, C.POINTER(_vp), _pu64, _vp, C.POINTER(IcpParams), _vp, _vp]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -510,6 +524,43 @@ class Context:
         self._ck(self.lib.ltm_sc_from_descriptors(self.h, d.ctypes.data, d.shape[0], C.byref(p), C.byref(h)))
         return ScanContexts(self, h.value, p)
 
+    # ---- icp
+    def icp_align(self, pairs, init=None, trace=False, **params):
+        """ltm_icp_align: point-to-point ICP of every (target, source) of `pairs` in one batch -- target a SearchIndex of this context (one index
+        may serve many pairs), source a Cloud of this context or an (n, 3) / (n, 4) array.  init: (n, 4, 4) source->target start transforms
+        (None: identity); params: the fields of ltm_icp_params, the reference's values by default.  Returns a record array of dtype ICP_RESULT
+        (T, fitness, last_mse, converged, iterations, state, n_corr), one record per pair; with trace=True also the (n, max_iterations, 2)
+        array of (n_corr, mse) per iteration, NaN where no iteration ran."""
+        p = icp_params(**params)
+        pairs = list(pairs)
+        n = len(pairs)
+        res = np.zeros(n, dtype=ICP_RESULT)
+        assert ICP_RESULT.itemsize == 160
+        tr = np.full((n, max(p.max_iterations, 0), 2), np.nan) if trace else None
+        if n:
+            for t, _ in pairs:
+                if not isinstance(t, SearchIndex):
+                    raise TypeError("the target of a pair must be a SearchIndex (Context.search_index)")
+            made = []
+            try:
+                src = []
+                for _, s_ in pairs:
+                    if not isinstance(s_, Cloud):
+                        s_ = self.upload(_xyzi(s_))
+                        made.append(s_)
+                    src.append(s_)
+                th = (_vp * n)(*[t.h for t, _ in pairs])
+                sh = (C.c_uint64 * n)(*[s_.h for s_ in src])
+                i16 = None
+                if init is not None:
+                    i16 = np.ascontiguousarray(init, dtype=np.float64).reshape(n, 16)
+                self._ck(self.lib.ltm_icp_align(self.h, n, th, sh, None if i16 is None else i16.ctypes.data, C.byref(p), res.ctypes.data,
+                                                tr.ctypes.data if trace and tr.size else None))
+            finally:
+                for s_ in made:
+                    s_.free()
+        return (res, tr) if trace else res
+
     # ---- debug / parity
     def pool_live(self):
         """ltm_debug_pool_live: (blocks, bytes) of the device pool that are handed out"""
@@ -696,6 +747,17 @@ class SearchIndex:
             self.close()
         except Exception:
             pass
+
+
+def icp_params(**over):
+    """ltm_icp_params: ltm_icp_default_params with the given fields replaced"""
+    p = IcpParams()
+    load_library().ltm_icp_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in dict(IcpParams._fields_):
+            raise TypeError(f"ltm_icp_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
 
 
 def sc_params(**over):

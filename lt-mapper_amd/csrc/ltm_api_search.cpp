@@ -97,6 +97,13 @@ void ltm_detail::search_release_all(ltm_ctx* c)      // ltm_destroy: indices and
     c->result_open.clear();
 }
 
+void ltm_detail::search_view(ltm_ctx* c, ltm_search* s, SearchTree* tree, SearchFrame* frame)
+{
+    get_search(c, s);
+    *tree = s->tree();
+    *frame = s->f;
+}
+
 extern "C" {
 
 int ltm_search_build(ltm_ctx* c, ltm_cloud htarget, ltm_search** out)

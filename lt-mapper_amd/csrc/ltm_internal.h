@@ -669,6 +669,7 @@ void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
 void vgs_release_all(ltm_ctx* c);                                                 // ltm_api_voxel.cpp: open ltm_voxel_grid_scanset tickets, at ltm_destroy
 void search_release_all(ltm_ctx* c);                                              // ltm_api_search.cpp: open search indices and results, at ltm_destroy
+void search_view(ltm_ctx* c, struct ltm_search* s, SearchTree* tree, SearchFrame* frame);   // ltm_api_search.cpp: tree and frame of an index OF THIS CONTEXT (throws otherwise)
 void sc_release_all(ltm_ctx* c);                                                  // ltm_api_scancontext.cpp: open descriptor sets, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp

@@ -1,0 +1,329 @@
+// ltm_k_icp.hip -- batched point-to-point ICP of source clouds against search indices: the counterpart of the pcl::IterativeClosestPoint runs of
+// LTslam::doICPVirtualRelative / doICPGlobalRelative (ltslam/src/LTslam.cpp:187-301), one batch for all the loop pairs of addSCloops / addRSloops.
+// (gfx950 / CDNA4, wave64; part of libltm_hip.so -- shared definitions in ltm_kernels_common.h, launch wrappers declared in ltm_kernels.h)
+//
+// One iteration of the WHOLE batch is two launches.  k_icp_correspond runs one thread per source point of every pair that has not stopped (the grid is
+// over the concatenated sources, a per-block table names the pair): transform by the pair's accumulated T in double, round to float, exact 1-NN in the
+// target's box tree (the walk of ltm_search_walk.h, so distances and ties are those of ltm_knn_search with k = 1), and the moments of the kept pairs
+// (count, sum p, sum q, sum p q^T, sum d2) in double about the pair's origin -- map coordinates are kilometres from zero and raw second moments would
+// cancel.  The moments of a workgroup are reduced by wave shuffles, then through LDS in wave order, and written as ONE record: no floating-point
+// atomics anywhere, so the order of every sum is fixed by (source order, kIcpBlock) alone and a pair's result does not depend on what else is in the
+// batch.  k_icp_update runs one workgroup per pair: the pair's records added in block order, the rigid transform by a one-sided Jacobi SVD of the 3 x 3
+// cross-covariance in double, T <- T_iter T, PCL's stop tests, the trace row and the done flag.  The fitness score is one more pass of the first kernel
+// in score mode (every finite point, no distance limit) and k_icp_fitness.
+#include "ltm_kernels_common.h"
+#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves
+#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include <cfloat>
+#include <climits>
+namespace ltm {
+
+namespace {
+
+// sums over the workgroup of NV doubles per thread, in a fixed order: xor butterfly inside each wave, then waves 0..3 in order.  Thread c < NV returns the
+// total of value c (the other threads return 0)
+template <int NV>
+__device__ __forceinline__ double block_sum(double (&v)[NV], double (*lds)[kIcpPartial])
+{
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    }
+    const int wave = (int)(threadIdx.x >> 6);
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (int c = 0; c < NV; ++c) lds[wave][c] = v[c];
+    }
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x < (unsigned)NV) {
+        r = lds[0][threadIdx.x];
+        for (int w = 1; w < kIcpBlock / 64; ++w) r += lds[w][threadIdx.x];
+    }
+    return r;
+}
+
+// Rotation of the rigid transform that takes the p's onto the q's from their cross-covariance H = mean((p - pm)(q - qm)^T), row-major: with
+// H = U S V^T, R = V diag(1, 1, det(V U^T)) U^T (Umeyama without scale).  One-sided Jacobi: the columns of A = H are rotated until they are
+// orthogonal, A = U S and V collects the rotations.  u1, u2 are the two longest columns (the second orthogonalised against the first), u3 = u1 x u2
+// -- whichever sign the third left singular vector has, the det term makes the product the same.  Rank 1: u2 is the unit vector most orthogonal
+// to u1, made orthogonal; rank 0: R = I.  Always finite, orthonormal to rounding, det +1.
+__device__ void rotation_from_covariance(const double* H, double* R)
+{
+    double A[3][3], V[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) { A[r][k] = H[3 * r + k]; V[r][k] = r == k ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+        for (int i = 0; i < 2; ++i)
+            for (int j = i + 1; j < 3; ++j) {
+                const double al = A[0][i] * A[0][i] + A[1][i] * A[1][i] + A[2][i] * A[2][i];
+                const double be = A[0][j] * A[0][j] + A[1][j] * A[1][j] + A[2][j] * A[2][j];
+                const double ga = A[0][i] * A[0][j] + A[1][i] * A[1][j] + A[2][i] * A[2][j];
+                if (ga == 0.0 || fabs(ga) <= 1.0e-16 * sqrt(al * be)) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                for (int k = 0; k < 3; ++k) {
+                    const double ai = A[k][i], aj = A[k][j], vi = V[k][i], vj = V[k][j];
+                    A[k][i] = cs * ai - sn * aj; A[k][j] = sn * ai + cs * aj;
+                    V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
+                }
+            }
+        if (!rotated) break;
+    }
+    double s2[3];
+    for (int k = 0; k < 3; ++k) s2[k] = A[0][k] * A[0][k] + A[1][k] * A[1][k] + A[2][k] * A[2][k];
+    int k0 = 0, k1 = 1, k2 = 2;      // columns by descending length, the smaller index first among equals
+    if (s2[k1] > s2[k0]) { const int x = k0; k0 = k1; k1 = x; }
+    if (s2[k2] > s2[k1]) { const int x = k1; k1 = k2; k2 = x; }
+    if (s2[k1] > s2[k0]) { const int x = k0; k0 = k1; k1 = x; }
+    for (int k = 0; k < 9; ++k) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    if (!(s2[k0] > 0.0) || !isfinite(s2[k0])) return;
+    double u1[3], u2[3], u3[3];
+    const double n1 = sqrt(s2[k0]);
+    for (int r = 0; r < 3; ++r) u1[r] = A[r][k0] / n1;
+    double d = A[0][k1] * u1[0] + A[1][k1] * u1[1] + A[2][k1] * u1[2];
+    for (int r = 0; r < 3; ++r) u2[r] = A[r][k1] - d * u1[r];
+    double w2 = u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2];
+    if (!(w2 > 1.0e-24 * s2[k0])) {      // rank 1
+        int e = 0;
+        if (fabs(u1[1]) < fabs(u1[e])) e = 1;
+        if (fabs(u1[2]) < fabs(u1[e])) e = 2;
+        for (int r = 0; r < 3; ++r) u2[r] = (r == e ? 1.0 : 0.0) - u1[e] * u1[r];
+        w2 = u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2];
+    }
+    const double n2 = sqrt(w2);
+    for (int r = 0; r < 3; ++r) u2[r] /= n2;
+    u3[0] = u1[1] * u2[2] - u1[2] * u2[1];
+    u3[1] = u1[2] * u2[0] - u1[0] * u2[2];
+    u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
+    const double detV = V[0][k0] * (V[1][k1] * V[2][k2] - V[2][k1] * V[1][k2]) - V[0][k1] * (V[1][k0] * V[2][k2] - V[2][k0] * V[1][k2])
+                      + V[0][k2] * (V[1][k0] * V[2][k1] - V[2][k0] * V[1][k1]);
+    const double sg = detV < 0.0 ? -1.0 : 1.0;
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) R[3 * r + k] = (V[r][k0] * u1[k] + V[r][k1] * u2[k]) + sg * V[r][k2] * u3[k];
+}
+
+} // namespace
+
+// -------------------------------------------------------------------------------------------------- source order
+__global__ void __launch_bounds__(kIcpBlock)
+k_icp_source_keys(const IcpPair* __restrict__ pairs, const uint32_t* __restrict__ block_pair, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
+{
+    const IcpPair& P = pairs[block_pair[blockIdx.x]];
+    const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
+    if (local >= P.n) return;
+    const float4 p = P.src[local];
+    keys[P.first + local] = search_key(P.f, p.x, p.y, p.z);
+    idx[P.first + local] = local;
+}
+__global__ void __launch_bounds__(kIcpBlock)
+k_icp_gather_sources(const IcpPair* __restrict__ pairs, const uint32_t* __restrict__ block_pair, const uint32_t* __restrict__ order, float4* __restrict__ sorted)
+{
+    const IcpPair& P = pairs[block_pair[blockIdx.x]];
+    const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
+    if (local >= P.n) return;
+    const uint32_t j = order[P.first + local];
+    if (j < P.n) sorted[P.first + local] = P.src[j];
+}
+hipError_t icp_source_keys(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s)
+{
+    if (!n_blocks) return hipSuccess;
+    k_icp_source_keys<<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, block_pair, keys, idx);
+    return hipGetLastError();
+}
+size_t icp_sort_temp_bytes(size_t total, size_t n_pairs)
+{
+    size_t b = 0;
+    (void)rocprim::segmented_radix_sort_pairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                              (unsigned)total, (unsigned)n_pairs, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, 64);
+    return std::max<size_t>(b, 16);
+}
+hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
+                            const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes,
+                            hipStream_t s)
+{
+    if (!n_blocks || !total) return hipSuccess;
+    hipError_t e = rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, idx, order, (unsigned)total, (unsigned)n_pairs, offsets, offsets + 1,
+                                                       0, 64, s);
+    if (e != hipSuccess) return e;
+    k_icp_gather_sources<<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, block_pair, order, sorted);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ correspondences
+template <bool SCORE>
+__global__ void __launch_bounds__(kIcpBlock)
+k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__ st, const uint32_t* __restrict__ block_pair, const float4* __restrict__ sorted,
+                 double max_corr2, double* __restrict__ partials)
+{
+    __shared__ double lds[kIcpBlock / 64][kIcpPartial];
+    const uint32_t pi = block_pair[blockIdx.x];
+    const IcpState& S = st[pi];
+    if (!SCORE && S.done) return;      // the whole workgroup: the flag was written by an earlier launch
+    const IcpPair& P = pairs[pi];
+    const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
+    constexpr int NV = SCORE ? 2 : kIcpPartial;
+    double v[kIcpPartial];
+#pragma unroll
+    for (int c = 0; c < kIcpPartial; ++c) v[c] = 0.0;
+    if (local < P.n) {
+        const float4 p = sorted[P.first + local];
+        if (finite3(p.x, p.y, p.z)) {
+            const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+            const float qx = (float)(((S.T[0] * x + S.T[1] * y) + S.T[2] * z) + S.T[3]);
+            const float qy = (float)(((S.T[4] * x + S.T[5] * y) + S.T[6] * z) + S.T[7]);
+            const float qz = (float)(((S.T[8] * x + S.T[9] * y) + S.T[10] * z) + S.T[11]);
+            // a transform that overflows float leaves no query: the point is skipped like a non-finite source point
+            if (finite3(qx, qy, qz)) {
+                const SearchTree t = P.t;
+                float bd = __builtin_inff();
+                int bi = INT_MAX;
+                uint32_t bj = 0;
+                auto visit = [&](uint32_t l) {
+                    const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
+                    for (uint32_t j = a; j < b; ++j) {
+                        const float4 tp = t.pts[j];
+                        const float d = sqdist_l2simple(qx, qy, qz, tp.x, tp.y, tp.z);
+                        const int i = (int)t.idx[j];
+                        if (pair_less(d, i, bd, bi)) { bd = d; bi = i; bj = j; }
+                    }
+                };
+                uint32_t sa, sb;
+                seed_leaves(t, search_key(P.f, qx, qy, qz), 1u, sa, sb);
+                for (uint32_t l = sa; l <= sb; ++l) visit(l);
+                walk(t, qx, qy, qz, sa, sb, [&](double lb) { return lb > (double)bd; }, visit);
+                if (SCORE) {
+                    if (bi != INT_MAX) { v[0] = 1.0; v[1] = (double)bd; }
+                } else if (bi != INT_MAX && (double)bd <= max_corr2) {
+                    const float4 tp = t.pts[bj];
+                    const double px = (double)qx - P.o[0], py = (double)qy - P.o[1], pz = (double)qz - P.o[2];
+                    const double tx = (double)tp.x - P.o[0], ty = (double)tp.y - P.o[1], tz = (double)tp.z - P.o[2];
+                    v[0] = 1.0;
+                    v[1] = px; v[2] = py; v[3] = pz;
+                    v[4] = tx; v[5] = ty; v[6] = tz;
+                    v[7] = px * tx; v[8] = px * ty; v[9] = px * tz;
+                    v[10] = py * tx; v[11] = py * ty; v[12] = py * tz;
+                    v[13] = pz * tx; v[14] = pz * ty; v[15] = pz * tz;
+                    v[16] = (double)bd;
+                }
+            }
+        }
+    }
+    double* out = partials + (size_t)blockIdx.x * kIcpPartial;
+    if (SCORE) {
+        double w[NV] = {v[0], v[1]};
+        const double r = block_sum<NV>(w, lds);
+        if (threadIdx.x < (unsigned)NV) out[threadIdx.x == 0 ? 0 : 16] = r;
+    } else {
+        const double r = block_sum<kIcpPartial>(v, lds);
+        if (threadIdx.x < (unsigned)kIcpPartial) out[threadIdx.x] = r;
+    }
+}
+hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32_t* block_pair, uint32_t n_blocks, const float4* sorted, double max_corr2,
+                          int score, double* partials, hipStream_t s)
+{
+    if (!n_blocks) return hipSuccess;
+    if (score) k_icp_correspond<true><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
+    else k_icp_correspond<false><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
+    return hipGetLastError();
+}
+
+// --------------------------------------------------------------------------------------------------------- update
+__global__ void __launch_bounds__(64)
+k_icp_update(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const double* __restrict__ partials, int max_iterations, double eps_t, double eps_mse,
+             double* __restrict__ trace, uint32_t* __restrict__ unfinished)
+{
+    __shared__ double m[kIcpPartial];
+    const uint32_t pi = blockIdx.x;
+    IcpState& S = st[pi];
+    if (S.done) return;
+    const IcpPair& P = pairs[pi];
+    if (threadIdx.x < (unsigned)kIcpPartial) {
+        double a = 0.0;
+        for (uint32_t b = 0; b < P.n_blocks; ++b) a += partials[(size_t)(P.block0 + b) * kIcpPartial + threadIdx.x];      // block order
+        m[threadIdx.x] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double n = m[0];
+    const int it = S.iterations;
+    const double mse = n > 0.0 ? m[16] / n : DBL_MAX;
+    S.n_corr = (uint32_t)n;
+    S.last_mse = mse;
+    if (trace && it < max_iterations) {
+        double* row = trace + ((size_t)pi * (size_t)max_iterations + (size_t)it) * 2;
+        row[0] = n;
+        if (n > 0.0) row[1] = mse;      // otherwise the NaN the buffer was filled with stays
+    }
+    int state = -1;
+    if (n < 3.0) {
+        state = 0;
+    } else {
+        double pm[3], qm[3], H[9], R[9], t[3];
+        for (int k = 0; k < 3; ++k) { pm[k] = m[1 + k] / n; qm[k] = m[4 + k] / n; }
+        for (int r = 0; r < 3; ++r)
+            for (int k = 0; k < 3; ++k) H[3 * r + k] = m[7 + 3 * r + k] / n - pm[r] * qm[k];
+        rotation_from_covariance(H, R);
+        // t = qm - R pm with the means taken back to the cloud's coordinates
+        for (int r = 0; r < 3; ++r) {
+            const double px = pm[0] + P.o[0], py = pm[1] + P.o[1], pz = pm[2] + P.o[2];
+            t[r] = (qm[r] + P.o[r]) - ((R[3 * r] * px + R[3 * r + 1] * py) + R[3 * r + 2] * pz);
+        }
+        double Tn[12];
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 0; k < 4; ++k) Tn[4 * r + k] = (R[3 * r] * S.T[k] + R[3 * r + 1] * S.T[4 + k]) + R[3 * r + 2] * S.T[8 + k];
+            Tn[4 * r + 3] += t[r];
+        }
+        for (int k = 0; k < 12; ++k) S.T[k] = Tn[k];
+        S.iterations = it + 1;
+        const double cos_angle = 0.5 * ((R[0] + R[4] + R[8]) - 1.0);
+        const double t2 = (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
+        const double dm = fabs(mse - S.prev_mse);
+        if (it + 1 >= max_iterations) state = 1;
+        else if (cos_angle >= 1.0 - eps_t && t2 <= eps_t) state = 2;
+        else if (dm < 1.0e-12) state = 3;
+        else if (dm / S.prev_mse < eps_mse) state = 4;
+        else S.prev_mse = mse;
+    }
+    if (state >= 0) {
+        S.state = state;
+        S.converged = state > 0 ? 1 : 0;
+        S.done = 1;
+        atomicSub(unfinished, 1u);
+    }
+}
+hipError_t icp_update(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, int max_iterations, double transformation_epsilon,
+                      double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s)
+{
+    if (!n_pairs) return hipSuccess;
+    k_icp_update<<<dim3((unsigned)n_pairs), dim3(64), 0, s>>>(pairs, st, partials, max_iterations, transformation_epsilon, euclidean_fitness_epsilon, trace, unfinished);
+    return hipGetLastError();
+}
+
+// fitness = mean d2 of the score pass (DBL_MAX if no point counted)
+__global__ void __launch_bounds__(64)
+k_icp_fitness(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const double* __restrict__ partials)
+{
+    __shared__ double m[2];
+    const IcpPair& P = pairs[blockIdx.x];
+    if (threadIdx.x < 2) {
+        const int c = threadIdx.x == 0 ? 0 : 16;
+        double a = 0.0;
+        for (uint32_t b = 0; b < P.n_blocks; ++b) a += partials[(size_t)(P.block0 + b) * kIcpPartial + c];
+        m[threadIdx.x] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) st[blockIdx.x].fitness = m[0] > 0.0 ? m[1] / m[0] : DBL_MAX;
+}
+hipError_t icp_fitness(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, hipStream_t s)
+{
+    if (!n_pairs) return hipSuccess;
+    k_icp_fitness<<<dim3((unsigned)n_pairs), dim3(64), 0, s>>>(pairs, st, partials);
+    return hipGetLastError();
+}
+
+} // namespace ltm

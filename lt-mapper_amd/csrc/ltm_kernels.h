@@ -245,6 +245,30 @@ size_t     radius_sort_temp_bytes(size_t total, size_t n);
 hipError_t radius_fill(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, const uint64_t* full_off, uint64_t total_full,
                        const uint64_t* out_off, uint64_t* pairs, uint64_t* pairs_sorted, int32_t* out_idx, float* out_d2, void* temp, size_t temp_bytes, hipStream_t s);
 
+// ---- batched point-to-point ICP over search indices (ltm_k_icp.hip; LTslam.cpp:187-301) ----
+static constexpr int kIcpBlock = 256;           // source points per workgroup of the correspondence kernel = per partial record
+static constexpr int kIcpPartial = 17;          // doubles per partial record: count, sum p (3), sum q (3), sum p q^T (9, row-major), sum d2
+// one pair of the batch: the target's tree and frame, the source as given (src, n points), its slice [first, first + n) of the batch's sorted sources and
+// its workgroups [block0, block0 + n_blocks) of the correspondence grid; o: the origin the moments are taken about (the corner of the target's frame)
+struct IcpPair { SearchTree t; SearchFrame f; const float4* src; double o[3]; uint64_t first; uint32_t n, block0, n_blocks, pad; };
+// what k_icp_update keeps per pair between iterations (T: rows 0..2 of the accumulated transform, row-major)
+struct IcpState { double T[12]; double prev_mse, last_mse, fitness; int32_t iterations, state, converged, done; uint32_t n_corr, pad; };
+// codes of every source point under its target's frame (keys) and its position in its source (idx); grid over the blocks of block_pair
+hipError_t icp_source_keys(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s);
+size_t     icp_sort_temp_bytes(size_t total, size_t n_pairs);
+// every source sorted by code (offsets: n_pairs + 1 slice bounds), then sorted[first + j] = src[order[first + j]]
+hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
+                            const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes,
+                            hipStream_t s);
+// one record of kIcpPartial doubles per workgroup; score = 0: correspondences within max_corr2 of the pairs not done yet, 1: count and sum d2 of every
+// finite point of every pair, no limit
+hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32_t* block_pair, uint32_t n_blocks, const float4* sorted, double max_corr2,
+                          int score, double* partials, hipStream_t s);
+// per pair: partials added in block order, transform estimate, stop tests; trace (nullable): n_pairs x max_iterations x 2; unfinished: one counter
+hipError_t icp_update(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, int max_iterations, double transformation_epsilon,
+                      double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s);
+hipError_t icp_fitness(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, hipStream_t s);
+
 // ---- scan context (ltm_k_scancontext.hip; Scancontext.cpp:69-324) ----
 struct ScGeom { double lidar_height, max_radius; int R, S; };      // rings x sectors
 // makeScancontext for keyframes [kb, kb + nb): bins (zeroed by the caller, R * S uint32 per keyframe) receive the order-preserving key of the largest
