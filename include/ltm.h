@@ -397,12 +397,11 @@ int  ltm_sc_free(ltm_ctx*, ltm_sc*);
  *  det +1, and reproducible.
  *  trace (n_pairs x max_iterations x 2 doubles, may be NULL): row i of a pair = (n_corr, mse) of its iteration i, counted from 0, the iteration that stopped
  *  in step 4 included (mse NaN if it kept nothing); rows that never ran are NaN.
- *  targets[i] is an index from ltm_search_build (the same index may serve many pairs), sources[i] a cloud; both belong to this context (a handle of
+ *  targets[i] is an index from ltm_search_build or ltm_search_build_scanset (the same index may serve many pairs), sources[i] a cloud; both belong to this context (a handle of
  *  another context is LTM_E_INVALID).  init16_or_null: n_pairs row-major 4x4 doubles whose last row is taken to be 0 0 0 1, NULL = identity.  A NULL
  *  parameter pointer means the defaults.  Each source (< 2^31 points, < 2^31 in all) is copied in sorted order for the call; all device memory comes from
  *  the context's pool and is back when the call returns, on every error path too.  The call returns when the host arrays are written.
- *  Out of scope: assembling the submaps (loopFindNearKeyframesCloud and its float Affine3f transformPointCloud), Euler / gtsam::Pose3 conversions,
- *  point-to-plane and generalized ICP. */
+ *  The submaps themselves come from the section "loop submaps" below.  Out of scope: Euler / gtsam::Pose3 conversions, point-to-plane and generalized ICP. */
 typedef struct {
     double max_corr_dist;             /* 150.0  setMaxCorrespondenceDistance, LTslam.cpp:207 */
     int    max_iterations;            /* 100    :208 */
@@ -422,6 +421,48 @@ void ltm_icp_default_params(ltm_icp_params*);     /* host only, needs no device 
 int  ltm_icp_align(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources,
                    const double* init16_or_null /* n_pairs x 16, NULL = identity */, const ltm_icp_params*,
                    ltm_icp_result* results_host, double* trace_host_or_null /* n_pairs x max_iterations x 2: (n_corr, mse) per iteration, rest NaN */);
+/* the same routine with sources[i] = keyframe source_kf[i] of the scan set `sources` (a submap of ltm_submaps_assemble) read in place, no cloud handle and
+ * no copy per pair; a keyframe outside the set is LTM_E_INVALID.  Results are those of ltm_icp_align on ltm_scanset_keyframe of the same keyframes, bit for bit. */
+int  ltm_icp_align_scanset(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf /* n_pairs */,
+                           const double* init16_or_null, const ltm_icp_params*, ltm_icp_result* results_host, double* trace_host_or_null);
+
+/* ----------------------------------------------------------- loop submaps ---- */
+/* The step between a loop proposal and its ICP verification: the two clouds of every ICP run of LTslam::doICPVirtualRelative / doICPGlobalRelative
+ * (ltslam/src/LTslam.cpp:187-301) are built by Session::loopFindNearKeyframesLocalCoord / CentralCoord (ltslam/src/Session.cpp:91-142) -- the keyframes
+ * within +-searchNum of a key, each moved by the float Eigen::Affine3f that pcl::getTransformation makes of a 6-D pose (ltslam/src/utility.cpp:80-103),
+ * concatenated and put through pcl::VoxelGrid at 0.3 m (Session.cpp:18-19) -- and a kd-tree is built over every target.  Here all windows of a batch are
+ * assembled by ONE gather launch and gridded together, and all their search indices are built together.  What this library takes the reference to do:
+ *  - pose -> affine (ltm_pose6d_to_affine3f; host only, needs no device): pcl::getTransformation(x, y, z, roll, pitch, yaw) in float as PCL 1.10 writes it
+ *    (common/impl/eigen.hpp; PCL is not available here, so "as understood"): A = cosf(yaw), B = sinf(yaw), C = cosf(pitch), D = sinf(pitch), E = cosf(roll),
+ *    F = sinf(roll), DE = D*E, DF = D*F; row 0 = (A*C, A*DF - B*E, B*F + A*DE, x), row 1 = (B*C, A*E + B*DF, B*DE - A*F, y), row 2 = (-D, C*F, C*E, z); every
+ *    product and sum a separate float rounding.  xyzrpy: n x 6 floats (x y z roll pitch yaw), affine12: n x 12 floats, rows 0..2 row-major.
+ *  - window w of ltm_submaps_assemble holds the points of keyframes keys[w] - search_num ... keys[w] + search_num in ascending order; a keyframe index
+ *    outside [0, n_kf) is skipped (Session.cpp:101), so any int32 key is legal; a window with no point is an empty keyframe of `out` (:106).
+ *  - every point is moved by its keyframe's affine as utility.cpp:97-99 does: x' = ((t00*x + t01*y) + t02*z) + t03 in float, left to right, without fused
+ *    multiply-adds, likewise y', z'; the intensity is copied.  affine12 = NULL means the identity for every keyframe (the LocalCoord form, whose pose is the
+ *    origin): the arithmetic is still performed, so -0.0 becomes +0.0 and an infinite coordinate makes NaNs, as the reference's multiply by identity does.
+ *  - each window is then gridded by pcl::VoxelGrid at `leaf` with the machinery of ltm_voxel_grid_scanset, unchanged: the same frames, the same "leaf size
+ *    is too small" pass-through, the same treatment of non-finite points.  order = 1 sums a voxel's points in the order PCL's std::sort leaves them in
+ *    (through the host threads of that path), order = 0 in input order, entirely on the device (the last bit of a centroid of three or more points may
+ *    differ).  LTM_VOXELGRID_ORDER is not read here.
+ * DEPARTURES: leaf == 0 means no grid -- `out` is the transformed concatenation (the reference always grids).  The reference transforms on 8 OpenMP threads
+ * and grids each window alone; neither changes a result.
+ * Domain: search_num < 0, a negative or non-finite leaf, an order other than 0 or 1 are LTM_E_INVALID; a batch whose windows hold 2^32 - 1 points or more
+ * before the grid (the grid's 32-bit point indices) is LTM_E_UNSUPPORTED -- split the batch.  All scratch memory is back in the pool when the call returns,
+ * on every error path too. */
+int ltm_pose6d_to_affine3f(const float* xyzrpy /* n x 6: x y z roll pitch yaw */, size_t n, float* affine12 /* n x 12, rows 0..2 row-major */);
+int ltm_submaps_assemble(ltm_ctx*, ltm_scanset scans, const float* affine12_host_or_null /* n_kf x 12; NULL = identity for every keyframe */,
+                         const int32_t* keys_host, size_t n_windows, int search_num, float leaf, int order, ltm_scanset* out);
+/* kdtree->setInputCloud for every keyframe of [kf_begin, kf_end) of a scan set at once (the submaps above): out receives kf_end - kf_begin handles, each
+ * interchangeable with ltm_search_build of that keyframe as a cloud -- the same frame (the keyframe's own finite bounding box, 2097151 / extent), the same
+ * finite count, leaf size and box tree -- so every query through it (ltm_knn_search, ltm_radius_search, ltm_icp_align) returns the bytes the single build
+ * returns.  (The promise is on query results, not on the index arrays: the batch is ordered by ONE segmented radix sort, which need not be stable, so points
+ * with equal codes may sit in another order; the search is exact and ties are ordered by target index.)  The whole batch is a fixed number of launches --
+ * segmented bounding boxes with finite counts, keys, sort, gather, all box trees -- and ONE read-back by the host (the boxes), where n single builds pay one
+ * each.  Every handle is freed on its own with ltm_search_free; the pool blocks the batch shares return when its last handle is freed (ltm_destroy
+ * releases what is left).  Empty keyframes and keyframes without a finite point give valid empty indices; a range outside the set is LTM_E_INVALID, a batch
+ * of 2^31 points or more LTM_E_UNSUPPORTED.  On an error no handle is returned and nothing stays allocated. */
+int ltm_search_build_scanset(ltm_ctx*, ltm_scanset, size_t kf_begin, size_t kf_end, ltm_search** out /* kf_end - kf_begin handles */);
 
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the

@@ -146,6 +146,10 @@ SIGNATURES = {
     "ltm_sc_free": (_i, [_vp, _vp]),
     "ltm_icp_default_params": (None, [C.POINTER(IcpParams)]),
     "ltm_icp_align": (_i, [_vp, _sz, C.POINTER(_vp), _pu64, _vp, C.POINTER(IcpParams), _vp, _vp]),
+    "ltm_icp_align_scanset": (_i, [_vp, _sz, C.POINTER(_vp), _u64, _vp, _vp, C.POINTER(IcpParams), _vp, _vp]),
+    "ltm_pose6d_to_affine3f": (_i, [_vp, _sz, _vp]),
+    "ltm_submaps_assemble": (_i, [_vp, _u64, _vp, _vp, _sz, _i, _f, _i, _pu64]),
+    "ltm_search_build_scanset": (_i, [_vp, _u64, _sz, _sz, C.POINTER(_vp)]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -212,6 +216,18 @@ def inverse4x4(m):
     if load_library().ltm_inverse4x4(a.ctypes.data, out.ctypes.data) != 0:
         raise ValueError("singular or non-finite matrix")
     return out.reshape(4, 4)
+
+
+def pose6d_to_affine3f(xyzrpy):
+    """ltm_pose6d_to_affine3f: (n, 6) poses x y z roll pitch yaw -> (n, 3, 4) float32 affines, pcl::getTransformation in float (needs no device)"""
+    a = np.ascontiguousarray(xyzrpy, dtype=np.float32).reshape(-1, 6)
+    out = np.empty((a.shape[0], 3, 4), dtype=np.float32)
+    if a.shape[0] and load_library().ltm_pose6d_to_affine3f(a.ctypes.data, a.shape[0], out.ctypes.data) != 0:
+        raise ValueError("ltm_pose6d_to_affine3f failed")
+    return out
+
+
+ORDERS = {"input": 0, "pcl": 1}
 
 
 def _np_pts(a):
@@ -506,6 +522,75 @@ class Context:
         self._ck(self.lib.ltm_search_build(self.h, cloud.h, C.byref(h)))
         return SearchIndex(self, h.value)
 
+    def search_index_batch(self, scanset, kf_begin=0, kf_end=None):
+        """ltm_search_build_scanset: one SearchIndex per keyframe [kf_begin, kf_end) of a ScanSet, built together (a fixed number of launches and one
+        read-back for the whole batch); each is interchangeable with search_index(scan_of_keyframe(scanset, kf))"""
+        ke = scanset.n_kf if kf_end is None else kf_end
+        n = max(int(ke) - int(kf_begin), 0)
+        hs = (_vp * max(n, 1))()
+        self._ck(self.lib.ltm_search_build_scanset(self.h, scanset.h, kf_begin, ke, hs))
+        return [SearchIndex(self, hs[i]) for i in range(n)]
+
+    # ---- loop submaps
+    def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
+        """ltm_submaps_assemble: Session::loopFindNearKeyframesLocalCoord (affines=None) / CentralCoord (affines: (n_kf, 3, 4) float32, see
+        pose6d_to_affine3f) for every key at once.  Returns a ScanSet with one keyframe per key: keyframes key - search_num ... key + search_num of
+        `scans`, each moved by its affine in float, concatenated and gridded by pcl::VoxelGrid at `leaf` (0: no grid); order: "pcl" sums a voxel in
+        PCL's std::sort order (host threads), "input" in input order on the device alone."""
+        k = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+        a = None
+        if affines is not None:
+            a = np.ascontiguousarray(affines, dtype=np.float32).reshape(-1, 12)
+            if a.shape[0] != scans.n_kf:
+                raise ValueError("one affine per keyframe of the scan set")
+        out = _u64()
+        self._ck(self.lib.ltm_submaps_assemble(self.h, scans.h, None if a is None else a.ctypes.data, k.ctypes.data, k.size, int(search_num), float(leaf),
+                                               ORDERS[order], C.byref(out)))
+        return ScanSet(self, out.value)
+
+    def verify_loops(self, target_scans, source_scans, pairs, target_affines=None, source_affines=None, search_num=25, leaf=0.3,
+                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, **icp):
+        """The body of LTslam::addSCloops' loop (LTslam.cpp:370-416) for all `pairs` = (target key, source key): the target submap (+-search_num
+        keyframes) and its search index are made ONCE per distinct target key, the source submap is the source keyframe alone (searchNum = 0), every
+        source is aligned to its target by icp_align, and a pair is accepted iff converged and fitness <= fitness_threshold (loopFitnessScoreThreshold,
+        0.5 by default: ltslam/src/RosParamServer.cpp:23).  The work is cut into batches of consecutive pairs whose submaps hold at most max_batch_points
+        points before the grid (estimated from the scan sets' offsets).  Returns (ICP_RESULT records, accept mask), one entry per pair."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        res = np.zeros(len(pairs), dtype=ICP_RESULT)
+        t_off = target_scans.offsets().astype(np.int64)
+        s_off = source_scans.offsets().astype(np.int64)
+
+        def window_points(off, key, sn):
+            lo, hi = max(key - sn, 0), min(key + sn, len(off) - 2)
+            return int(off[hi + 1] - off[lo]) if hi >= lo else 0
+
+        batches, cur, seen, pts = [], [], set(), 0
+        for i, (tk, sk) in enumerate(pairs):
+            add = window_points(s_off, int(sk), 0) + (0 if int(tk) in seen else window_points(t_off, int(tk), search_num))
+            if cur and pts + add > max_batch_points:
+                batches.append(cur)
+                cur, seen, pts = [], set(), 0
+                add = window_points(s_off, int(sk), 0) + window_points(t_off, int(tk), search_num)
+            cur.append(i)
+            seen.add(int(tk))
+            pts += add
+        if cur:
+            batches.append(cur)
+        for b in batches:
+            tkeys = sorted({int(pairs[i, 0]) for i in b})
+            slot = {k: j for j, k in enumerate(tkeys)}
+            tsub = self.loop_submaps(target_scans, tkeys, search_num, leaf, target_affines, order)
+            ssub = self.loop_submaps(source_scans, [int(pairs[i, 1]) for i in b], 0, leaf, source_affines, order)
+            idx = self.search_index_batch(tsub)
+            try:
+                res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], (ssub, j)) for j, i in enumerate(b)], **icp)
+            finally:
+                for x in idx:
+                    x.close()
+                tsub.free()
+                ssub.free()
+        return res, (res["converged"] != 0) & (res["fitness"] <= fitness_threshold)
+
     # ---- scan context
     def scan_contexts(self, scans, kf_begin=0, kf_end=None, **params):
         """ltm_sc_from_scanset: Scan Context descriptors and keys of keyframes [kf_begin, kf_end) of a ScanSet (makeAndSaveScancontextAndKeys per
@@ -527,7 +612,8 @@ class Context:
     # ---- icp
     def icp_align(self, pairs, init=None, trace=False, **params):
         """ltm_icp_align: point-to-point ICP of every (target, source) of `pairs` in one batch -- target a SearchIndex of this context (one index
-        may serve many pairs), source a Cloud of this context or an (n, 3) / (n, 4) array.  init: (n, 4, 4) source->target start transforms
+        may serve many pairs), source a Cloud of this context, an (n, 3) / (n, 4) array or (ScanSet, keyframe) -- when every source is a keyframe of one
+        ScanSet they are read in place (ltm_icp_align_scanset).  init: (n, 4, 4) source->target start transforms
         (None: identity); params: the fields of ltm_icp_params, the reference's values by default.  Returns a record array of dtype ICP_RESULT
         (T, fitness, last_mse, converged, iterations, state, n_corr), one record per pair; with trace=True also the (n, max_iterations, 2)
         array of (n_corr, mse) per iteration, NaN where no iteration ran."""
@@ -543,17 +629,27 @@ class Context:
                     raise TypeError("the target of a pair must be a SearchIndex (Context.search_index)")
             made = []
             try:
-                src = []
-                for _, s_ in pairs:
-                    if not isinstance(s_, Cloud):
-                        s_ = self.upload(_xyzi(s_))
-                        made.append(s_)
-                    src.append(s_)
                 th = (_vp * n)(*[t.h for t, _ in pairs])
-                sh = (C.c_uint64 * n)(*[s_.h for s_ in src])
                 i16 = None
                 if init is not None:
                     i16 = np.ascontiguousarray(init, dtype=np.float64).reshape(n, 16)
+                in_set = [isinstance(s_, tuple) and len(s_) == 2 and isinstance(s_[0], ScanSet) for _, s_ in pairs]
+                if all(in_set) and all(s_[0] is pairs[0][1][0] for _, s_ in pairs):
+                    # every source a keyframe of ONE scan set (the submaps of loop_submaps): read in place
+                    kf = np.ascontiguousarray([s_[1] for _, s_ in pairs], dtype=np.uint32)
+                    self._ck(self.lib.ltm_icp_align_scanset(self.h, n, th, pairs[0][1][0].h, kf.ctypes.data, None if i16 is None else i16.ctypes.data,
+                                                            C.byref(p), res.ctypes.data, tr.ctypes.data if trace and tr.size else None))
+                    return (res, tr) if trace else res
+                src = []
+                for (_, s_), sset in zip(pairs, in_set):
+                    if sset:
+                        s_ = self.scan_of_keyframe(s_[0], int(s_[1]))
+                        made.append(s_)
+                    elif not isinstance(s_, Cloud):
+                        s_ = self.upload(_xyzi(s_))
+                        made.append(s_)
+                    src.append(s_)
+                sh = (C.c_uint64 * n)(*[s_.h for s_ in src])
                 self._ck(self.lib.ltm_icp_align(self.h, n, th, sh, None if i16 is None else i16.ctypes.data, C.byref(p), res.ctypes.data,
                                                 tr.ctypes.data if trace and tr.size else None))
             finally:

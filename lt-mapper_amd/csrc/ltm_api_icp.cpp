@@ -20,6 +20,123 @@ void check_params(const ltm_icp_params& p)
     LTM_REQUIRE(p.max_iterations <= (1 << 20), "max_iterations must be at most 2^20");
 }
 
+// the routine behind both entry points: source_of(i) names the points of pair i's source (a cloud, or a keyframe of a scan set read in place)
+struct IcpSource { const float4* d; size_t n; };
+template <class SourceOf>
+void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, SourceOf&& source_of, const double* init16, const ltm_icp_params* params,
+                    ltm_icp_result* results, double* trace)
+{
+    ltm_icp_params prm;
+    ltm_icp_default_params(&prm);
+    if (params) prm = *params;
+    check_params(prm);
+    if (!n_pairs) return;
+    LTM_REQUIRE(targets && results, "null argument");
+    LTM_REQUIRE(n_pairs < 0x7fffffffull, "too many pairs");
+    const int max_it = prm.max_iterations;
+    const size_t trace_n = trace && max_it > 0 ? n_pairs * (size_t)max_it * 2 : 0;
+
+    // the batch: every pair's slice of the concatenated sources and of the correspondence grid.  A pair with nothing to do (empty source, empty
+    // target, no iteration allowed) gets no point and no workgroup and keeps the state it starts with
+    std::vector<IcpPair> pairs(n_pairs);
+    std::vector<IcpState> st(n_pairs);
+    std::vector<uint64_t> off(n_pairs + 1, 0);
+    std::vector<uint32_t> block_pair;
+    uint32_t active = 0;
+    for (size_t i = 0; i < n_pairs; ++i) {
+        IcpPair& P = pairs[i];
+        memset(&P, 0, sizeof P);
+        search_view(c, targets[i], &P.t, &P.f);
+        const IcpSource src = source_of(i);
+        LTM_REQUIRE(src.n < 0x80000000ull, "a source must have fewer than 2^31 points");
+        const bool run = src.n && P.t.Mf && max_it >= 1;
+        P.src = src.d;
+        P.o[0] = P.f.ox; P.o[1] = P.f.oy; P.o[2] = P.f.oz;
+        P.first = off[i];
+        P.n = run ? (uint32_t)src.n : 0u;
+        P.block0 = (uint32_t)block_pair.size();
+        P.n_blocks = (P.n + kIcpBlock - 1) / kIcpBlock;
+        off[i + 1] = off[i] + P.n;
+        LTM_REQUIRE(off[i + 1] < 0x80000000ull, "the sources of one batch must have fewer than 2^31 points in all");
+        block_pair.insert(block_pair.end(), P.n_blocks, (uint32_t)i);
+        IcpState& S = st[i];
+        memset(&S, 0, sizeof S);
+        const double* T0 = init16 ? init16 + 16 * i : nullptr;
+        for (int k = 0; k < 12; ++k) {
+            S.T[k] = T0 ? T0[k] : (k % 5 == 0 ? 1.0 : 0.0);
+            LTM_REQUIRE(std::isfinite(S.T[k]), "an initial transform is not finite");
+        }
+        S.prev_mse = S.last_mse = S.fitness = DBL_MAX;
+        S.done = run ? 0 : 1;
+        active += run ? 1u : 0u;
+    }
+    const size_t total = off[n_pairs];
+    const uint32_t n_blocks = (uint32_t)block_pair.size();
+
+    if (active) {
+        DevBuf d_pairs(c, n_pairs * sizeof(IcpPair)), d_st(c, n_pairs * sizeof(IcpState)), d_off(c, (n_pairs + 1) * 8), d_bp(c, (size_t)n_blocks * 4);
+        DevBuf d_sorted(c, total * sizeof(float4)), d_part(c, (size_t)n_blocks * kIcpPartial * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
+        h2d(c, d_pairs.p, pairs.data(), n_pairs * sizeof(IcpPair));
+        h2d(c, d_st.p, st.data(), n_pairs * sizeof(IcpState));
+        h2d(c, d_off.p, off.data(), (n_pairs + 1) * 8);
+        h2d(c, d_bp.p, block_pair.data(), (size_t)n_blocks * 4);
+        h2d(c, d_unf.p, &active, 4);
+        if (trace_n) LTM_HIP(hipMemsetAsync(d_trace.p, 0xff, trace_n * 8, c->stream));      // all ones: a NaN
+        const IcpPair* dp = d_pairs.as<IcpPair>();
+        IcpState* ds = d_st.as<IcpState>();
+        const uint32_t* bp = d_bp.as<uint32_t>();
+        {
+            // each source once into the code order of its target's frame: the lanes of a wavefront then walk the same part of the tree
+            ProfScope ps(c, "icp_prepare", (double)total, 72.0 * (double)total);
+            DevBuf keys(c, total * 8), keys_sorted(c, total * 8), idx(c, total * 4), order(c, total * 4);
+            const size_t tb = icp_sort_temp_bytes(total, n_pairs);
+            DevBuf temp(c, tb);
+            LTM_HIP(icp_source_keys(dp, bp, n_blocks, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
+            LTM_HIP(icp_sort_sources(dp, bp, n_blocks, n_pairs, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), idx.as<uint32_t>(),
+                                     order.as<uint32_t>(), d_sorted.as<float4>(), temp.p, tb, c->stream));
+        }
+        const double max2 = prm.max_corr_dist * prm.max_corr_dist;
+        const int poll = poll_interval();
+        for (int it = 0; it < max_it;) {
+            const int chunk = std::min(poll, max_it - it);
+            {
+                ProfScope ps(c, "icp_iter", (double)total * chunk, 16.0 * (double)total * chunk, -1.0, false);
+                if (ps.cls >= 0) c->prof[ps.cls].launches += 2 * (uint64_t)chunk;
+                for (int k = 0; k < chunk; ++k) {
+                    LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), max2, 0, d_part.as<double>(), c->stream));
+                    LTM_HIP(icp_update(dp, ds, n_pairs, d_part.as<double>(), max_it, prm.transformation_epsilon, prm.euclidean_fitness_epsilon,
+                                       trace_n ? d_trace.as<double>() : nullptr, d_unf.as<uint32_t>(), c->stream));
+                }
+            }
+            it += chunk;
+            if (it >= max_it) break;
+            uint32_t left = 0;
+            d2h(c, &left, d_unf.p, 4);
+            if (!left) break;
+        }
+        {
+            ProfScope ps(c, "icp_fitness", (double)total, 16.0 * (double)total, -1.0, false);
+            if (ps.cls >= 0) c->prof[ps.cls].launches += 2;
+            LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), 0.0, 1, d_part.as<double>(), c->stream));
+            LTM_HIP(icp_fitness(dp, ds, n_pairs, d_part.as<double>(), c->stream));
+        }
+        d2h(c, st.data(), d_st.p, n_pairs * sizeof(IcpState));
+        if (trace_n) d2h(c, trace, d_trace.p, trace_n * 8);
+    } else if (trace_n) {
+        for (size_t k = 0; k < trace_n; ++k) trace[k] = std::nan("");
+    }
+    for (size_t i = 0; i < n_pairs; ++i) {
+        const IcpState& S = st[i];
+        ltm_icp_result& r = results[i];
+        for (int k = 0; k < 12; ++k) r.T[k] = S.T[k];
+        r.T[12] = r.T[13] = r.T[14] = 0.0; r.T[15] = 1.0;
+        // a pair that never ran has no 1-NN distance at all; one that ran reports the score pass
+        r.fitness = pairs[i].n ? S.fitness : DBL_MAX;
+        r.last_mse = S.last_mse;
+        r.converged = S.converged; r.iterations = S.iterations; r.state = S.state; r.n_corr = S.n_corr;
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -37,115 +154,21 @@ int ltm_icp_align(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, const 
                   ltm_icp_result* results, double* trace)
 {
     return guarded(c, [&] {
-        ltm_icp_params prm;
-        ltm_icp_default_params(&prm);
-        if (params) prm = *params;
-        check_params(prm);
-        if (!n_pairs) return;
-        LTM_REQUIRE(targets && sources && results, "null argument");
-        LTM_REQUIRE(n_pairs < 0x7fffffffull, "too many pairs");
-        const int max_it = prm.max_iterations;
-        const size_t trace_n = trace && max_it > 0 ? n_pairs * (size_t)max_it * 2 : 0;
+        LTM_REQUIRE(!n_pairs || sources, "null argument");
+        icp_align_impl(c, n_pairs, targets, [&](size_t i) { const Cloud& src = get_cloud(c, sources[i]); return IcpSource{src.d, src.n}; }, init16, params, results, trace);
+    });
+}
 
-        // the batch: every pair's slice of the concatenated sources and of the correspondence grid.  A pair with nothing to do (empty source, empty
-        // target, no iteration allowed) gets no point and no workgroup and keeps the state it starts with
-        std::vector<IcpPair> pairs(n_pairs);
-        std::vector<IcpState> st(n_pairs);
-        std::vector<uint64_t> off(n_pairs + 1, 0);
-        std::vector<uint32_t> block_pair;
-        uint32_t active = 0;
-        for (size_t i = 0; i < n_pairs; ++i) {
-            IcpPair& P = pairs[i];
-            memset(&P, 0, sizeof P);
-            search_view(c, targets[i], &P.t, &P.f);
-            const Cloud& src = get_cloud(c, sources[i]);
-            LTM_REQUIRE(src.n < 0x80000000ull, "a source must have fewer than 2^31 points");
-            const bool run = src.n && P.t.Mf && max_it >= 1;
-            P.src = src.d;
-            P.o[0] = P.f.ox; P.o[1] = P.f.oy; P.o[2] = P.f.oz;
-            P.first = off[i];
-            P.n = run ? (uint32_t)src.n : 0u;
-            P.block0 = (uint32_t)block_pair.size();
-            P.n_blocks = (P.n + kIcpBlock - 1) / kIcpBlock;
-            off[i + 1] = off[i] + P.n;
-            LTM_REQUIRE(off[i + 1] < 0x80000000ull, "the sources of one batch must have fewer than 2^31 points in all");
-            block_pair.insert(block_pair.end(), P.n_blocks, (uint32_t)i);
-            IcpState& S = st[i];
-            memset(&S, 0, sizeof S);
-            const double* T0 = init16 ? init16 + 16 * i : nullptr;
-            for (int k = 0; k < 12; ++k) {
-                S.T[k] = T0 ? T0[k] : (k % 5 == 0 ? 1.0 : 0.0);
-                LTM_REQUIRE(std::isfinite(S.T[k]), "an initial transform is not finite");
-            }
-            S.prev_mse = S.last_mse = S.fitness = DBL_MAX;
-            S.done = run ? 0 : 1;
-            active += run ? 1u : 0u;
-        }
-        const size_t total = off[n_pairs];
-        const uint32_t n_blocks = (uint32_t)block_pair.size();
-
-        if (active) {
-            DevBuf d_pairs(c, n_pairs * sizeof(IcpPair)), d_st(c, n_pairs * sizeof(IcpState)), d_off(c, (n_pairs + 1) * 8), d_bp(c, (size_t)n_blocks * 4);
-            DevBuf d_sorted(c, total * sizeof(float4)), d_part(c, (size_t)n_blocks * kIcpPartial * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
-            h2d(c, d_pairs.p, pairs.data(), n_pairs * sizeof(IcpPair));
-            h2d(c, d_st.p, st.data(), n_pairs * sizeof(IcpState));
-            h2d(c, d_off.p, off.data(), (n_pairs + 1) * 8);
-            h2d(c, d_bp.p, block_pair.data(), (size_t)n_blocks * 4);
-            h2d(c, d_unf.p, &active, 4);
-            if (trace_n) LTM_HIP(hipMemsetAsync(d_trace.p, 0xff, trace_n * 8, c->stream));      // all ones: a NaN
-            const IcpPair* dp = d_pairs.as<IcpPair>();
-            IcpState* ds = d_st.as<IcpState>();
-            const uint32_t* bp = d_bp.as<uint32_t>();
-            {
-                // each source once into the code order of its target's frame: the lanes of a wavefront then walk the same part of the tree
-                ProfScope ps(c, "icp_prepare", (double)total, 72.0 * (double)total);
-                DevBuf keys(c, total * 8), keys_sorted(c, total * 8), idx(c, total * 4), order(c, total * 4);
-                const size_t tb = icp_sort_temp_bytes(total, n_pairs);
-                DevBuf temp(c, tb);
-                LTM_HIP(icp_source_keys(dp, bp, n_blocks, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
-                LTM_HIP(icp_sort_sources(dp, bp, n_blocks, n_pairs, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), idx.as<uint32_t>(),
-                                         order.as<uint32_t>(), d_sorted.as<float4>(), temp.p, tb, c->stream));
-            }
-            const double max2 = prm.max_corr_dist * prm.max_corr_dist;
-            const int poll = poll_interval();
-            for (int it = 0; it < max_it;) {
-                const int chunk = std::min(poll, max_it - it);
-                {
-                    ProfScope ps(c, "icp_iter", (double)total * chunk, 16.0 * (double)total * chunk, -1.0, false);
-                    if (ps.cls >= 0) c->prof[ps.cls].launches += 2 * (uint64_t)chunk;
-                    for (int k = 0; k < chunk; ++k) {
-                        LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), max2, 0, d_part.as<double>(), c->stream));
-                        LTM_HIP(icp_update(dp, ds, n_pairs, d_part.as<double>(), max_it, prm.transformation_epsilon, prm.euclidean_fitness_epsilon,
-                                           trace_n ? d_trace.as<double>() : nullptr, d_unf.as<uint32_t>(), c->stream));
-                    }
-                }
-                it += chunk;
-                if (it >= max_it) break;
-                uint32_t left = 0;
-                d2h(c, &left, d_unf.p, 4);
-                if (!left) break;
-            }
-            {
-                ProfScope ps(c, "icp_fitness", (double)total, 16.0 * (double)total, -1.0, false);
-                if (ps.cls >= 0) c->prof[ps.cls].launches += 2;
-                LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), 0.0, 1, d_part.as<double>(), c->stream));
-                LTM_HIP(icp_fitness(dp, ds, n_pairs, d_part.as<double>(), c->stream));
-            }
-            d2h(c, st.data(), d_st.p, n_pairs * sizeof(IcpState));
-            if (trace_n) d2h(c, trace, d_trace.p, trace_n * 8);
-        } else if (trace_n) {
-            for (size_t k = 0; k < trace_n; ++k) trace[k] = std::nan("");
-        }
-        for (size_t i = 0; i < n_pairs; ++i) {
-            const IcpState& S = st[i];
-            ltm_icp_result& r = results[i];
-            for (int k = 0; k < 12; ++k) r.T[k] = S.T[k];
-            r.T[12] = r.T[13] = r.T[14] = 0.0; r.T[15] = 1.0;
-            // a pair that never ran has no 1-NN distance at all; one that ran reports the score pass
-            r.fitness = pairs[i].n ? S.fitness : DBL_MAX;
-            r.last_mse = S.last_mse;
-            r.converged = S.converged; r.iterations = S.iterations; r.state = S.state; r.n_corr = S.n_corr;
-        }
+int ltm_icp_align_scanset(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
+                          const ltm_icp_params* params, ltm_icp_result* results, double* trace)
+{
+    return guarded(c, [&] {
+        const ScanSet& ss = get_ss(c, sources);
+        LTM_REQUIRE(!n_pairs || source_kf, "null argument");
+        icp_align_impl(c, n_pairs, targets, [&](size_t i) {
+            LTM_REQUIRE(source_kf[i] < ss.nkf(), "source keyframe out of range");
+            return IcpSource{ss.d + ss.off[source_kf[i]], (size_t)(ss.off[source_kf[i] + 1] - ss.off[source_kf[i]])};
+        }, init16, params, results, trace);
     });
 }
 

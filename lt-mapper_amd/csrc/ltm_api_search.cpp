@@ -2,8 +2,17 @@
 // pcl::KdTreeFLANN members (Session.cpp:18-23, :404, :457, :471, :489, :592, :627).  Kernels in ltm_k_search.hip.
 #include "ltm_internal.h"
 
+// the pool blocks that the indices of one ltm_search_build_scanset share: back in the pool when the last of them is released
+struct SearchBatch {
+    ltm_ctx* c;
+    void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
+    explicit SearchBatch(ltm_ctx* c_) : c(c_) {}
+    ~SearchBatch() { for (void* b : blocks) c->pool.free(b); }
+    SearchBatch(const SearchBatch&) = delete; SearchBatch& operator=(const SearchBatch&) = delete;
+};
 struct ltm_search {
     ltm_ctx* owner = nullptr;
+    std::shared_ptr<SearchBatch> batch;   // set: pts / idx / keys / box point into the batch's blocks
     size_t n_target = 0;
     uint32_t Mf = 0, L = 0, P = 0;      // finite points, leaves, leaves rounded up to a power of two
     SearchFrame f{};
@@ -23,7 +32,7 @@ namespace {
 
 void search_release(ltm_ctx* c, ltm_search* s)
 {
-    c->pool.free(s->pts); c->pool.free(s->idx); c->pool.free(s->keys); c->pool.free(s->box);
+    if (!s->batch) { c->pool.free(s->pts); c->pool.free(s->idx); c->pool.free(s->keys); c->pool.free(s->box); }
     delete s;
 }
 void result_release(ltm_ctx* c, ltm_search_result* r)
@@ -43,6 +52,7 @@ ltm_search_result* get_result(ltm_ctx* c, ltm_search_result* r)
     return r;
 }
 
+SearchFrame frame_of(const float mn[3], const float mx[3]);
 void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
 {
     const size_t n = target.n;
@@ -53,9 +63,7 @@ void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
     float mn[3], mx[3];
     s->Mf = read_box(c, mn, mx, [&](uint32_t* bb) { return search_bbox(target.d, n, bb, c->stream); });
     if (!s->Mf) return;
-    double ext = 0.0;
-    for (int d = 0; d < 3; ++d) ext = std::max(ext, (double)mx[d] - (double)mn[d]);
-    s->f = SearchFrame{(double)mn[0], (double)mn[1], (double)mn[2], ext > 0.0 ? 2097151.0 / ext : 0.0};
+    s->f = frame_of(mn, mx);
     // codes of every point (non-finite: ~0, sorted behind the finite ones) -> the first Mf entries of the sorted arrays are the index
     DevBuf keys(c, n * 8), idx(c, n * 4);
     s->keys = reinterpret_cast<uint64_t*>(c->pool.alloc(n * 8));
@@ -73,6 +81,88 @@ void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
     while (s->P < s->L) s->P <<= 1;
     s->box = reinterpret_cast<float4*>(c->pool.alloc((size_t)4 * s->P * sizeof(float4)));
     LTM_HIP(search_tree_boxes(s->pts, s->Mf, s->L, s->P, s->box, c->stream));
+}
+
+// the frame of an index from the box of its finite points
+SearchFrame frame_of(const float mn[3], const float mx[3])
+{
+    double ext = 0.0;
+    for (int d = 0; d < 3; ++d) ext = std::max(ext, (double)mx[d] - (double)mn[d]);
+    return SearchFrame{(double)mn[0], (double)mn[1], (double)mn[2], ext > 0.0 ? 2097151.0 / ext : 0.0};
+}
+
+// One index per keyframe [kb, ke) of a scan set: the stages of build_index in segmented form, a fixed number of launches and ONE read-back (the boxes and
+// finite counts of all keyframes) for the whole batch.  The indices are views into four blocks the batch shares.
+void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std::vector<std::unique_ptr<ltm_search>>& out)
+{
+    const size_t nk = ke - kb;
+    const uint64_t first = ss.off[kb], total = ss.off[ke] - first;
+    if (total >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, "a batch of search indices must have fewer than 2^31 points in all"};
+    auto batch = std::make_shared<SearchBatch>(c);
+    out.resize(nk);
+    std::vector<SearchSeg> segs(nk);
+    std::vector<uint64_t> off(nk + 1, 0);
+    std::vector<uint32_t> block_seg;
+    for (size_t k = 0; k < nk; ++k) {
+        out[k].reset(new ltm_search);
+        out[k]->owner = c;
+        out[k]->n_target = ss.off[kb + k + 1] - ss.off[kb + k];
+        SearchSeg& S = segs[k];
+        memset(&S, 0, sizeof S);
+        S.src = ss.d + ss.off[kb + k];
+        S.first = ss.off[kb + k] - first;
+        S.n = (uint32_t)out[k]->n_target;
+        S.block0 = (uint32_t)block_seg.size();
+        block_seg.insert(block_seg.end(), (S.n + kSearchSegChunk - 1) / kSearchSegChunk, (uint32_t)k);
+        off[k + 1] = S.first + S.n;
+    }
+    if (!total) return;
+    const uint32_t n_blocks = (uint32_t)block_seg.size();
+    ProfScope p(c, "search_build_batch", (double)total, 48.0 * (double)total);
+    DevBuf d_segs(c, nk * sizeof(SearchSeg)), d_bs(c, (size_t)n_blocks * 4), d_off(c, (nk + 1) * 8), bb(c, nk * 8 * sizeof(uint32_t));
+    h2d(c, d_segs.p, segs.data(), nk * sizeof(SearchSeg));
+    h2d(c, d_bs.p, block_seg.data(), (size_t)n_blocks * 4);
+    h2d(c, d_off.p, off.data(), (nk + 1) * 8);
+    LTM_HIP(search_bbox_seg(d_segs.as<SearchSeg>(), nk, d_bs.as<uint32_t>(), n_blocks, bb.as<uint32_t>(), c->stream));
+    std::vector<uint32_t> enc(nk * 8);
+    d2h(c, enc.data(), bb.p, enc.size() * 4);      // the one read-back: every size below follows from it
+    uint64_t box_total = 0;
+    for (size_t k = 0; k < nk; ++k) {
+        ltm_search* s = out[k].get();
+        SearchSeg& S = segs[k];
+        s->Mf = S.Mf = enc[8 * k + 6];
+        if (!s->Mf) continue;
+        float mn[3], mx[3];
+        decode_box(&enc[8 * k], mn, mx);
+        s->f = S.f = frame_of(mn, mx);
+        s->L = (s->Mf + kSearchLeaf - 1) / kSearchLeaf;
+        s->P = 1;
+        while (s->P < s->L) s->P <<= 1;
+        S.L = s->L; S.P = s->P;
+        S.box0 = box_total;
+        box_total += (uint64_t)4 * s->P;
+    }
+    if (!box_total) return;      // no finite point anywhere: every index is a valid empty one
+    h2d(c, d_segs.p, segs.data(), nk * sizeof(SearchSeg));
+    DevBuf keys(c, total * 8), idx(c, total * 4);
+    uint64_t* keys_sorted = reinterpret_cast<uint64_t*>(batch->blocks[0] = c->pool.alloc(total * 8));
+    uint32_t* order = reinterpret_cast<uint32_t*>(batch->blocks[1] = c->pool.alloc(total * 4));
+    float4* pts = reinterpret_cast<float4*>(batch->blocks[2] = c->pool.alloc(total * sizeof(float4)));
+    float4* box = reinterpret_cast<float4*>(batch->blocks[3] = c->pool.alloc(box_total * sizeof(float4)));
+    LTM_HIP(search_keys_seg(d_segs.as<SearchSeg>(), d_bs.as<uint32_t>(), n_blocks, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
+    {
+        const size_t tb = search_sort_seg_temp_bytes(total, nk);
+        DevBuf temp(c, tb);
+        LTM_HIP(search_sort_gather_seg(d_segs.as<SearchSeg>(), d_bs.as<uint32_t>(), n_blocks, nk, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted,
+                                       idx.as<uint32_t>(), order, pts, temp.p, tb, c->stream));
+    }
+    LTM_HIP(search_tree_boxes_seg(d_segs.as<SearchSeg>(), nk, pts, box, c->stream));
+    for (size_t k = 0; k < nk; ++k) {
+        ltm_search* s = out[k].get();
+        if (!s->Mf) continue;
+        s->batch = batch;
+        s->pts = pts + segs[k].first; s->idx = order + segs[k].first; s->keys = keys_sorted + segs[k].first; s->box = box + segs[k].box0;
+    }
 }
 
 // the queries in code order under the index's frame
@@ -121,6 +211,24 @@ int ltm_search_build(ltm_ctx* c, ltm_cloud htarget, ltm_search** out)
         }
         c->search_open.push_back(s.get());
         *out = s.release();
+    });
+}
+
+int ltm_search_build_scanset(ltm_ctx* c, ltm_scanset hss, size_t kf_begin, size_t kf_end, ltm_search** out)
+{
+    return guarded(c, [&] {
+        const ScanSet& ss = get_ss(c, hss);
+        LTM_REQUIRE(kf_begin <= kf_end && kf_end <= ss.nkf(), "keyframe range outside the scan set");
+        if (kf_begin == kf_end) return;
+        LTM_REQUIRE(out, "null argument");
+        std::vector<std::unique_ptr<ltm_search>> made;
+        // an error leaves nothing behind: the handles die with `made`, the shared blocks with the last reference to the batch, scratch with its DevBufs
+        build_index_batch(c, ss, kf_begin, kf_end, made);
+        c->search_open.reserve(c->search_open.size() + made.size());
+        for (size_t k = 0; k < made.size(); ++k) {
+            c->search_open.push_back(made[k].get());
+            out[k] = made[k].release();
+        }
     });
 }
 

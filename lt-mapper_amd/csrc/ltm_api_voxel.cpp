@@ -563,7 +563,8 @@ void vgs_release(ltm_ctx* c, ltm_vgs* v)
     if (v->hi) { pinned_free(c, v->hi); v->hi = nullptr; }
     delete v;
 }
-void vgs_begin(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_vgs** ticket)
+// order: 1 = PCL's std::sort order (host threads), 0 = input order (device only), < 0 = as LTM_VOXELGRID_ORDER says (the public entry points)
+void vgs_begin(ltm_ctx* c, ltm_scanset hin, float leaf, int order, ltm_vgs** ticket)
 {
     LTM_REQUIRE(ticket, "null argument");
     LTM_REQUIRE(leaf > 0.0f, "leaf size must be positive");
@@ -623,8 +624,8 @@ void vgs_begin(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_vgs** ticket)
     // default makes the SAME std::sort call on the host, one keyframe per task (the permutation is a function of the key sequence
     // alone): keys down (8 B / point), point order up (4 B / point), everything else stays on the device.  LTM_VOXELGRID_ORDER=input
     // keeps the whole grid on the device with a stable radix sort (input order inside a voxel; faster, not bit-identical to PCL).
-    const char* order_env = std::getenv("LTM_VOXELGRID_ORDER");
-    v->pcl_order = !(order_env && std::strcmp(order_env, "input") == 0);
+    const char* order_env = order < 0 ? std::getenv("LTM_VOXELGRID_ORDER") : nullptr;
+    v->pcl_order = order < 0 ? !(order_env && std::strcmp(order_env, "input") == 0) : order != 0;
     if (v->pcl_order) {
         // The pinned buffer receives the 64-bit keys (keyframe id << 32 | leaf index) and is read as the (leaf index, point index) pairs PCL
         // sorts: on this little-endian host a key's low word IS the pair's first member, and the high word -- the keyframe id, which the
@@ -729,7 +730,7 @@ void vgs_end(ltm_ctx* c, ltm_vgs* v, ltm_scanset* out)
 int ltm_voxel_grid_scanset_begin(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_vgs** ticket)
 {
     if (ticket) *ticket = nullptr;
-    return guarded(c, [&] { vgs_begin(c, hin, leaf, ticket); });
+    return guarded(c, [&] { vgs_begin(c, hin, leaf, -1, ticket); });
 }
 
 int ltm_voxel_grid_scanset_end(ltm_ctx* c, ltm_vgs* ticket, ltm_scanset* out)
@@ -777,6 +778,15 @@ int ltm_debug_voxel_stats(ltm_ctx* c, uint64_t* grids, uint64_t* identity_hits, 
 }
 
 } // extern "C"
+
+// begin + end with the order given by the caller (ltm_submaps_assemble); returns the code of the half that failed, the message in c->err
+int ltm_detail::voxel_grid_scanset_ordered(ltm_ctx* c, ltm_scanset hin, float leaf, int order, ltm_scanset* out)
+{
+    ltm_vgs* t = nullptr;
+    const int rc = guarded(c, [&] { vgs_begin(c, hin, leaf, order, &t); });
+    if (rc != LTM_OK) return rc;
+    return ltm_voxel_grid_scanset_end(c, t, out);
+}
 
 void ltm_detail::vgs_release_all(ltm_ctx* c)      // ltm_destroy: tickets nobody ended (an exception between _begin and _end on the host side)
 {

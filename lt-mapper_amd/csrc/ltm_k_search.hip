@@ -100,6 +100,149 @@ hipError_t search_tree_boxes(const float4* sorted_pts, uint32_t Mf, uint32_t L, 
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------- batched build
+// One index per keyframe of a scan set (ltm_search_build_scanset), the stages of the build above in segmented form: the grid of the first three kernels is
+// over chunks of kSearchSegChunk points, a per-block table names the segment (as ltm_k_icp.hip does for its pairs), so a workgroup never straddles two
+// keyframes and its segment record is uniform.
+static constexpr int kSegPerThread = kSearchSegChunk / kBlock;
+__global__ void __launch_bounds__(kBlock)
+k_search_bbox_seg_init(uint32_t* __restrict__ b, size_t n_words)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_words) b[i] = (i & 7u) < 3u ? 0xffffffffu : 0u;
+}
+__global__ void __launch_bounds__(kBlock)
+k_search_bbox_seg(const SearchSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, uint32_t* __restrict__ out)
+{
+    __shared__ uint32_t scnt[kBlock / 64];
+    const uint32_t si = block_seg[blockIdx.x];
+    const SearchSeg& S = segs[si];
+    const uint32_t base = (blockIdx.x - S.block0) * kSearchSegChunk;
+    BoxAcc box;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int it = 0; it < kSegPerThread; ++it) {
+        const uint32_t local = base + it * kBlock + threadIdx.x;
+        if (local >= S.n) continue;
+        const float4 p = S.src[local];
+        if (!finite3(p.x, p.y, p.z)) continue;
+        box.add(p);
+        ++cnt;
+    }
+    box.wave_reduce();
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, off, 64);
+    if ((threadIdx.x & 63u) == 0) scnt[threadIdx.x >> 6] = cnt;
+    box.commit<kBlock / 64>(out + 8 * (size_t)si, true);      // (its barrier orders scnt as well) one set of atomics per workgroup, for its one segment
+    if (threadIdx.x == 0) {
+        uint32_t c = 0;
+        for (int w = 0; w < kBlock / 64; ++w) c += scnt[w];
+        if (c) atomicAdd(&out[8 * (size_t)si + 6], c);
+    }
+}
+hipError_t search_bbox_seg(const SearchSeg* segs, size_t n_segs, const uint32_t* block_seg, uint32_t n_blocks, uint32_t* bbox8, hipStream_t s)
+{
+    if (!n_segs) return hipSuccess;
+    k_search_bbox_seg_init<<<dim3(grid_for(n_segs * 8)), dim3(kBlock), 0, s>>>(bbox8, n_segs * 8);
+    if (n_blocks) k_search_bbox_seg<<<dim3(n_blocks), dim3(kBlock), 0, s>>>(segs, block_seg, bbox8);
+    return hipGetLastError();
+}
+__global__ void __launch_bounds__(kBlock)
+k_search_keys_seg(const SearchSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
+{
+    const SearchSeg& S = segs[block_seg[blockIdx.x]];
+    const uint32_t base = (blockIdx.x - S.block0) * kSearchSegChunk;
+#pragma unroll
+    for (int it = 0; it < kSegPerThread; ++it) {
+        const uint32_t local = base + it * kBlock + threadIdx.x;
+        if (local >= S.n) continue;
+        const float4 p = S.src[local];
+        keys[S.first + local] = search_key(S.f, p.x, p.y, p.z);
+        idx[S.first + local] = local;
+    }
+}
+hipError_t search_keys_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s)
+{
+    if (!n_blocks) return hipSuccess;
+    k_search_keys_seg<<<dim3(n_blocks), dim3(kBlock), 0, s>>>(segs, block_seg, keys, idx);
+    return hipGetLastError();
+}
+// sorted[first + j] = src[order[first + j]] for the Mf finite points of every segment (they sort in front: a non-finite point's code is ~0)
+__global__ void __launch_bounds__(kBlock)
+k_search_gather_seg(const SearchSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, const uint32_t* __restrict__ order, float4* __restrict__ sorted)
+{
+    const SearchSeg& S = segs[block_seg[blockIdx.x]];
+    const uint32_t base = (blockIdx.x - S.block0) * kSearchSegChunk;
+#pragma unroll
+    for (int it = 0; it < kSegPerThread; ++it) {
+        const uint32_t local = base + it * kBlock + threadIdx.x;
+        if (local >= S.Mf) continue;
+        const uint32_t j = order[S.first + local];
+        if (j < S.n) sorted[S.first + local] = S.src[j];
+    }
+}
+size_t search_sort_seg_temp_bytes(size_t total, size_t n_segs)
+{
+    size_t b = 0;
+    (void)rocprim::segmented_radix_sort_pairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                              (unsigned)total, (unsigned)n_segs, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, 64);
+    return std::max<size_t>(b, 16);
+}
+hipError_t search_sort_gather_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, size_t n_segs, const uint64_t* offsets, size_t total,
+                                  const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp,
+                                  size_t temp_bytes, hipStream_t s)
+{
+    if (!n_blocks || !total) return hipSuccess;
+    // the full 63-bit code leaves no room for a segment prefix in a 64-bit key: a segmented sort (not necessarily stable -- equal codes may change places,
+    // which no query result depends on)
+    hipError_t e = rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, idx, order, (unsigned)total, (unsigned)n_segs, offsets, offsets + 1,
+                                                       0, 64, s);
+    if (e != hipSuccess) return e;
+    k_search_gather_seg<<<dim3(n_blocks), dim3(kBlock), 0, s>>>(segs, block_seg, order, sorted);
+    return hipGetLastError();
+}
+// all box trees in one launch, one workgroup per segment: the leaf boxes, then the inner levels bottom-up with a barrier between two levels (a level reads
+// what the same workgroup wrote one level below).  The same min / max over the same leaves as k_search_leaf_boxes / k_search_inner_boxes.
+static constexpr int kTreeBlock = 1024;
+__global__ void __launch_bounds__(kTreeBlock)
+k_search_tree_boxes_seg(const SearchSeg* __restrict__ segs, const float4* __restrict__ sorted, float4* __restrict__ box_all)
+{
+    const SearchSeg& S = segs[blockIdx.x];
+    const uint32_t Mf = S.Mf, L = S.L, P = S.P;
+    if (!P) return;
+    const float4* __restrict__ pts = sorted + S.first;
+    float4* box = box_all + S.box0;
+    const float inf = __builtin_inff();
+    for (uint32_t l = threadIdx.x; l < P; l += kTreeBlock) {
+        float4 lo = make_float4(inf, inf, inf, 0.0f), hi = make_float4(-inf, -inf, -inf, 0.0f);
+        if (l < L) {
+            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, Mf);
+            for (uint32_t j = a; j < b; ++j) {
+                const float4 p = pts[j];
+                lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
+                hi.x = fmaxf(hi.x, p.x); hi.y = fmaxf(hi.y, p.y); hi.z = fmaxf(hi.z, p.z);
+            }
+        }
+        box[2 * (P + l)] = lo;
+        box[2 * (P + l) + 1] = hi;
+    }
+    for (uint32_t lvl = P >> 1; lvl >= 1; lvl >>= 1) {
+        __threadfence_block();
+        __syncthreads();
+        for (uint32_t v = lvl + threadIdx.x; v < 2 * lvl; v += kTreeBlock) {
+            const float4 l0 = box[4 * v], h0 = box[4 * v + 1], l1 = box[4 * v + 2], h1 = box[4 * v + 3];
+            box[2 * v] = make_float4(fminf(l0.x, l1.x), fminf(l0.y, l1.y), fminf(l0.z, l1.z), 0.0f);
+            box[2 * v + 1] = make_float4(fmaxf(h0.x, h1.x), fmaxf(h0.y, h1.y), fmaxf(h0.z, h1.z), 0.0f);
+        }
+    }
+}
+hipError_t search_tree_boxes_seg(const SearchSeg* segs, size_t n_segs, const float4* sorted, float4* box, hipStream_t s)
+{
+    if (!n_segs) return hipSuccess;
+    k_search_tree_boxes_seg<<<dim3((unsigned)n_segs), dim3(kTreeBlock), 0, s>>>(segs, sorted, box);
+    return hipGetLastError();
+}
+
 // --------------------------------------------------------------------------------------------------- query order
 // queries sorted by their code under the index's frame: the lanes of a wavefront then walk the same part of the tree (temp: sort_temp_bytes(n))
 hipError_t search_query_order(const float4* query, size_t n, SearchFrame f, uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order,

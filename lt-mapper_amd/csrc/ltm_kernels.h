@@ -245,6 +245,29 @@ size_t     radius_sort_temp_bytes(size_t total, size_t n);
 hipError_t radius_fill(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, const uint64_t* full_off, uint64_t total_full,
                        const uint64_t* out_off, uint64_t* pairs, uint64_t* pairs_sorted, int32_t* out_idx, float* out_d2, void* temp, size_t temp_bytes, hipStream_t s);
 
+// batched build (ltm_search_build_scanset): one segment per keyframe.  src: the keyframe's points, n of them; its slice [first, first + n) of the batch's
+// keys / order / sorted points; its workgroups [block0, block0 + ceil(n / kSearchSegChunk)) of the segmented kernels; f, Mf, L, P and box0 (first float4 of
+// its tree in the batch's box array) are filled in by the host once the boxes are known
+static constexpr int kSearchSegChunk = 1024;    // points per workgroup of the segmented build kernels
+struct SearchSeg { SearchFrame f; const float4* src; uint64_t first, box0; uint32_t n, Mf, L, P, block0, pad; };
+// bbox8: 8 words per segment (initialised here): box of its finite points as ordered keys, word 6 their number; one commit per workgroup and segment
+hipError_t search_bbox_seg(const SearchSeg* segs, size_t n_segs, const uint32_t* block_seg, uint32_t n_blocks, uint32_t* bbox8, hipStream_t s);
+// keys[first + j] = code of point j under its segment's frame (non-finite: ~0), idx[first + j] = j
+hipError_t search_keys_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s);
+size_t     search_sort_seg_temp_bytes(size_t total, size_t n_segs);
+// every segment sorted by code (offsets: n_segs + 1 slice bounds), then sorted[first + j] = src[order[first + j]] for j < Mf
+hipError_t search_sort_gather_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, size_t n_segs, const uint64_t* offsets, size_t total,
+                                  const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp,
+                                  size_t temp_bytes, hipStream_t s);
+// the box trees of all segments in one launch (one workgroup per segment): box + box0 of a segment is what search_tree_boxes gives for its points
+hipError_t search_tree_boxes_seg(const SearchSeg* segs, size_t n_segs, const float4* sorted, float4* box, hipStream_t s);
+
+// ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
+// one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; workgroups [block0, block0 + ceil(n / 256))
+struct SubmapPiece { uint64_t src, dst; uint32_t n, block0, affine, pad; };
+hipError_t submap_gather(const float4* scans, const SubmapPiece* pieces, const uint32_t* block_piece, uint32_t n_blocks, const float* affines12, float4* out,
+                         hipStream_t s);
+
 // ---- batched point-to-point ICP over search indices (ltm_k_icp.hip; LTslam.cpp:187-301) ----
 static constexpr int kIcpBlock = 256;           // source points per workgroup of the correspondence kernel = per partial record
 static constexpr int kIcpPartial = 17;          // doubles per partial record: count, sum p (3), sum q (3), sum p q^T (9, row-major), sum d2

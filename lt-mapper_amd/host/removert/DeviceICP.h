@@ -5,7 +5,7 @@
 // original source).  setInputTarget builds a search index on the device, which align and alignAll reuse until the next setInputTarget: addSCloops'
 // loop over many sources against one submap becomes ONE alignAll.  The swap for the member of LTslam is shown in INTEGRATION.md.
 // Every member reports a failure by throwing (std::runtime_error with the context's message, std::logic_error for a call out of order).
-// Not here: assembling the submaps (loopFindNearKeyframesCloud) and the Euler / gtsam::Pose3 conversions of the result stay on the host as they are.
+// Not here: the Euler / gtsam::Pose3 conversions of the result stay on the host as they are (the submaps: DeviceLoopSubmaps.h).
 #pragma once
 #include <initializer_list>
 #include <stdexcept>
