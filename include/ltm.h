@@ -259,7 +259,15 @@ int ltm_reproject(ltm_ctx*, ltm_cloud map, ltm_poses poses, size_t kf_begin, siz
 
 /* extractLowDynPointsViaKnnDiff / extractHighDynPointsViaKnnDiff (Session.cpp:393-427, 487-504, 537-642):
  * exact k-NN of every scan point (moved to the global frame) in `target`; coexist iff mean of the k squared
- * distances < thr.  Outputs are in the local frame, input order kept.  Either output may be NULL. */
+ * distances < thr.  Outputs are in the local frame, input order kept.  Either output may be NULL.
+ * Domain (also of ltm_knn_split_cloud): 1 <= k <= 16 and thr > 0 (a NaN thr included), else LTM_E_INVALID.  k is clamped to the target
+ * size for the search and stays the divisor of the mean, as pcl::KdTreeFLANN::nearestKSearch + Session.cpp:590-599 give; an empty target
+ * makes every query "diff" / "far".  A query whose global-frame point has a non-finite coordinate (NaN, +-inf, or a finite value
+ * whose squared distance overflows) is "diff" / "far" and keeps its input position.  A target of more than 64 points whose bounding
+ * box is not finite (a +-inf coordinate, or a NaN that reaches the box) is LTM_E_INVALID; a NaN the box does not show is undefined, as
+ * in the reference.  Targets of up to 64 points are searched by brute force, no box is taken and none is checked: a target point with
+ * a +-inf coordinate is a point at infinite distance (it only counts where k exceeds the finite points, and then makes the query
+ * "diff" / "far"), a NaN target coordinate is undefined there too. */
 int ltm_knn_partition(ltm_ctx*, ltm_cloud target, ltm_scanset scans, ltm_poses poses, size_t kf_begin, size_t kf_end,
                       int k, float thr, ltm_scanset* coexist, ltm_scanset* diff);
 /* removeWeakNDMapPointsHavingStrongNDInNear (Session.cpp:452-484): split `query` by k-NN distance to `target` */
@@ -549,6 +557,11 @@ int ltm_debug_occlusion_stats(ltm_ctx*, uint64_t* pairs, uint64_t* first_shell, 
  * input an order-preserving subset of an earlier grid's output, still in octree order and one point per voxel under the frame this
  * call derives: output = copy of the input, bit for bit what the sort + centroid path gives) */
 int ltm_debug_voxel_stats(ltm_ctx*, uint64_t* grids, uint64_t* identity_hits, int reset);
+/* ltm_knn_partition's two-phase query (k <= 4, more than 64 target points, LTM_KNN_FAST != 0) since the last reset: scan queries it served,
+ * queries its bucket test (phase 1) left undecided for the exact search, calls that took the two-phase path, and calls among them whose
+ * cell id + query index did not fit 64 bits so that phase 2 walked its queue in scan order.  All four are counted only in a context created
+ * with LTM_KNN_STATS=1 (lanes inherit the switch) and stay 0 otherwise; any pointer may be NULL. */
+int ltm_debug_knn_stats(ltm_ctx*, uint64_t* queries, uint64_t* undecided, uint64_t* two_phase_calls, uint64_t* unsorted_queue_calls, int reset);
 /* diagnostic counters of the range-culled vote kernel since the last reset: points tested / points that needed the exact path */
 int ltm_debug_cull_stats(ltm_ctx*, uint64_t* survivors, uint64_t* points, int reset);
 /* blocks of the context's device pool that are handed out (live) and the bytes they hold: what a caller's handles and open tickets own */

@@ -163,6 +163,7 @@ SIGNATURES = {
     "ltm_debug_cull_validation": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_occlusion_stats": (_i, [_vp, _pu64, _pu64, _pu64, _i]),
     "ltm_debug_voxel_stats": (_i, [_vp, _pu64, _pu64, _i]),
+    "ltm_debug_knn_stats": (_i, [_vp, _pu64, _pu64, _pu64, _pu64, _i]),
     "ltm_rimg_size": (None, [_f, _f, _f, C.POINTER(_i), C.POINTER(_i)]),
     "ltm_profile_enable": (_i, [_vp, _i]),
     "ltm_profile_reset": (_i, [_vp]),
@@ -703,6 +704,13 @@ class Context:
         a, b = _u64(), _u64()
         self._ck(self.lib.ltm_debug_voxel_stats(self.h, C.byref(a), C.byref(b), 1 if reset else 0))
         return int(a.value), int(b.value)
+
+    def knn_stats(self, reset=False):
+        """(scan queries of two-phase ltm_knn_partition calls, queries phase 1 left undecided, two-phase calls, calls whose phase-2 queue stayed in
+        scan order); counted only in a context created with LTM_KNN_STATS=1"""
+        q, u, t, s = _u64(), _u64(), _u64(), _u64()
+        self._ck(self.lib.ltm_debug_knn_stats(self.h, C.byref(q), C.byref(u), C.byref(t), C.byref(s), 1 if reset else 0))
+        return int(q.value), int(u.value), int(t.value), int(s.value)
 
     def cull_validation(self):
         """(image shapes whose bounded-error projection was validated on first use, shapes that failed and fell back to the exact kernels)"""

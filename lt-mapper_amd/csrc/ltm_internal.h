@@ -308,6 +308,7 @@ struct ltm_ctx {
     int knn_two_phase = 1;                      // LTM_KNN_FAST=0: the one-kernel exact search for every query (A/B switch)
     int knn_stats_on = 0;                       // LTM_KNN_STATS=1: count the queries phase 1 leaves undecided (one host round trip per call)
     uint64_t knn_undecided = 0, knn_queries = 0;
+    uint64_t knn_two_phase_calls = 0, knn_unsorted_calls = 0;      // ltm_knn_partition calls that ran the two-phase query / its scan-order phase-2 queue (same switch)
     // The culled kernels rest on error bounds of the bounded-error projection that were validated empirically (tools/eps_sweep.py, ltm_debug_cull_check in the
     // tests) for the fields of view and extrinsics that were fuzzed.  Every image shape is therefore checked ON THE DEVICE the first time a context uses
     // it (cull_geometry_ok: 2^20 probe points on and beside the pixel boundaries, local frame and through one real keyframe pose); a shape that fails falls
