@@ -562,6 +562,11 @@ int ltm_debug_voxel_stats(ltm_ctx*, uint64_t* grids, uint64_t* identity_hits, in
  * cell id + query index did not fit 64 bits so that phase 2 walked its queue in scan order.  All four are counted only in a context created
  * with LTM_KNN_STATS=1 (lanes inherit the switch) and stay 0 otherwise; any pointer may be NULL. */
 int ltm_debug_knn_stats(ltm_ctx*, uint64_t* queries, uint64_t* undecided, uint64_t* two_phase_calls, uint64_t* unsorted_queue_calls, int reset);
+/* which kernel forms a Scan Context shape gets (host arithmetic only, needs no device; the launch wrappers' own expressions): *scatter_in_lds = 1 if
+ * ltm_sc_from_scanset pre-reduces a block's points in LDS (up to 4096 bins), 0 if it goes straight to device memory; *pair_in_lds = 1 if the pair
+ * distance of ltm_sc_distance / ltm_sc_detect stages both descriptors in LDS (up to 60 KB with the keys and norms), 0 if it reads them from device
+ * memory.  Either pointer may be NULL.  LTM_E_INVALID outside 1 <= num_ring <= 64, 1 <= num_sector <= 256. */
+int ltm_debug_sc_paths(int num_ring, int num_sector, int* scatter_in_lds, int* pair_in_lds);
 /* diagnostic counters of the range-culled vote kernel since the last reset: points tested / points that needed the exact path */
 int ltm_debug_cull_stats(ltm_ctx*, uint64_t* survivors, uint64_t* points, int reset);
 /* blocks of the context's device pool that are handed out (live) and the bytes they hold: what a caller's handles and open tickets own */

@@ -164,6 +164,7 @@ SIGNATURES = {
     "ltm_debug_occlusion_stats": (_i, [_vp, _pu64, _pu64, _pu64, _i]),
     "ltm_debug_voxel_stats": (_i, [_vp, _pu64, _pu64, _i]),
     "ltm_debug_knn_stats": (_i, [_vp, _pu64, _pu64, _pu64, _pu64, _i]),
+    "ltm_debug_sc_paths": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "ltm_rimg_size": (None, [_f, _f, _f, C.POINTER(_i), C.POINTER(_i)]),
     "ltm_profile_enable": (_i, [_vp, _i]),
     "ltm_profile_reset": (_i, [_vp]),
@@ -873,6 +874,15 @@ def sc_params(**over):
             raise TypeError(f"ltm_sc_params has no field {k!r}")
         setattr(p, k, v)
     return p
+
+
+def sc_paths(num_ring, num_sector):
+    """ltm_debug_sc_paths: (the descriptor scatter pre-reduces in LDS, the pair distance stages both descriptors in LDS) for this shape; host only"""
+    a, b = _i(), _i()
+    rc = load_library().ltm_debug_sc_paths(num_ring, num_sector, C.byref(a), C.byref(b))
+    if rc != 0:
+        raise LtmError(rc, "ltm_debug_sc_paths")
+    return bool(a.value), bool(b.value)
 
 
 class ScanContexts:

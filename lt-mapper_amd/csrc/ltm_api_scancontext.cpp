@@ -240,6 +240,16 @@ int ltm_sc_detect(ltm_ctx* c, ltm_sc* hdb, ltm_sc* hq, const ltm_sc_params* para
     });
 }
 
+int ltm_debug_sc_paths(int num_ring, int num_sector, int* scatter_in_lds, int* pair_in_lds)
+{
+    if (num_ring < 1 || num_ring > kMaxRing || num_sector < 1 || num_sector > kMaxSector) return LTM_E_INVALID;
+    bool scatter = false, pair = false;
+    sc_paths(num_ring, num_sector, &scatter, &pair);
+    if (scatter_in_lds) *scatter_in_lds = scatter ? 1 : 0;
+    if (pair_in_lds) *pair_in_lds = pair ? 1 : 0;
+    return LTM_OK;
+}
+
 int ltm_sc_free(ltm_ctx* c, ltm_sc* s)
 {
     return guarded(c, [&] {

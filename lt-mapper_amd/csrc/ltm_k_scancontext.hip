@@ -138,9 +138,16 @@ k_sc_ring_distances(const float* __restrict__ qk, size_t nq, const float* __rest
     rd[t] = result;
 }
 
-__device__ __forceinline__ float sc_nan_last(float d) { return (d != d) ? __builtin_inff() : d; }
+// The candidates' order: (key distance is NaN, key distance, index) ascending -- a NaN sorts after everything, +inf included, and NaNs among
+// themselves by index.  True if candidate (d, j) comes before (pd, pj).
+__device__ __forceinline__ bool sc_key_before(float d, int j, float pd, int pj)
+{
+    const bool n = d != d, pn = pd != pd;
+    if (n != pn) return pn;
+    return (!n && d < pd) || ((n || d == pd) && j < pj);
+}
 
-// The K nearest ring keys of every query in ascending (distance, index) order: one wave per query, K selection rounds over its row of rd.
+// The K nearest ring keys of every query in sc_key_before order (ascending (distance, index), NaN distances last): one wave per query, K selection rounds over its row of rd.
 // pairs[(q * K + k) * 2] = {q, index}.  K <= nd.
 __global__ void __launch_bounds__(64)
 k_sc_candidates(const float* __restrict__ rd, size_t nd, int K, int32_t* __restrict__ pairs)
@@ -150,18 +157,17 @@ k_sc_candidates(const float* __restrict__ rd, size_t nd, int K, int32_t* __restr
     float pd = -1.0f;
     int pj = -1;
     for (int k = 0; k < K; ++k) {
-        float bd = __builtin_inff();
+        float bd = __builtin_nanf("");      // (NaN, INT_MAX): after every entry
         int bj = INT_MAX;
         for (size_t j = threadIdx.x; j < nd; j += 64) {
-            const float d = sc_nan_last(row[j]);
-            const bool after = d > pd || (d == pd && (int)j > pj);
-            if (after && (d < bd || (d == bd && (int)j < bj))) { bd = d; bj = (int)j; }
+            const float d = row[j];
+            if (sc_key_before(pd, pj, d, (int)j) && sc_key_before(d, (int)j, bd, bj)) { bd = d; bj = (int)j; }
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             const float od = __shfl_xor(bd, off, 64);
             const int oj = __shfl_xor(bj, off, 64);
-            if (od < bd || (od == bd && oj < bj)) { bd = od; bj = oj; }
+            if (sc_key_before(od, oj, bd, bj)) { bd = od; bj = oj; }
         }
         pd = bd; pj = bj;
         if (threadIdx.x == 0) {
@@ -263,8 +269,8 @@ k_sc_pair(const double* __restrict__ descA, const double* __restrict__ skA, cons
     }
 }
 
-// detectLoopClosureIDBetweenSession :296-311 for one query per wave: the candidate with the smallest distance, the first one in ascending (ring-key
-// distance, index) order among equals.  A candidate whose distance is NaN or not below 10000000 never wins (nn_idx 0, shift 0 if none does).
+// detectLoopClosureIDBetweenSession :296-311 for one query per wave: the candidate with the smallest distance, the first one in sc_key_before order (ring-key
+// distance, index; NaN last) among equals.  A candidate whose distance is NaN or not below 10000000 never wins (nn_idx 0, shift 0 if none does).
 __global__ void __launch_bounds__(64)
 k_sc_detect_reduce(const double* __restrict__ dist, const int32_t* __restrict__ shift, const int32_t* __restrict__ pairs, const float* __restrict__ rd,
                    size_t nd, size_t K, int32_t* __restrict__ nn_idx, double* __restrict__ min_dist, int32_t* __restrict__ nn_align)
@@ -278,15 +284,15 @@ k_sc_detect_reduce(const double* __restrict__ dist, const int32_t* __restrict__ 
         const double d = dist[p];
         if (!(d < 10000000.0)) continue;
         const int j = pairs ? pairs[2 * p + 1] : (int)k;
-        const float r = sc_nan_last(rd[q * nd + (size_t)j]);
-        if (bj < 0 || d < bd || (d == bd && (r < br || (r == br && j < bj)))) { bd = d; br = r; bj = j; bs = shift[p]; }
+        const float r = rd[q * nd + (size_t)j];
+        if (bj < 0 || d < bd || (d == bd && sc_key_before(r, j, br, bj))) { bd = d; br = r; bj = j; bs = shift[p]; }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const double od = __shfl_xor(bd, off, 64);
         const float orr = __shfl_xor(br, off, 64);
         const int oj = __shfl_xor(bj, off, 64), os = __shfl_xor(bs, off, 64);
-        if (oj >= 0 && (bj < 0 || od < bd || (od == bd && (orr < br || (orr == br && oj < bj))))) { bd = od; br = orr; bj = oj; bs = os; }
+        if (oj >= 0 && (bj < 0 || od < bd || (od == bd && sc_key_before(orr, oj, br, bj)))) { bd = od; br = orr; bj = oj; bs = os; }
     }
     if (threadIdx.x == 0) {
         nn_idx[q] = bj < 0 ? 0 : bj;
@@ -302,7 +308,15 @@ size_t sc_pair_lds_bytes(int R, int S, bool* fits)
     return *fits ? full : small;
 }
 
+bool sc_scatter_in_lds(int R, int S) { return R * S <= kScLdsBins; }
+
 } // namespace
+
+void sc_paths(int R, int S, bool* scatter_in_lds, bool* pair_in_lds)
+{
+    *scatter_in_lds = sc_scatter_in_lds(R, S);
+    sc_pair_lds_bytes(R, S, pair_in_lds);
+}
 
 hipError_t sc_scatter(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t max_kf_pts, ScGeom g, uint32_t* bins, hipStream_t s)
 {
@@ -311,7 +325,7 @@ hipError_t sc_scatter(const float4* scans, const uint64_t* offsets_dev, size_t k
     for (size_t k0 = 0; k0 < nb; k0 += 65535) {       // gridDim.y limit
         const size_t nk = std::min<size_t>(65535, nb - k0);
         uint32_t* out = bins + k0 * (size_t)g.R * (size_t)g.S;
-        if (g.R * g.S <= kScLdsBins) k_sc_scatter<true><<<dim3(gx, (unsigned)nk), dim3(kBlock), (size_t)g.R * g.S * sizeof(uint32_t), s>>>(scans, offsets_dev, kb + k0, g, out);
+        if (sc_scatter_in_lds(g.R, g.S)) k_sc_scatter<true><<<dim3(gx, (unsigned)nk), dim3(kBlock), (size_t)g.R * g.S * sizeof(uint32_t), s>>>(scans, offsets_dev, kb + k0, g, out);
         else k_sc_scatter<false><<<dim3(gx, (unsigned)nk), dim3(kBlock), 0, s>>>(scans, offsets_dev, kb + k0, g, out);
     }
     return hipGetLastError();

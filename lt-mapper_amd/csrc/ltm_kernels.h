@@ -294,6 +294,8 @@ hipError_t icp_fitness(const IcpPair* pairs, IcpState* st, size_t n_pairs, const
 
 // ---- scan context (ltm_k_scancontext.hip; Scancontext.cpp:69-324) ----
 struct ScGeom { double lidar_height, max_radius; int R, S; };      // rings x sectors
+// which kernel forms a shape gets (host arithmetic, the launch wrappers' own decisions): sc_scatter pre-reduces in LDS, sc_pair_distance stages both descriptors in LDS
+void sc_paths(int R, int S, bool* scatter_in_lds, bool* pair_in_lds);
 // makeScancontext for keyframes [kb, kb + nb): bins (zeroed by the caller, R * S uint32 per keyframe) receive the order-preserving key of the largest
 // height of every bin; sc_finish turns them into the descriptor
 hipError_t sc_scatter(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t max_kf_pts, ScGeom g, uint32_t* bins, hipStream_t s);

@@ -12,34 +12,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from sc_cases import away_from, place, polar_points, rotated, session_scans      # the generators, shared with the case builder
 from tools import sc_numpy as ref
 
 pytestmark = pytest.mark.gpu
 
 KF_SIZES = (0, 1, 63, 64, 65, 5000)
-
-
-def polar_points(rng, n, p, exclude=()):
-    """n points in the interior of random bins (never one of `exclude`, 0-based (ring, sector)); z so that z + 2 covers negatives, zero and ordinary heights"""
-    R, S = p["num_ring"], p["num_sector"]
-    ri, si = rng.integers(0, R, n), rng.integers(0, S, n)
-    return place(rng, *away_from(ri, si, S, exclude), p, rng.uniform(-2.9, 9.0, n))
-
-
-def away_from(ri, si, S, exclude):
-    """bin indices moved one sector on where they hit a bin of `exclude` (distinct rings there, so the move never lands in another one)"""
-    for (er, es) in exclude:
-        hit = (ri == er) & (si == es)
-        si[hit] = (si[hit] + 1) % S if S > 1 else si[hit]
-    return ri, si
-
-
-def place(rng, ri, si, p, z):
-    R, S = p["num_ring"], p["num_sector"]
-    n = len(ri)
-    r = (ri + rng.uniform(0.1, 0.9, n)) * (p["max_radius"] / R)
-    th = np.deg2rad((si + rng.uniform(0.1, 0.9, n)) * (360.0 / S))
-    return np.stack([r * np.cos(th), r * np.sin(th), np.asarray(z, np.float64), np.zeros(n)], axis=1).astype(np.float32)
 
 
 def edge_case_scans(seed, p):
@@ -75,17 +53,6 @@ def edge_case_scans(seed, p):
     kfs.append(np.array([[0, 0, 7, 0]], np.float32))
     off = np.concatenate([[0], np.cumsum([len(k) for k in kfs])]).astype(np.uint64)
     return np.concatenate(kfs), off
-
-
-def session_scans(seed, n_kf, pts_per_kf, p):
-    rng = np.random.default_rng(seed)
-    scans = np.concatenate([polar_points(rng, pts_per_kf, p) for _ in range(n_kf)])
-    return scans, (np.arange(n_kf + 1) * pts_per_kf).astype(np.uint64)
-
-
-def rotated(rng, desc, rot, noise=1e-3):
-    out = np.roll(desc, rot, axis=1)
-    return out + np.where(out != 0, rng.uniform(-noise, noise, out.shape), 0.0)
 
 
 @pytest.fixture(scope="module")
