@@ -540,6 +540,16 @@ int ltm_debug_pcl_sort_order(const uint32_t* leaf_idx, size_t n, uint32_t* order
  * that the radix sort looks at -- the others are functions of more significant bits for every key inside the box and are left out
  * (fewer passes; order and equality of codes are unchanged).  Returns the number of kept bits, or < 0. */
 int ltm_debug_voxel_key_bits(const float* mn3, const float* mx3, float leaf, uint64_t* kept_mask, unsigned* depth, double* frame_min3);
+/* The launch constants of the projection kernels (k_vote_map_cull, k_map_rimg_blockmin, k_map_rimg_lds, k_map_rimg and the cull check), which the host
+ * computes once per launch and passes as a kernel argument, for a context with this field of view and base->lidar extrinsic (4x4 row-major, NULL =
+ * identity), the image of `res_alpha`, a map of `map_points` points and `n_keyframes` keyframes in the batch.  Needs no context; host arithmetic unless
+ * on_device != 0, which lets one thread of the current device evaluate the same expressions (what every thread did before they moved to the host).
+ *   out_f32[16] = half_v, half_h, 1/vfov, 1/hfov, rows, cols, rows - 1, cols - 1, row_scale, col_scale, row_bias, col_bias, 1 - 2 eps, rmin^2, eps, el_tclamp
+ *   out_u32[12] = rows, cols, rows * cols, steep_clamps, packable, n_tiles, n_tile_groups, magic, shift, grid size, el_fit, 0
+ * and, for the workgroups [first_block, first_block + n_blocks) of that launch, the map tile and the keyframe each one works on (0xffffffff in both
+ * for a workgroup with nothing to do): (b >> 6) / n_tile_groups is taken as mulhi(b & ~63, magic) >> shift, exact for every b < 2^32. */
+int ltm_debug_proj_launch(float vfov, float hfov, float res_alpha, const double* base2lidar16_or_null, size_t map_points, size_t n_keyframes, int on_device,
+                          float* out_f32, uint32_t* out_u32, uint32_t first_block, size_t n_blocks, uint32_t* out_tile, uint32_t* out_kf);
 /* checks the bounded-error projection that the range-culled vote kernel uses to decide which points need the exact
  * arithmetic: counts points (host xyz, n*3 floats; global frame if inv_pose16 is given, else local) whose exact pixel /
  * range fall outside its candidate set / bounds.  Must be 0. */

@@ -160,6 +160,7 @@ SIGNATURES = {
     "ltm_debug_selfcheck": (_i, [_vp, _pu64, C.POINTER(_i)]),
     "ltm_debug_cull_check": (_i, [_vp, _vp, _sz, _vp, _f, _pu64]),
     "ltm_debug_cull_stats": (_i, [_vp, _pu64, _pu64, _i]),
+    "ltm_debug_proj_launch": (_i, [_f, _f, _f, _vp, _sz, _sz, _i, _vp, _vp, C.c_uint32, _sz, _vp, _vp]),
     "ltm_debug_cull_validation": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_occlusion_stats": (_i, [_vp, _pu64, _pu64, _pu64, _i]),
     "ltm_debug_voxel_stats": (_i, [_vp, _pu64, _pu64, _i]),
@@ -209,6 +210,27 @@ def voxel_key_bits(mn, mx, leaf):
     if n < 0:
         raise ValueError("unsupported box / leaf")
     return n, mask.value, depth.value, np.array(list(fmin))
+
+
+PROJ_LAUNCH_F32 = ("half_v", "half_h", "inv_v", "inv_h", "frows", "fcols", "row_max", "col_max", "row_scale", "col_scale", "row_bias", "col_bias",
+                   "certain_lim", "rmin2", "eps", "el_tclamp")
+PROJ_LAUNCH_U32 = ("rows", "cols", "npx", "steep_clamps", "packable", "n_tiles", "n_tg", "tg_magic", "tg_shift", "grid", "el_fit", "fast")
+
+
+def proj_launch(vfov, hfov, alpha, base2lidar=None, map_points=0, n_keyframes=1, on_device=False, first_block=0, n_blocks=0):
+    """ltm_debug_proj_launch: ({name: float32}, {name: int}, tile[n_blocks], keyframe[n_blocks]) -- the launch constants of the projection kernels
+    and the (tile, keyframe) of a run of workgroups (0xffffffff: idle).  Needs no context; on_device evaluates the constants with one device thread."""
+    f = np.zeros(len(PROJ_LAUNCH_F32), dtype=np.float32)
+    u = np.zeros(len(PROJ_LAUNCH_U32), dtype=np.uint32)
+    tile = np.zeros(max(n_blocks, 1), dtype=np.uint32)
+    kf = np.zeros(max(n_blocks, 1), dtype=np.uint32)
+    b2l = None if base2lidar is None else _mat16(base2lidar)
+    rc = load_library().ltm_debug_proj_launch(float(vfov), float(hfov), float(alpha), None if b2l is None else b2l.ctypes.data, int(map_points),
+                                              int(n_keyframes), int(bool(on_device)), f.ctypes.data, u.ctypes.data, int(first_block), int(n_blocks),
+                                              tile.ctypes.data, kf.ctypes.data)
+    if rc != 0:
+        raise LtmError(rc, "ltm_debug_proj_launch")
+    return dict(zip(PROJ_LAUNCH_F32, f)), {k: int(v) for k, v in zip(PROJ_LAUNCH_U32, u)}, tile[:n_blocks], kf[:n_blocks]
 
 
 def inverse4x4(m):

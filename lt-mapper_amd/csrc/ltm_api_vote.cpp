@@ -4,13 +4,14 @@
 namespace ltm_detail {
 
 // utility.cpp:222-236 resetRimgSize
-Geom geom_for(const ltm_ctx* c, float alpha)
+// (the context's part of it as arguments: ltm_debug_proj_launch has no context)
+static Geom geom_from(float vfov, float hfov, float alpha, int fast_math, int el_fit, const float* el_c, float cull_eps_scale, float cull_eps_floor)
 {
     Geom g;
-    g.vfov = c->cfg.vfov; g.hfov = c->cfg.hfov;
-    g.rows = (int)roundf(c->cfg.vfov * alpha);
-    g.cols = (int)roundf(c->cfg.hfov * alpha);
-    g.fast = c->fast_math;
+    g.vfov = vfov; g.hfov = hfov;
+    g.rows = (int)roundf(vfov * alpha);
+    g.cols = (int)roundf(hfov * alpha);
+    g.fast = fast_math;
     // Error budget of the bounded-error projection in ANGLE: elevation polynomial 6e-7 rad fitted / 1.8e-6 generic, azimuth 4e-7,
     // transform 5e-7, v_rsq 1e-7, plus the reference's own float roundings of the degree / pixel arithmetic (~6e-7 rad equivalent).
     // In pixels the error is proportional to the resolution, and so is the band; never below cull_eps_floor (1e-3 px).
@@ -19,14 +20,18 @@ Geom geom_for(const ltm_ctx* c, float alpha)
     // tools/eps_sweep.py (profiles/r2_cull_eps_sweep*.json): with the band switched down the first exact pixels are missed at
     // 1e-4 * ppd with the generic elevation polynomial and at 5e-5 * ppd with the fitted one, at every resolution; the shipped band
     // is six times that.
-    const float scale = c->cull_eps_scale > 0.0f ? c->cull_eps_scale : (c->el_fit ? 3.0e-4f : 6.0e-4f);
-    g.cull_eps_px = std::max(c->cull_eps_floor, scale * ppd);
+    const float scale = cull_eps_scale > 0.0f ? cull_eps_scale : (el_fit ? 3.0e-4f : 6.0e-4f);
+    g.cull_eps_px = std::max(cull_eps_floor, scale * ppd);
     // elevation of the bounded-error projection (see Geom): the clamp sits one pixel outside the image, at most 2 deg (the fitted range)
-    g.el_fit = c->el_fit;
-    for (int i = 0; i < 4; ++i) g.el_c[i] = c->el_c[i];
+    g.el_fit = el_fit;
+    for (int i = 0; i < 4; ++i) g.el_c[i] = el_c[i];
     const double out_deg = std::min(2.0, (double)g.vfov / std::max(g.rows, 1));
     g.el_tclamp = (float)std::tan((0.5 * (double)g.vfov + out_deg) * (3.14159265358979323846 / 180.0));
     return g;
+}
+Geom geom_for(const ltm_ctx* c, float alpha)
+{
+    return geom_from(c->cfg.vfov, c->cfg.hfov, alpha, c->fast_math, c->el_fit, c->el_c, c->cull_eps_scale, c->cull_eps_floor);
 }
 
 // count of set labels given the exclusive scan `pos` of `labels` (n > 0)
@@ -586,6 +591,26 @@ int ltm_debug_cull_check(ltm_ctx* c, const float* xyz, size_t n, const double* i
 int ltm_debug_cull_validation(ltm_ctx* c, uint64_t* shapes_checked, uint64_t* shapes_failed)
 {
     return guarded(c, [&] { if (shapes_checked) *shapes_checked = c->cull_geoms_checked; if (shapes_failed) *shapes_failed = c->cull_geoms_failed; });
+}
+
+int ltm_debug_proj_launch(float vfov, float hfov, float alpha, const double* base2lidar16, size_t map_points, size_t n_keyframes, int on_device,
+                          float* out_f32, uint32_t* out_u32, uint32_t first_block, size_t n_blocks, uint32_t* out_tile, uint32_t* out_kf)
+{
+    if (!(vfov > 0.0f) || !(hfov > 0.0f) || !(alpha > 0.0f) || !out_f32 || !out_u32 || (n_blocks && (!out_tile || !out_kf))) return LTM_E_INVALID;
+    if (map_points >= 0xffffffffull || n_keyframes >= 0xffffffffull) return LTM_E_INVALID;
+    // the geometry a fresh context derives for this field of view (defaults of ltm_ctx; the fast-form switch is a device result and not part of the constants)
+    float el_c[4];
+    double err = 0.0;
+    const int el_fit = elevation_fit_for(vfov, el_c, &err);
+    const Geom g = geom_from(vfov, hfov, alpha, 0, el_fit, el_c, 0.0f, 1.0e-3f);
+    if (g.rows <= 0 || g.cols <= 0) return LTM_E_INVALID;
+    HostMat34 b2l{};
+    b2l.m[0] = b2l.m[5] = b2l.m[10] = 1.0;
+    int ident = 1;
+    if (base2lidar16) { b2l = to34(base2lidar16); ident = mat_is_identity(base2lidar16) ? 1 : 0; }
+    if (proj_launch_debug(g, b2l, ident, map_points, n_keyframes, on_device, out_f32, out_u32) != hipSuccess) return LTM_E_DEVICE;
+    if (n_blocks) proj_launch_blocks(map_points, n_keyframes, first_block, n_blocks, out_tile, out_kf);
+    return LTM_OK;
 }
 
 int ltm_debug_cull_stats(ltm_ctx* c, uint64_t* survivors, uint64_t* points, int reset)

@@ -239,20 +239,20 @@ hipError_t tile_bounds(const float4* map, size_t M, float* bounds, hipStream_t s
 template <bool B2L_IDENTITY>
 __global__ void __launch_bounds__(kBlock)
 k_map_rimg(const float4* __restrict__ map, size_t M, const double* __restrict__ inv_poses, size_t kb,
-           HostMat34 b2l_h, Geom gg, uint64_t* __restrict__ img)
+           HostMat34 b2l_h, ProjLaunch pl, uint64_t* __restrict__ img)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= M) return;
     const size_t kf = kb + blockIdx.y;
     const Mat34 Tinv = load_mat(inv_poses + 12 * kf);
-    const RimgGeom g = make_geom(gg);
+    const RimgGeom& g = pl.g;
     const float4 p4 = map[i];
     float3 p = xform(Tinv, make_float3(p4.x, p4.y, p4.z));
     if (B2L_IDENTITY) p = xform_identity(p); else p = xform(to_dev(b2l_h), p);
     const Sph s = cart2sph(p.x, p.y, p.z);
     const int px = pixel_index(g, s.az, s.el);
     const uint64_t v = ((uint64_t)f2u(s.r) << 32) | (uint64_t)(uint32_t)i;
-    img_min_u64(img + (size_t)blockIdx.y * (size_t)(g.rows * g.cols) + px, v);
+    img_min_u64(img + (size_t)blockIdx.y * (size_t)pl.npx + px, v);
 }
 
 // Same contract as k_map_rimg, with a per-workgroup LDS pre-reduction.  Map points are stored in octree (Morton)
@@ -265,46 +265,21 @@ static constexpr int kLdsSlots = 2048;
 static constexpr int kPtsPerThread = 16;
 static constexpr uint32_t kEmptyTag = 0xffffffffu;
 
-// XCD-aware workgroup -> (map tile, keyframe) mapping.  Workgroup b runs on XCD b % 8 (observed dispatch rule; used for speed
-// only, any other placement is still correct).  Consecutive workgroups of one XCD take the SAME map tile for `kfg`
-// consecutive keyframes, so the tile (64 KB) is fetched from HBM / Infinity Cache once and served from that XCD's L2
-// for the other kfg-1 keyframes: with ~224 resident workgroups per XCD the live tile set is ~28 x 64 KB << 4 MiB of L2.
-static constexpr unsigned kKfPerTile = 8;      // keyframes that reuse one map tile on an XCD (4 / 16 measured no better in round 2)
-struct TileKf { uint32_t tile, kfb; bool valid; };
-__device__ __forceinline__ TileKf tile_kf_of_block(uint32_t b, uint32_t n_tiles, uint32_t nb, uint32_t kfg)
-{
-    const uint32_t x = b & 7u, r = b >> 3;
-    const uint32_t n_tg = (n_tiles + 7u) >> 3;
-    const uint32_t kfl = r % kfg, q = r / kfg;
-    const uint32_t tg = q % n_tg, kg = q / n_tg;
-    TileKf t;
-    // the divisions above run on the vector unit; hand the (uniform) results back to scalar registers so that every address derived
-    // from them is a scalar base instead of a per-use v_readfirstlane
-    t.tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tg * 8u + x));
-    t.kfb = (uint32_t)__builtin_amdgcn_readfirstlane((int)(kg * kfg + kfl));
-    t.valid = (t.tile < n_tiles) & (t.kfb < nb);
-    return t;
-}
-static inline unsigned tile_kf_grid(size_t n_tiles, size_t nb, unsigned kfg)
-{
-    const size_t n_tg = (n_tiles + 7) / 8, n_kg = (nb + kfg - 1) / kfg;
-    return (unsigned)(n_tg * 8 * kfg * n_kg);
-}
-
+// (the XCD-aware workgroup -> (map tile, keyframe) mapping, tile_kf_of_block, is in ltm_kernels_common.h)
 template <bool B2L_IDENTITY>
 __global__ void __launch_bounds__(kBlock)
-k_map_rimg_lds(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, uint32_t kb, uint32_t nb, uint32_t kfg,
-               HostMat34 b2l_h, Geom gg, uint64_t* __restrict__ img)
+k_map_rimg_lds(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, uint32_t kb, uint32_t nb,
+               HostMat34 b2l_h, ProjLaunch pl, uint64_t* __restrict__ img)
 {
     __shared__ uint64_t vals[kLdsSlots];
     __shared__ uint32_t tags[kLdsSlots];
     const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
-    const TileKf tk = tile_kf_of_block(blockIdx.x, (M + per_block - 1) / per_block, nb, kfg);
+    const TileKf tk = tile_kf_of_block(blockIdx.x, pl, nb);
     if (!tk.valid) return;
     for (int s = threadIdx.x; s < kLdsSlots; s += kBlock) { tags[s] = kEmptyTag; vals[s] = ~0ull; }
     __syncthreads();
-    const RimgGeom g = make_geom(gg);
-    const uint32_t npx = (uint32_t)(g.rows * g.cols);
+    const RimgGeom& g = pl.g;
+    const uint32_t npx = pl.npx;
     const uint32_t block_base = tk.tile * per_block;
     const float4* __restrict__ mapb = map + block_base;
     const uint32_t nloc = min(per_block, M - block_base);
@@ -380,8 +355,9 @@ __device__ __forceinline__ float3 xform_approx(const float* __restrict__ ap, flo
 // (Tried: packed v_pk_* evaluation of the two polynomials -- no gain on gfx950, where v_pk_fma_f32 issues at half the rate of
 // v_fma_f32, tools/ubench/valu_rate.hip.)
 template <bool EL3 = false>
-__device__ __forceinline__ CullCand cull_candidates(const RimgGeom& g, float3 p, float row_scale, float col_scale, bool steep_clamps)
+__device__ __forceinline__ CullCand cull_candidates(const ProjLaunch& pl, float3 p)
 {
+    const RimgGeom& g = pl.g;
     CullCand cc;
     const float xy2 = __builtin_fmaf(p.x, p.x, p.y * p.y);
     cc.r2 = __builtin_fmaf(p.z, p.z, xy2);
@@ -405,9 +381,9 @@ __device__ __forceinline__ CullCand cull_candidates(const RimgGeom& g, float3 p,
     // rowh = rowf + 0.5 - eps: floor(rowf + 0.5) is the rounded pixel, and with the band half-width eps taken off up front
     //   fract(rowh) < 1 - 2 eps  <=>  fract(rowf + 0.5) in [eps, 1 - eps)  <=>  the pixel is certain, and then floor(rowh) is that pixel
     // (one fract and one compare per axis instead of a two-sided test; the sign of el sits on the uniform factor).
-    cc.rowh = __builtin_fmaf(el, -row_scale, 0.5f * g.frows + 0.5f - g.eps);
-    cc.colh = __builtin_fmaf(az, col_scale, 0.5f * g.fcols + 0.5f - g.eps);
-    const bool certain = fmaxf(__builtin_amdgcn_fractf(cc.rowh), __builtin_amdgcn_fractf(cc.colh)) < 1.0f - 2.0f * g.eps;
+    cc.rowh = __builtin_fmaf(el, -pl.row_scale, pl.row_bias);
+    cc.colh = __builtin_fmaf(az, pl.col_scale, pl.col_bias);
+    const bool certain = fmaxf(__builtin_amdgcn_fractf(cc.rowh), __builtin_amdgcn_fractf(cc.colh)) < pl.certain_lim;
     // Outside the fast forms' domain (every such case ends in the exact path):
     //  - the +-180 deg seam -- the SIGN of y picks column 0 or C-1 there, and the approximate y is only good to ~1e-7 of the range,
     //    so x < 0 with |y| <= 1e-6 |x| is undecidable here (y == +-0 included); the same test catches vanishing x and y (the squares
@@ -419,11 +395,11 @@ __device__ __forceinline__ CullCand cull_candidates(const RimgGeom& g, float3 p,
     // A NaN coordinate needs no guard: its range is NaN, `r < rimg` is false in the reference (utility.cpp:134), so the point never
     // wins a pixel -- and here r2 = NaN fails both compares below and the caller's r2 < qbound, so it is dropped, which is the same.
     cc.unusual = (fabsf(p.y) <= __builtin_fmaf(-1.0e-6f, p.x, 1.0e-18f)) | (cc.r2 > 6.4e7f);
-    if (!EL3) cc.unusual |= !steep_clamps & (t_el > 1.0f);
+    if (!EL3) cc.unusual |= !pl.steep_clamps & (t_el > 1.0f);
     cc.multi = !certain;
     // clamp(floor(v), 0, n-1) == trunc(med3(v, 0, n-1)): the bounds are integers and the clamped value is non-negative
-    cc.rb = (int)__builtin_amdgcn_fmed3f(cc.rowh, 0.0f, g.frows - 1.0f);
-    cc.cb = (int)__builtin_amdgcn_fmed3f(cc.colh, 0.0f, g.fcols - 1.0f);
+    cc.rb = (int)__builtin_amdgcn_fmed3f(cc.rowh, 0.0f, g.row_max);
+    cc.cb = (int)__builtin_amdgcn_fmed3f(cc.colh, 0.0f, g.col_max);
     cc.r0 = cc.r1 = cc.rb; cc.c0 = cc.c1 = cc.cb;
     return cc;
 }
@@ -432,15 +408,16 @@ __device__ __forceinline__ CullCand cull_candidates(const RimgGeom& g, float3 p,
 __device__ __forceinline__ float cull_r_lo(float r2) { return __builtin_amdgcn_sqrtf(r2) * (1.0f - 1.5e-6f); }
 
 // candidate pixel rectangle of a point that sits within cull_eps_px of a rounding boundary (rare)
-__device__ __forceinline__ void cull_expand(const RimgGeom& g, CullCand& cc)
+__device__ __forceinline__ void cull_expand(const ProjLaunch& pl, CullCand& cc)
 {
+    const RimgGeom& g = pl.g;
     // rowh / colh carry the -eps shift of cull_candidates: a fraction >= 1 - 2 eps means the unshifted value is within eps of the
     // integer above floor(rowh) -- either pixel floor(rowh) or floor(rowh) + 1
     const float rfl = floorf(cc.rowh), cfl = floorf(cc.colh);
     const float rfr = cc.rowh - rfl, cfr = cc.colh - cfl;
     const int rc = (int)rfl, ccn = (int)cfl;
     const int rmax = g.rows - 1, cmax = g.cols - 1;
-    const float lim = 1.0f - 2.0f * g.eps;
+    const float lim = pl.certain_lim;
     cc.r0 = min(max(rc, 0), rmax);
     cc.r1 = min(max(rc + (rfr >= lim ? 1 : 0), 0), rmax);
     cc.c0 = min(max(ccn, 0), cmax);
@@ -449,14 +426,8 @@ __device__ __forceinline__ void cull_expand(const RimgGeom& g, CullCand& cc)
 
 // With a non-identity base->lidar extrinsic the exact path rounds to float between the two transforms (utility.cpp:70-71), i.e.
 // at magnitude range + lever arm; relative to a range much smaller than the lever arm that rounding exceeds the validated bounds
-// of the approximate projection, so points nearer than lever/8 take the exact path (none with an identity extrinsic).
-template <bool B2L_IDENTITY>
-__device__ __forceinline__ float cull_min_range(const HostMat34& b2l)
-{
-    if (B2L_IDENTITY) return 0.0f;
-    const float tx = (float)b2l.m[3], ty = (float)b2l.m[7], tz = (float)b2l.m[11];
-    return 0.125f * __builtin_sqrtf(tx * tx + ty * ty + tz * tz) + 1.0e-6f;
-}
+// of the approximate projection, so points nearer than lever/8 take the exact path (none with an identity extrinsic):
+// ProjLaunch::rmin2 = (0.125 |t| + 1e-6)^2 of the extrinsic's translation t (make_proj_launch).
 
 __device__ unsigned long long g_cull_stats[4];   // {survivors, points} of k_vote_map_cull, then of k_map_rimg_blockmin: diagnostic, read by cull_stats()
 
@@ -565,7 +536,7 @@ static constexpr int kCullSlots = 512;   // survivors are ~10 % of a workgroup's
 template <bool B2L_IDENTITY, bool EL3>     // EL3: fitted elevation polynomial (Geom::el_fit), see cull_candidates
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, const float* __restrict__ approx_poses,
-                uint32_t kb, uint32_t nb, uint32_t kfg, HostMat34 b2l_h, Geom gg, const float* __restrict__ qbound_img,
+                uint32_t kb, uint32_t nb, HostMat34 b2l_h, ProjLaunch pl, const float* __restrict__ qbound_img,
                 const float* __restrict__ tile_bounds, const uint32_t* __restrict__ smax_bits, float thr, uint64_t* __restrict__ img)
 {
     __shared__ uint64_t vals[kCullSlots];
@@ -576,14 +547,14 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
     __shared__ uint16_t uqueue[kCullQueue];    // the uncertain ones, re-queued densely in phase 2
     __shared__ uint32_t qcount, ucount;
     const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
-    const TileKf tk = tile_kf_of_block(blockIdx.x, (M + per_block - 1) / per_block, nb, kfg);
+    const TileKf tk = tile_kf_of_block(blockIdx.x, pl, nb);
     if (!tk.valid) return;
     if (tile_bounds && tile_out_of_reach(approx_poses + 16 * (size_t)(kb + tk.kfb), tile_bounds + 6 * (size_t)tk.tile, u2f(smax_bits[tk.kfb]), thr)) return;
     for (int s = threadIdx.x; s < kCullSlots; s += kBlock) { tags[s] = kEmptyTag; vals[s] = ~0ull; }
     if (threadIdx.x == 0) { qcount = 0; ucount = 0; }
     __syncthreads();
-    const RimgGeom g = make_geom(gg);
-    const uint32_t npx = (uint32_t)(g.rows * g.cols);
+    const RimgGeom& g = pl.g;
+    const uint32_t npx = pl.npx;
     const uint32_t block_base = tk.tile * per_block;
     const float4* __restrict__ mapb = map + block_base;
     const uint32_t nloc = min(per_block, M - block_base);
@@ -593,13 +564,11 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
     // ---- phase 1: who can matter?  (bounded-error arithmetic only).  Four points per lane are in flight at once so the
     // dependent scan-image load of one overlaps the arithmetic of the others.  Only full tiles: the one partial tile at the end
     // of the map takes the exact path as a whole (below), which keeps bounds tests and clamped indices out of this loop.
-    const bool full_tile = nloc == per_block;
+    // Neither does an image whose rows / columns do not fit the queue word (9 + 11 bits) nor a keyframe whose approximate pose is not usable (ap[15] == 0):
+    // every point of such a tile used to be queued as "uncertain", which overflowed the queue and sent the tile down the exact path anyway.
+    const float* __restrict__ ap = approx_poses + 16 * (size_t)kf;
+    const bool full_tile = (nloc == per_block) & pl.packable & (ap[15] != 0.0f);
     if (full_tile) {
-        const float* __restrict__ ap = approx_poses + 16 * (size_t)kf;
-        const float row_scale = g.frows * (57.29577951308232f / g.vfov), col_scale = g.fcols * (57.29577951308232f / g.hfov);
-        const float rmin = cull_min_range<B2L_IDENTITY>(b2l_h), rmin2 = rmin * rmin;
-        const bool steep_clamps = g.vfov < 88.0f;
-        const bool ok_img = g.rows < 511 && g.cols <= 2048;      // the queue word holds 9 row bits and 11 column bits
         constexpr int kInFlight = 4;
         constexpr bool kPrefetch = true;     // software pipelining: the next group's points are requested before this group's arithmetic
         float4 nxt[kInFlight];
@@ -625,11 +594,11 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
             }
 #pragma unroll
             for (int u = 0; u < kInFlight; ++u) {
-                bool ok;
+                bool ok;      // (uniform, part of full_tile)
                 const float3 p = xform_approx(ap, pt[u], ok);
-                cc[u] = cull_candidates<EL3>(g, p, row_scale, col_scale, steep_clamps);
+                cc[u] = cull_candidates<EL3>(pl, p);
                 // not certain of the pixel (within cull_eps_px of a rounding boundary, ~1 % of the points): straight to the exact path
-                cc[u].unusual |= !ok_img | !ok | cc[u].multi | (B2L_IDENTITY ? false : (cc[u].r2 < rmin2));
+                cc[u].unusual |= cc[u].multi | (B2L_IDENTITY ? false : (cc[u].r2 < pl.rmin2));
                 q0[u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(qk) + ((__umul24((uint32_t)cc[u].rb, (uint32_t)g.cols) + (uint32_t)cc[u].cb) << 2));   // uniform base + 32-bit offset
             }
             bool mt[kInFlight];
@@ -668,7 +637,7 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
     // ---- phase 2: survivors.  Certain pixel: only the exact range is computed; the ~1 % others are re-queued densely at the
     // top of the same array and get the full exact projection afterwards (keeps both loops free of divergence).
     const uint32_t nq_all = full_tile ? qcount : (uint32_t)kCullQueue + 1u;
-    if (full_tile && threadIdx.x == 0 && (blockIdx.x & 63u) == 0u) {   // sampled 1/64: same-address atomics from every workgroup would serialise the grid
+    if (nloc == per_block && threadIdx.x == 0 && (blockIdx.x & 63u) == 0u) {   // sampled 1/64: same-address atomics from every workgroup would serialise the grid
         atomicAdd(&g_cull_stats[0], (unsigned long long)nq_all);
         atomicAdd(&g_cull_stats[1], (unsigned long long)nloc);
     }
@@ -722,11 +691,11 @@ hipError_t vote_map_range_images(const float4* map, size_t M, const double* inv_
     if (!M || !nb) return hipSuccess;
     if (mode != 0 || !ko.vote_cull || !approx_poses_dev || !qbound_img) return map_range_images(map, M, inv_poses_dev, approx_poses_dev, kb, nb, b2l, b2l_identity, g, map_img, s, ko);
     const size_t per_block = (size_t)kBlock * kPtsPerThread;
-    const unsigned kfg = kKfPerTile;
-    dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb, kfg));
+    dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb));
+    const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);
     const float* tb = (ko.tile_cull && smax_bits_dev) ? tile_bounds_dev : nullptr;
     const bool el3 = g.el_fit != 0;
-#define LTM_LAUNCH_CULL(ID, E) k_vote_map_cull<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, kfg, b2l, g, qbound_img, tb, smax_bits_dev, thr, map_img)
+#define LTM_LAUNCH_CULL(ID, E) k_vote_map_cull<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, qbound_img, tb, smax_bits_dev, thr, map_img)
     if (!b2l_identity) { if (el3) LTM_LAUNCH_CULL(false, true); else LTM_LAUNCH_CULL(false, false); }
     else { if (el3) LTM_LAUNCH_CULL(true, true); else LTM_LAUNCH_CULL(true, false); }
 #undef LTM_LAUNCH_CULL
@@ -736,12 +705,12 @@ hipError_t vote_map_range_images(const float4* map, size_t M, const double* inv_
 // debug: number of points whose exact pixel is NOT inside the candidate set of the bounded-error projection.
 // T (3x4 double) / ap (16 floats) are the exact and the approximate form of the same keyframe transform, or null.
 __global__ void __launch_bounds__(kBlock)
-k_cull_check(const float* __restrict__ xyz, size_t n, HostMat34 T, HostMat34 b2l, int b2l_identity, const float* __restrict__ ap, Geom gg,
+k_cull_check(const float* __restrict__ xyz, size_t n, HostMat34 T, HostMat34 b2l, int b2l_identity, const float* __restrict__ ap, ProjLaunch pl,
              unsigned long long* __restrict__ bad)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const RimgGeom g = make_geom(gg);
+    const RimgGeom& g = pl.g;
     const float4 p4 = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
     float3 pe = make_float3(p4.x, p4.y, p4.z), pa = pe;
     bool ok = true;
@@ -750,12 +719,10 @@ k_cull_check(const float* __restrict__ xyz, size_t n, HostMat34 T, HostMat34 b2l
         pe = b2l_identity ? xform_identity(pe) : xform(to_dev(b2l), pe);
         pa = xform_approx(ap, p4, ok);
     }
-    const float row_scale = g.frows * (57.29577951308232f / g.vfov), col_scale = g.fcols * (57.29577951308232f / g.hfov);
-    CullCand cc = g.el_fit ? cull_candidates<true>(g, pa, row_scale, col_scale, g.vfov < 88.0f) : cull_candidates<false>(g, pa, row_scale, col_scale, g.vfov < 88.0f);
+    CullCand cc = g.el_fit ? cull_candidates<true>(pl, pa) : cull_candidates<false>(pl, pa);      // the launch constants of the hot kernels, from the same make_proj_launch
     if (cc.unusual || !ok) return;
-    const float rmin = cull_min_range<false>(b2l);
-    if (ap && !b2l_identity && cc.r2 < rmin * rmin) return;      // these take the exact path in the kernels
-    if (cc.multi) cull_expand(g, cc);
+    if (ap && !b2l_identity && cc.r2 < pl.rmin2) return;      // these take the exact path in the kernels
+    if (cc.multi) cull_expand(pl, cc);
     const Sph s = cart2sph(pe.x, pe.y, pe.z);
     int row, col;
     pixel_row_col(g, s.az, s.el, row, col);
@@ -771,8 +738,9 @@ hipError_t cull_check(const float* xyz_dev, size_t n, const HostMat34* T, const 
 {
     if (!n) return hipSuccess;
     HostMat34 z{};
-    k_cull_check<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(xyz_dev, n, T ? *T : z, b2l ? *b2l : z, b2l ? b2l_identity : 1,
-                                                            T ? approx_pose_dev : nullptr, g, bad_dev);
+    const int ident = b2l ? b2l_identity : 1;
+    k_cull_check<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(xyz_dev, n, T ? *T : z, b2l ? *b2l : z, ident,
+                                                            T ? approx_pose_dev : nullptr, make_proj_launch(g, b2l ? *b2l : z, ident, 0), bad_dev);
     return hipGetLastError();
 }
 
@@ -837,7 +805,7 @@ static constexpr int kBmUQueue = 1024;    // dense re-queue of the uncertain sur
 template <bool B2L_IDENTITY, bool EL3, int SLOT_ROWS = 16>
 __global__ void __launch_bounds__(kBlock)
 k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, const float* __restrict__ approx_poses,
-                    uint32_t kb, uint32_t nb, uint32_t kfg, HostMat34 b2l_h, Geom gg, uint64_t* __restrict__ img, const uint32_t* __restrict__ pairs, uint32_t n_pairs,
+                    uint32_t kb, uint32_t nb, HostMat34 b2l_h, ProjLaunch pl, uint64_t* __restrict__ img, const uint32_t* __restrict__ pairs, uint32_t n_pairs,
                     const uint8_t* __restrict__ submask)
 {
     constexpr int kBmSlots = SLOT_ROWS * 64;
@@ -862,31 +830,30 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
         tk.tile = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pr / nb)); tk.kfb = (uint32_t)__builtin_amdgcn_readfirstlane((int)(pr % nb)); tk.valid = true;
         if (submask) quarters = (uint32_t)__builtin_amdgcn_readfirstlane((int)submask[pr]);      // quarters of the tile the occlusion cull left alive
     } else {
-        tk = tile_kf_of_block(blockIdx.x, (M + per_block - 1) / per_block, nb, kfg);
+        tk = tile_kf_of_block(blockIdx.x, pl, nb);
     }
     if (!tk.valid) return;
     for (int s = threadIdx.x; s < kBmSlots; s += kBlock) { tags[s] = kEmptyTag; amin[s] = 0x7f800000u; }
     if (threadIdx.x == 0) { qcount = 0; ucount = 0; }
     __syncthreads();
-    const RimgGeom g = make_geom(gg);
-    const uint32_t npx = (uint32_t)(g.rows * g.cols);
+    const RimgGeom& g = pl.g;
+    const uint32_t npx = pl.npx;
     const uint32_t block_base = tk.tile * per_block;
     const float4* __restrict__ mapb = map + block_base;
     const uint32_t nloc = min(per_block, M - block_base);
     const uint32_t kf = kb + tk.kfb;
     uint64_t* __restrict__ imgk = img + (size_t)tk.kfb * npx;
     const float* __restrict__ ap = approx_poses + 16 * (size_t)kf;
-    const float row_scale = g.frows * (57.29577951308232f / g.vfov), col_scale = g.fcols * (57.29577951308232f / g.hfov);
-    const bool packable = g.rows < (int)kBmRowUncertain && g.cols <= 2048;
-    const float rmin = cull_min_range<B2L_IDENTITY>(b2l_h), rmin2 = rmin * rmin;
-    const bool steep_clamps = g.vfov < 88.0f;
+    static_assert(kBmRowUncertain == 511u, "ProjLaunch::packable is rows < 511");
     // per-lane record of the 16 points: amin slot (bits 20+) | row | col, and the range lower bound -- of the points that own an
     // amin slot; -1 for the others, which no table entry can beat (their slot field is 0: any valid index)
     float rlo[kPtsPerThread];
     uint32_t rec[kPtsPerThread];
     // Only full tiles run the pre-filter: the one partial tile at the end of the map takes the exact path as a whole (phase 2),
     // which keeps bounds tests and clamped indices out of these loops.
-    const bool full_tile = nloc == per_block;
+    // Neither does an image whose rows / columns do not fit the record (9 + 11 bits) nor a keyframe whose approximate pose is not usable (ap[15] == 0):
+    // every point of such a tile used to be recorded as "uncertain" and survive, which overflowed the queue and sent the tile down the exact path anyway.
+    const bool full_tile = (nloc == per_block) & pl.packable & (ap[15] != 0.0f);
     if (full_tile) {
         // ---- phase 1a (four points per lane in flight, as in k_vote_map_cull)
 #pragma unroll
@@ -901,18 +868,18 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
             CullCand cc[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) pt[u] = mapb[(uint32_t)(j0 + u) * kBlock + threadIdx.x];
-            bool ok = true;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
+                bool ok;      // (uniform, part of full_tile)
                 const float3 p = xform_approx(ap, pt[u], ok);
-                cc[u] = cull_candidates<EL3>(g, p, row_scale, col_scale, steep_clamps);
+                cc[u] = cull_candidates<EL3>(pl, p);
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + u;
                 const float r_lo = cull_r_lo(cc[u].r2);
                 rlo[j] = -1.0f;
-                const bool certain = packable & ok & !cc[u].unusual & !cc[u].multi & !(cc[u].r2 < rmin2);
+                const bool certain = !cc[u].unusual & !cc[u].multi & !(cc[u].r2 < pl.rmin2);
                 rec[j] = ((certain ? (uint32_t)cc[u].rb : kBmRowUncertain) << 11) | (uint32_t)(cc[u].cb & 2047);
                 if (!certain) continue;
                 const uint32_t px = (uint32_t)(cc[u].rb * g.cols + cc[u].cb);
@@ -966,7 +933,7 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
     __syncthreads();
     // ---- phase 2: survivors.  Certain pixel: only the exact range; the others are re-queued densely and get the full exact projection
     const uint32_t nq = full_tile ? qcount : (uint32_t)kBmQueue + 1u;
-    if (full_tile && threadIdx.x == 0 && (blockIdx.x & 63u) == 0u) {   // sampled diagnostic
+    if (nloc == per_block && threadIdx.x == 0 && (blockIdx.x & 63u) == 0u) {   // sampled diagnostic
         atomicAdd(&g_cull_stats[2], (unsigned long long)nq);
         atomicAdd(&g_cull_stats[3], (unsigned long long)nloc);
     }
@@ -1010,11 +977,11 @@ hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses
                             HostMat34 b2l, int b2l_identity, Geom g, uint64_t* map_img, hipStream_t s, const KernelOpts& ko)
 {
     if (!M || !nb) return hipSuccess;
+    const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);      // once per launch, on the host
     if (ko.map_kernel_variant >= 2 && approx_poses_dev) {
         const size_t per_block = (size_t)kBlock * kPtsPerThread;
-        const unsigned kfg = kKfPerTile;
-        dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb, kfg));
-#define LTM_LAUNCH_BM(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, kfg, b2l, g, map_img, nullptr, 0u, nullptr)
+        dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb));
+#define LTM_LAUNCH_BM(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img, nullptr, 0u, nullptr)
         const bool el3 = g.el_fit != 0;
         if (!b2l_identity) { if (el3) LTM_LAUNCH_BM(false, true); else LTM_LAUNCH_BM(false, false); }
         else { if (el3) LTM_LAUNCH_BM(true, true); else LTM_LAUNCH_BM(true, false); }
@@ -1023,15 +990,14 @@ hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses
     }
     if (ko.map_kernel_variant >= 1) {
         const size_t per_block = (size_t)kBlock * kPtsPerThread;
-        const unsigned kfg = kKfPerTile;
-        dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb, kfg));
-        if (b2l_identity) k_map_rimg_lds<true><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, (uint32_t)kb, (uint32_t)nb, kfg, b2l, g, map_img);
-        else k_map_rimg_lds<false><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, (uint32_t)kb, (uint32_t)nb, kfg, b2l, g, map_img);
+        dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb));
+        if (b2l_identity) k_map_rimg_lds<true><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img);
+        else k_map_rimg_lds<false><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img);
         return hipGetLastError();
     }
     dim3 grid(grid_for(M), (unsigned)nb);
-    if (b2l_identity) k_map_rimg<true><<<grid, dim3(kBlock), 0, s>>>(map, M, inv_poses_dev, kb, b2l, g, map_img);
-    else k_map_rimg<false><<<grid, dim3(kBlock), 0, s>>>(map, M, inv_poses_dev, kb, b2l, g, map_img);
+    if (b2l_identity) k_map_rimg<true><<<grid, dim3(kBlock), 0, s>>>(map, M, inv_poses_dev, kb, b2l, pl, map_img);
+    else k_map_rimg<false><<<grid, dim3(kBlock), 0, s>>>(map, M, inv_poses_dev, kb, b2l, pl, map_img);
     return hipGetLastError();
 }
 
@@ -1217,7 +1183,8 @@ hipError_t map_range_images_pairs(const float4* map, size_t M, const double* inv
 {
     if (!n_pairs) return hipSuccess;
     dim3 grid((unsigned)(((n_pairs + 7) / 8) * 8));
-#define LTM_LAUNCH_BMP(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, 1u, b2l, g, map_img, pairs, (uint32_t)n_pairs, submask)
+    const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);
+#define LTM_LAUNCH_BMP(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img, pairs, (uint32_t)n_pairs, submask)
     const bool el3 = g.el_fit != 0;
     if (!b2l_identity) { if (el3) LTM_LAUNCH_BMP(false, true); else LTM_LAUNCH_BMP(false, false); }
     else { if (el3) LTM_LAUNCH_BMP(true, true); else LTM_LAUNCH_BMP(true, false); }
@@ -1329,5 +1296,48 @@ hipError_t selfcheck_fast_math(float vfov, float hfov, unsigned long long* count
     return hipGetLastError();
 }
 
+// debug (ltm_debug_proj_launch): the launch constants as the hot kernels get them, flattened -- from the host's make_proj_launch, or (on_device) from
+// the same expressions evaluated by one device thread, which is what every thread of every workgroup did before the constants moved to the host
+static void proj_launch_flatten(const ProjLaunch& pl, uint32_t nb, float* f, uint32_t* u)
+{
+    const RimgGeom& g = pl.g;
+    const float ff[kProjLaunchFloats] = {g.half_v, g.half_h, g.inv_v, g.inv_h, g.frows, g.fcols, g.row_max, g.col_max, pl.row_scale, pl.col_scale,
+                                         pl.row_bias, pl.col_bias, pl.certain_lim, pl.rmin2, g.eps, g.el_tclamp};
+    const uint32_t uu[kProjLaunchWords] = {(uint32_t)g.rows, (uint32_t)g.cols, pl.npx, pl.steep_clamps ? 1u : 0u, pl.packable ? 1u : 0u, pl.n_tiles, pl.n_tg,
+                                           pl.tg_magic, pl.tg_shift, tile_kf_grid(pl.n_tiles, nb), g.el_fit ? 1u : 0u, g.fast ? 1u : 0u};
+    memcpy(f, ff, sizeof ff);
+    memcpy(u, uu, sizeof uu);
+}
+__global__ void k_proj_launch_eval(Geom gg, HostMat34 b2l, int b2l_identity, size_t M, ProjLaunch* out)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *out = make_proj_launch(gg, b2l, b2l_identity, M);
+}
+hipError_t proj_launch_debug(Geom g, HostMat34 b2l, int b2l_identity, size_t M, size_t nb, int on_device, float* f, uint32_t* u)
+{
+    ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);
+    if (on_device) {
+        ProjLaunch* d = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(ProjLaunch));
+        if (e != hipSuccess) return e;
+        k_proj_launch_eval<<<dim3(1), dim3(64)>>>(g, b2l, b2l_identity, M, d);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(&pl, d, sizeof(ProjLaunch), hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        if (e != hipSuccess) return e;
+    }
+    proj_launch_flatten(pl, (uint32_t)nb, f, u);
+    return hipSuccess;
+}
+void proj_launch_blocks(size_t M, size_t nb, uint32_t first_block, size_t n, uint32_t* tile, uint32_t* kf)
+{
+    Geom g{};
+    g.vfov = g.hfov = 1.0f;
+    const ProjLaunch pl = make_proj_launch(g, HostMat34{}, 1, M);
+    for (size_t i = 0; i < n; ++i) {
+        const TileKf t = tile_kf_of_block(first_block + (uint32_t)i, pl, (uint32_t)nb);
+        tile[i] = t.valid ? t.tile : 0xffffffffu;
+        kf[i] = t.valid ? t.kfb : 0xffffffffu;
+    }
+}
 
 } // namespace ltm

@@ -77,6 +77,12 @@ hipError_t vote_map_range_images(const float4* map, size_t M, const double* inv_
                                  const uint32_t* smax_bits_dev, float thr, int mode, uint64_t* map_img, hipStream_t s, const KernelOpts& ko);
 hipError_t count_live_tiles(const float* approx_poses_dev, size_t kb, size_t nb, const float* tile_bounds_dev, size_t n_tiles,
                             const uint32_t* smax_bits_dev, float thr, unsigned long long* live_dev, hipStream_t s);
+// debug (ltm_debug_proj_launch): the launch constants of the projection kernels (ProjLaunch, ltm_kernels_common.h) for a map of M points and nb keyframes,
+// evaluated on the host as every launch does (on_device: by one device thread instead); f / u in the order include/ltm.h documents
+static constexpr int kProjLaunchFloats = 16, kProjLaunchWords = 12;
+hipError_t proj_launch_debug(Geom g, HostMat34 b2l, int b2l_identity, size_t M, size_t nb, int on_device, float* f, uint32_t* u);
+// (tile, keyframe) of workgroups [first_block, first_block + n) of a (tiles x keyframes) launch, 0xffffffff for a workgroup with nothing to do
+void proj_launch_blocks(size_t M, size_t nb, uint32_t first_block, size_t n, uint32_t* tile, uint32_t* kf);
 hipError_t cull_stats(unsigned long long* out2, int reset, hipStream_t s, int which_kernel);   // {survivors, points} since the last reset; 0 vote kernel, 1 exact-image kernel
 hipError_t cull_check(const float* xyz_dev, size_t n, const HostMat34* T, const HostMat34* b2l, int b2l_identity, const float* approx_pose_dev,
                       Geom g, unsigned long long* bad_dev, hipStream_t s);

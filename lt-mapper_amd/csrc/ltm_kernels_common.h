@@ -35,6 +35,78 @@ __host__ __device__ inline RimgGeom make_geom(Geom g)
     return r;
 }
 
+// What a projection launch needs that depends only on the launch (image shape, extrinsic, map size): filled once on the host by make_proj_launch and
+// passed by value, so every field sits in scalar registers.  gfx950 has no scalar float unit: the same expressions evaluated in the kernels cost VALU
+// issue slots and VGPRs in every one of the ~10^6 workgroups of a full-map launch.  Every float is computed with exactly the expression and operand
+// order the kernels used (binary32, no contraction, correctly rounded division and square root on both sides), so the bits are the same.
+static constexpr unsigned kKfPerTile = 8;      // keyframes that reuse one map tile on an XCD (4 / 16 measured no better in round 2)
+struct ProjLaunch {
+    RimgGeom g;
+    float row_scale, col_scale;        // pixels per radian: rows * (180/pi / vfov), cols * (180/pi / hfov)
+    float row_bias, col_bias;          // rows/2 + 0.5 - eps, cols/2 + 0.5 - eps (cull_candidates: rowh / colh)
+    float certain_lim;                 // 1 - 2 eps
+    float rmin2;                       // square of cull_min_range: nearer points take the exact path (0 with an identity base->lidar)
+    uint32_t npx;                      // rows * cols
+    uint32_t n_tiles, n_tg;            // 4096-point map tiles, groups of 8 tiles (tile_kf_of_block)
+    uint32_t tg_magic, tg_shift;       // (b >> 6) / n_tg == mulhi(b & ~63, tg_magic) >> tg_shift for every b < 2^32
+    bool steep_clamps;                 // vfov < 88: every elevation beyond +-45 deg clamps into the first / last row
+    bool packable;                     // rows < 511 and cols <= 2048: row and column fit the 9 + 11 bits of a queue word
+};
+__host__ __device__ inline ProjLaunch make_proj_launch(Geom gg, const HostMat34& b2l, int b2l_identity, size_t M)
+{
+    ProjLaunch pl;
+    const RimgGeom g = make_geom(gg);
+    pl.g = g;
+    pl.row_scale = g.frows * (57.29577951308232f / g.vfov); pl.col_scale = g.fcols * (57.29577951308232f / g.hfov);
+    pl.row_bias = 0.5f * g.frows + 0.5f - g.eps; pl.col_bias = 0.5f * g.fcols + 0.5f - g.eps;
+    pl.certain_lim = 1.0f - 2.0f * g.eps;
+    float rmin = 0.0f;
+    if (!b2l_identity) {      // see cull_min_range
+        const float tx = (float)b2l.m[3], ty = (float)b2l.m[7], tz = (float)b2l.m[11];
+        rmin = 0.125f * __builtin_sqrtf(tx * tx + ty * ty + tz * tz) + 1.0e-6f;
+    }
+    pl.rmin2 = rmin * rmin;
+    pl.npx = (uint32_t)(g.rows * g.cols);
+    pl.steep_clamps = g.vfov < 88.0f;
+    pl.packable = g.rows < 511 && g.cols <= 2048;
+    const size_t per_block = (size_t)kBlock * 16;
+    pl.n_tiles = (uint32_t)((M + per_block - 1) / per_block);
+    pl.n_tg = (pl.n_tiles + 7u) >> 3;
+    // q = b >> 6 < 2^26 and d = n_tg <= 2^s: with m = floor(2^(26+s) / d) + 1 = (2^(26+s) + e) / d, 0 < e <= d, q m / 2^(26+s) = q/d + q e / (d 2^(26+s)) and
+    // q e < 2^(26+s), so the floor is floor(q / d); m < 2^27 + 1.  q m / 2^26 is the high word of (q << 6) m.
+    const uint32_t d = pl.n_tg ? pl.n_tg : 1u;
+    uint32_t s = 0;
+    while (((uint64_t)1 << s) < d) ++s;
+    pl.tg_shift = s;
+    pl.tg_magic = (uint32_t)((((uint64_t)1 << (26u + s)) / d) + 1u);
+    return pl;
+}
+
+// XCD-aware workgroup -> (map tile, keyframe) mapping.  Workgroup b runs on XCD b % 8 (observed dispatch rule; used for speed
+// only, any other placement is still correct).  Consecutive workgroups of one XCD take the SAME map tile for kKfPerTile
+// consecutive keyframes, so the tile (64 KB) is fetched from HBM / Infinity Cache once and served from that XCD's L2
+// for the other keyframes: with ~224 resident workgroups per XCD the live tile set is ~28 x 64 KB << 4 MiB of L2.
+// b = ((kg * n_tg + tg) * kKfPerTile + kfl) * 8 + x  ->  tile = tg * 8 + x, keyframe = kg * kKfPerTile + kfl.  The quotient by n_tg comes from the
+// launch's multiply-high constant and the rest are shifts: the block index is uniform, so all of it runs on the scalar unit.
+struct TileKf { uint32_t tile, kfb; bool valid; };
+__host__ __device__ inline TileKf tile_kf_of_block(uint32_t b, const ProjLaunch& pl, uint32_t nb)
+{
+    static_assert(kKfPerTile == 8, "the shifts below are log2(8 XCDs) + log2(kKfPerTile)");
+    const uint32_t x = b & 7u, kfl = (b >> 3) & (kKfPerTile - 1u), q = b >> 6;
+    const uint32_t kg = (uint32_t)(((uint64_t)(b & ~63u) * pl.tg_magic) >> 32) >> pl.tg_shift;
+    const uint32_t tg = q - kg * pl.n_tg;
+    TileKf t;
+    t.tile = tg * 8u + x;
+    t.kfb = kg * kKfPerTile + kfl;
+    t.valid = (t.tile < pl.n_tiles) & (t.kfb < nb);
+    return t;
+}
+static inline unsigned tile_kf_grid(size_t n_tiles, size_t nb)
+{
+    const size_t n_tg = (n_tiles + 7) / 8, n_kg = (nb + kKfPerTile - 1) / kKfPerTile;
+    return (unsigned)(n_tg * 8 * kKfPerTile * n_kg);
+}
+
 inline unsigned grid_for(size_t n, int block = kBlock)
 {
     size_t b = (n + block - 1) / block;

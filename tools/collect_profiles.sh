@@ -10,6 +10,8 @@
 # Results land in gpurun_out/profiles_<tag>/ (merged back by gpurun); copy what should be judged into profiles/
 # (pmc_*.json keep their names: bench.py reads them and checks the kernel-source hash and the workload inside).
 # Counter passes are separate runs with --pmc only (no tracing domains), as the pool requires.
+# Every step that uses the GPU runs under its own time limit, and the first one that fails ends the collection: nothing more is started on a card that
+# has just faulted or hung.
 TAG=${1:-rX}
 PARTS=${2:-"trace pmc line sq"}
 ROOT=$(pwd)
@@ -17,13 +19,15 @@ OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 BENCH="python $ROOT/bench.py"
+LIMIT="timeout -k 10 600"
+set -o pipefail
 COMMIT=$(cat "$ROOT/.commit_for_profiles" 2>/dev/null || echo unknown)
 
 kernel_trace() {   # $1 = workload, $2 = output stem
   rm -rf /tmp/prof_kt
   # round 6: --lanes 1 -- per-kernel durations and counters are taken from the ONE-lane order (launches that overlap count each other's time); the bench line itself runs two lanes
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o bench -- $BENCH --workload $1 --steps 1 --warmup 0 --lanes 1 --full --no-cpu-baseline --no-t-total \
-      --extra-out "$OUT/${2}_bench_under_rocprof_extra.json" 2>/dev/null | tail -1 > "$OUT/${2}_bench_under_rocprof.json"
+  $LIMIT rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -o bench -- $BENCH --workload $1 --steps 1 --warmup 0 --lanes 1 --full --no-cpu-baseline --no-t-total \
+      --extra-out "$OUT/${2}_bench_under_rocprof_extra.json" 2>/dev/null | tail -1 > "$OUT/${2}_bench_under_rocprof.json" || return 1
   f=$(find /tmp/prof_kt -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$OUT/${2}_rocprofv3_kernel_stats.csv" <<'PY'
 import csv, sys
@@ -38,7 +42,7 @@ PY
 pmc_passes() {   # $1 = workload, $2 = output file
   for C in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU; do
     rm -rf /tmp/prof_$C
-    rocprofv3 --pmc $C --output-format csv -d /tmp/prof_$C -o bench -- $BENCH --workload $1 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-t-total --extra-out /tmp/extra_$C.json > /dev/null 2>&1
+    $LIMIT rocprofv3 --pmc $C --output-format csv -d /tmp/prof_$C -o bench -- $BENCH --workload $1 --steps 1 --warmup 0 --lanes 1 --no-cpu-baseline --no-t-total --extra-out /tmp/extra_$C.json > /dev/null 2>&1 || return 1
   done
   python3 - "$2" "$ROOT" "$COMMIT" "$1" <<'PY'
 import csv, glob, json, sys, collections
@@ -69,25 +73,25 @@ PY
 
 for PART in $PARTS; do
   case $PART in
-    trace) kernel_trace lot-2x500-os1-64-3res "${TAG}" ;;
+    trace) kernel_trace lot-2x500-os1-64-3res "${TAG}" || exit 1 ;;
     pmc)
-      pmc_passes lot-2x500-os1-64-3res "$OUT/pmc_latest.json"
+      pmc_passes lot-2x500-os1-64-3res "$OUT/pmc_latest.json" || exit 1
       cp "$OUT/pmc_latest.json" "$OUT/${TAG}_pmc.json"
       cp "$OUT/pmc_latest.json" "$ROOT/profiles/pmc_latest.json" ;;
     line)
       # the default bench line exactly as the driver runs it, after the counter passes so that it carries `traffic` and the VALU figures of THIS kernel source
-      ( cd "$ROOT" && python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --extra-out "$OUT/${TAG}_bench_extra.json" ) > /tmp/bench_stdout.txt 2>/tmp/bench_stderr.txt
+      ( cd "$ROOT" && $LIMIT python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --extra-out "$OUT/${TAG}_bench_extra.json" ) > /tmp/bench_stdout.txt 2>/tmp/bench_stderr.txt || exit 1
       tail -c 8000 /tmp/bench_stdout.txt | tail -1 > "$OUT/${TAG}_bench_as_driver_runs_it.json"
       python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read()); print('line bytes', len(json.dumps(d)), 'value', d['value'], 'frac', d['roofline']['frac'])" "$OUT/${TAG}_bench_as_driver_runs_it.json" ;;
     sq)
-      (cd "$ROOT" && bash tools/pmc_sq.sh) > "$OUT/${TAG}_pmc_sq.txt" 2>&1
+      (cd "$ROOT" && $LIMIT bash tools/pmc_sq.sh) > "$OUT/${TAG}_pmc_sq.txt" 2>&1 || exit 1
       [ -x "$ROOT/tools/ubench/valu_rate" ] && "$ROOT/tools/ubench/valu_rate" > "$OUT/${TAG}_valu_rate_ubench.txt" 2>&1 ;;
     w:*)
       W=${PART#w:}
-      kernel_trace "$W" "${TAG}_${W}"
-      pmc_passes "$W" "$OUT/pmc_${W}.json"
+      kernel_trace "$W" "${TAG}_${W}" || exit 1
+      pmc_passes "$W" "$OUT/pmc_${W}.json" || exit 1
       cp "$OUT/pmc_${W}.json" "$ROOT/profiles/pmc_${W}.json"
-      ( cd "$ROOT" && python3 bench.py --workload "$W" --steps 2 --warmup 1 --full --extra-out "$OUT/${TAG}_bench_${W}_extra.json" ) 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_${W}.json" ;;
+      ( cd "$ROOT" && $LIMIT python3 bench.py --workload "$W" --steps 2 --warmup 1 --full --extra-out "$OUT/${TAG}_bench_${W}_extra.json" ) 2>/dev/null | tail -1 > "$OUT/${TAG}_bench_${W}.json" ;;
   esac
 done
 ls -la "$OUT"

@@ -32,12 +32,23 @@ def main():
             body = [l.split()[0] for l in lines[i:end] if l.strip() and not l.strip().startswith(";") and not l.startswith((".", "_")) and l.split()]
             valu = [b for b in body if b.startswith("v_")]
             meta = {}
-            for l in lines[end:end + 400]:
+            k0 = next((j for j, l in enumerate(lines) if l.strip() == ".amdhsa_kernel " + name), None)      # the descriptor block is not next to the code
+            for l in (lines[k0:k0 + 400] if k0 is not None else []):
                 m = re.match(r"\s*\.amdhsa_(next_free_vgpr|next_free_sgpr|group_segment_fixed_size|private_segment_fixed_size)\s+(\d+)", l)
                 if m:
                     meta[m.group(1)] = int(m.group(2))
                 if "end_amdhsa_kernel" in l:
                     break
+            # the per-workgroup prologue: VALU instructions before the first barrier, and from there to the first point's v_rsq_f32
+            bar = next((j for j, b in enumerate(body) if b == "s_barrier"), len(body))
+            rsq = next((j for j, b in enumerate(body) if j > bar and b.startswith("v_rsq_f32")), len(body))
+            bar2 = next((j for j, b in enumerate(body) if j > bar and b == "s_barrier"), len(body))
+            count = lambda seg, pre: sum(b.startswith(pre) for b in seg)
+            meta["valu_before_first_barrier"] = count(body[:bar], "v_")
+            meta["valu_first_barrier_to_first_rsq"] = count(body[bar:rsq], "v_")
+            meta["valu_first_to_second_barrier"] = count(body[bar:bar2], "v_")
+            meta["v_rcp_iflag"] = count(body, "v_rcp_iflag"); meta["v_div_scale"] = count(body, "v_div_scale")
+            meta["v_writelane"] = count(body, "v_writelane"); meta["v_readlane"] = count(body, "v_readlane")
             mix = collections.Counter(re.sub(r"_e(32|64)$", "", v) for v in valu).most_common(12)
             print(f"{name[:90]}\n  VALU {len(valu)}  SALU {sum(b.startswith('s_') for b in body)}  LDS {sum(b.startswith('ds_') for b in body)}  "
                   f"global {sum(b.startswith('global_') for b in body)}  loops {sum('Loop Header' in l for l in lines[i:end])}  {meta}\n  {mix}")
