@@ -10,8 +10,8 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vect
 all: hip oracle host
 
 hip: $(PKG)/libltm_hip.so
-# kernels by stage (projection + vote, streaming helpers, voxel grid, kNN, search index, scan context, ICP, loop submaps), one translation unit each, then the C ABI
-KOBJ = $(PKG)/csrc/ltm_k_projection.o $(PKG)/csrc/ltm_k_stream.o $(PKG)/csrc/ltm_k_voxel.o $(PKG)/csrc/ltm_k_knn.o $(PKG)/csrc/ltm_k_search.o $(PKG)/csrc/ltm_k_scancontext.o $(PKG)/csrc/ltm_k_icp.o $(PKG)/csrc/ltm_k_submap.o
+# kernels by stage (projection + vote, streaming helpers, voxel grid, kNN, search index, scan context, ICP, loop submaps, normals), one translation unit each, then the C ABI
+KOBJ = $(PKG)/csrc/ltm_k_projection.o $(PKG)/csrc/ltm_k_stream.o $(PKG)/csrc/ltm_k_voxel.o $(PKG)/csrc/ltm_k_knn.o $(PKG)/csrc/ltm_k_search.o $(PKG)/csrc/ltm_k_scancontext.o $(PKG)/csrc/ltm_k_icp.o $(PKG)/csrc/ltm_k_submap.o $(PKG)/csrc/ltm_k_normals.o
 $(PKG)/csrc/ltm_k_%.o: $(PKG)/csrc/ltm_k_%.hip $(PKG)/csrc/ltm_kernels_common.h $(PKG)/csrc/ltm_kernels.h $(PKG)/csrc/ltm_device_math.h $(PKG)/csrc/ltm_device_prims.h $(PKG)/csrc/ltm_search_walk.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 AOBJ = $(PKG)/csrc/ltm_api_core.o $(PKG)/csrc/ltm_api_vote.o $(PKG)/csrc/ltm_api_voxel.o $(PKG)/csrc/ltm_api_knn.o $(PKG)/csrc/ltm_api_search.o $(PKG)/csrc/ltm_api_scancontext.o $(PKG)/csrc/ltm_api_icp.o $(PKG)/csrc/ltm_api_submap.o

@@ -307,6 +307,41 @@ int ltm_search_result_info(ltm_ctx*, ltm_search_result*, size_t* n_query, size_t
                            const uint64_t** offsets_dev, const int32_t** idx_dev, const float** d2_dev);
 int ltm_search_result_free(ltm_ctx*, ltm_search_result*);
 
+/* ---------------------------------------------------------------- normals ---- */
+/* pcl::NormalEstimation (setKSearch(k), setViewPoint(vx, vy, vz), compute) over the target of a search index: one (nx, ny, nz, curvature) per target
+ * point.  The reference calls neither NormalEstimation nor a method that needs normals; PCL is not available to compare against.  This is the arithmetic
+ * this library takes PCL 1.10's NormalEstimation (computePointNormal, flipNormalTowardsViewpoint) to do, as understood; tools/normals_numpy.py restates it
+ * in numpy and the tests compare against that.
+ *  - Neighbourhood of a finite target point: its min(k, n_finite) nearest target points, ITSELF INCLUDED at distance 0, in ltm_knn_search order
+ *    (L2_Simple in float, ties to the smaller target index).  3 <= k <= 64, anything else is LTM_E_INVALID.
+ *  - Fewer than 3 neighbours (a target with fewer than 3 finite points): normal and curvature are NaN (computePointNormal returns false there).
+ *  - Covariance, in double: with d_i = (double)q_i - (double)p the neighbours as differences from the point p itself, summed in the neighbourhood's
+ *    ascending (d2, index) order, m = sum d_i / n, C = sum d_i d_i^T / n - m m^T.
+ *  - Normal: the eigenvector of the smallest eigenvalue of C (the lower axis among equal eigenvalues) by cyclic Jacobi rotations in double, normalised to
+ *    unit length; CANONICAL SIGN: the component of largest magnitude is made positive (the lower axis among equals); then flipNormalTowardsViewpoint:
+ *    negated if ((vx - px) nx + (vy - py) ny) + (vz - pz) nz < 0, evaluated in double; then rounded to float.
+ *  - Curvature: lambda_min / (lambda_0 + lambda_1 + lambda_2) in double, rounded to float; negative rounding residue of lambda_min is clamped to 0, and a
+ *    trace that is not positive gives 0.
+ *  - Degenerate neighbourhoods: when the two smallest eigenvalues coincide (collinear or coincident neighbours) the direction is not unique; the normal is
+ *    then only promised to be finite, of unit length, and reproducible.
+ *  - Target points with a non-finite coordinate are not in the index: they are nobody's neighbour and ltm_search_normals_download writes NaN to all four
+ *    of their fields.
+ *  DEPARTURES from PCL: PCL accumulates the nine raw moments in float about the origin and takes the eigenvector with the closed-form eigen33; here the
+ *  moments are doubles about the point itself and the eigenvector comes from Jacobi rotations, so map coordinates kilometres from zero lose nothing.  PCL
+ *  leaves the sign before the viewpoint flip to eigen33; here it is canonical.  PCL's curvature divides by the trace of the float covariance.
+ * ltm_search_estimate_normals estimates the normals of ALL listed indices with one k in one kernel launch (viewpoints3_or_null: n_idx x 3 floats, NULL =
+ * (0, 0, 0) for every index) and reads nothing back.  The normals live with the index: one float4 per finite target point in the index's own order, in ONE
+ * pool block per call that the handles of the call share; it goes back to the pool when the last of them is freed or estimated again (a second estimate
+ * replaces the first).  Handles of ltm_search_build and of ltm_search_build_scanset may be mixed; the same handle twice in one call, a handle of another
+ * context, a non-finite viewpoint: LTM_E_INVALID, and every index stays as it was. */
+int ltm_search_estimate_normals(ltm_ctx*, size_t n_idx, ltm_search* const* idx, int k,
+                                const float* viewpoints3_or_null /* n_idx x 3, NULL = (0,0,0) for all */);
+/* k the normals were estimated with (0 = none) and the device array (n_finite float4 in the index's order; NULL without normals or finite points), borrowed
+ * until the index is freed or estimated again */
+int ltm_search_normals_info(ltm_ctx*, ltm_search*, int* k /* 0 = none */, const void** normals_dev /* borrowed */);
+/* (nx, ny, nz, curvature) of every target point in the target's ORIGINAL order; an index without normals is LTM_E_INVALID */
+int ltm_search_normals_download(ltm_ctx*, ltm_search*, float* nxyzc_host /* n_target x 4, the target's ORIGINAL order */);
+
 /* ----------------------------------------------------------- scan context ---- */
 /* Scan Context place recognition, the step of the reference that decides which keyframes of two sessions see the same place before LT-removert diffs
  * them: SCManager (ltslam/src/Scancontext.cpp:69-324, ltslam/include/ltslam/Scancontext.h:58-121) as LTslam::detectInterSessionSCloops drives it
@@ -409,7 +444,7 @@ int  ltm_sc_free(ltm_ctx*, ltm_sc*);
  *  another context is LTM_E_INVALID).  init16_or_null: n_pairs row-major 4x4 doubles whose last row is taken to be 0 0 0 1, NULL = identity.  A NULL
  *  parameter pointer means the defaults.  Each source (< 2^31 points, < 2^31 in all) is copied in sorted order for the call; all device memory comes from
  *  the context's pool and is back when the call returns, on every error path too.  The call returns when the host arrays are written.
- *  The submaps themselves come from the section "loop submaps" below.  Out of scope: Euler / gtsam::Pose3 conversions, point-to-plane and generalized ICP. */
+ *  The submaps themselves come from the section "loop submaps" below.  Point-to-plane ICP is the next section.  Out of scope: Euler / gtsam::Pose3 conversions and generalized ICP. */
 typedef struct {
     double max_corr_dist;             /* 150.0  setMaxCorrespondenceDistance, LTslam.cpp:207 */
     int    max_iterations;            /* 100    :208 */
@@ -422,7 +457,8 @@ typedef struct {
     double   last_mse;       /* mean squared correspondence distance of the last iteration */
     int32_t  converged;      /* hasConverged() */
     int32_t  iterations;
-    int32_t  state;          /* why it stopped: 0 too few correspondences / nothing to do, 1 iterations, 2 transform, 3 absolute MSE, 4 relative MSE */
+    int32_t  state;          /* why it stopped: 0 too few correspondences / nothing to do, 1 iterations, 2 transform, 3 absolute MSE, 4 relative MSE;
+                                point-to-plane only: 5 degenerate system */
     uint32_t n_corr;         /* correspondences of the last iteration */
 } ltm_icp_result;
 void ltm_icp_default_params(ltm_icp_params*);     /* host only, needs no device */
@@ -433,6 +469,35 @@ int  ltm_icp_align(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, const l
  * no copy per pair; a keyframe outside the set is LTM_E_INVALID.  Results are those of ltm_icp_align on ltm_scanset_keyframe of the same keyframes, bit for bit. */
 int  ltm_icp_align_scanset(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf /* n_pairs */,
                            const double* init16_or_null, const ltm_icp_params*, ltm_icp_result* results_host, double* trace_host_or_null);
+
+/* ------------------------------------------------- icp, point-to-plane ---- */
+/* The same batch with the point-to-plane error: pcl::IterativeClosestPointWithNormals (TransformationEstimationPointToPlaneLLS), as understood; the
+ * reference does not call it.  Arguments, ltm_icp_params, ltm_icp_result and the trace are those of ltm_icp_align / ltm_icp_align_scanset; every target
+ * must carry normals (ltm_search_estimate_normals), else LTM_E_INVALID.  Two kernel launches per iteration for the whole batch.  tools/icp_plane_numpy.py
+ * restates the arithmetic below and the tests compare against it.
+ *  Steps 1-3 of an iteration (transform of the ORIGINAL source in double -> float query, exact 1-NN, distance limit), the stop tests, mse, fitness, the
+ *  trace and the edge cases are those of the section "icp", unchanged.  Then:
+ *   4. a kept correspondence whose target normal is not finite is DROPPED: it counts neither in n_corr nor in the mse;
+ *   5. fewer than 3 correspondences: the pair stops, converged = 0, state = 0, as in "icp";
+ *   6. linear system: with the query p, its target point q and the target point's normal n as doubles, p and q taken about the pair's origin o (the corner
+ *      of the target's bounding box), every correspondence gives the row a = [p x n, n] and the right side b = n . (q - p).  A^T A (21 entries), A^T b (6),
+ *      the count and the sum of d2 are accumulated in double in the fixed order of "icp" (256 source points per partial sum, partial sums in order);
+ *   7. solve (A^T A) x = A^T b by Cholesky in double WITHOUT pivoting.  A diagonal entry (A^T A)_jj that is not positive or a pivot
+ *      d_j <= 1e-12 (A^T A)_jj stops the pair: converged = 0, state = 5 ("degenerate system", these entry points only), T and `iterations` stay as they
+ *      are, n_corr / last_mse / the trace row record what was found.  The threshold is relative to the entry's own scale, so the mixed units of rotation
+ *      and translation do not matter; a single exact plane gives exact zeros on three diagonal entries;
+ *   8. x = (alpha, beta, gamma, t'): R = Rz(gamma) Ry(beta) Rx(alpha), entry by entry as PCL's constructTransformationMatrix has it,
+ *        R00 = cg cb    R01 = -sg ca + cg sb sa    R02 =  sg sa + cg sb ca
+ *        R10 = sg cb    R11 =  cg ca + sg sb sa    R12 = -cg sa + sg sb ca
+ *        R20 = -sb      R21 =  cb sa               R22 =  cb ca              (sa = sin alpha, ca = cos alpha, ...)
+ *      t = t' + o - R o;  T <- [R t] T;  iterations += 1;  the stop tests of "icp" with this R and t.
+ *  DEPARTURES from PCL, beyond those of "icp": the system is formed about o and not about the coordinate origin.  The linearised problem is the same
+ *  about any origin; the nonlinear R applied about o differs from PCL's in the second order of the angles only (t = t' + o - R o instead of t').  PCL
+ *  solves with Eigen's inverse(); here Cholesky, and a system that does not determine all six unknowns is reported (state 5) instead of solved. */
+int  ltm_icp_align_plane(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources,
+                         const double* init16_or_null, const ltm_icp_params*, ltm_icp_result* results_host, double* trace_host_or_null);
+int  ltm_icp_align_plane_scanset(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf /* n_pairs */,
+                                 const double* init16_or_null, const ltm_icp_params*, ltm_icp_result* results_host, double* trace_host_or_null);
 
 /* ----------------------------------------------------------- loop submaps ---- */
 /* The step between a loop proposal and its ICP verification: the two clouds of every ICP run of LTslam::doICPVirtualRelative / doICPGlobalRelative

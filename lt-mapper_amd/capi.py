@@ -43,7 +43,8 @@ class IcpParams(C.Structure):
 # ltm_icp_result as a numpy record (the C layout: 160 bytes)
 ICP_RESULT = np.dtype([("T", np.float64, (4, 4)), ("fitness", np.float64), ("last_mse", np.float64), ("converged", np.int32),
                        ("iterations", np.int32), ("state", np.int32), ("n_corr", np.uint32)], align=True)
-ICP_STATES = ("too few correspondences", "iterations", "transform", "absolute mse", "relative mse")
+ICP_STATES = ("too few correspondences", "iterations", "transform", "absolute mse", "relative mse", "degenerate system")
+ICP_METHODS = ("point", "plane")
 
 
 # name -> (restype, argtypes); kept in one table so tests can check it against include/ltm.h
@@ -136,6 +137,9 @@ SIGNATURES = {
     "ltm_radius_search": (_i, [_vp, _vp, _u64, _f, _i, C.POINTER(_vp)]),
     "ltm_search_result_info": (_i, [_vp, _vp, _psz, _psz, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "ltm_search_result_free": (_i, [_vp, _vp]),
+    "ltm_search_estimate_normals": (_i, [_vp, _sz, C.POINTER(_vp), _i, _vp]),
+    "ltm_search_normals_info": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_vp)]),
+    "ltm_search_normals_download": (_i, [_vp, _vp, _vp]),
     "ltm_sc_default_params": (None, [C.POINTER(ScParams)]),
     "ltm_sc_from_scanset": (_i, [_vp, _u64, _sz, _sz, C.POINTER(ScParams), C.POINTER(_vp)]),
     "ltm_sc_from_descriptors": (_i, [_vp, _vp, _sz, C.POINTER(ScParams), C.POINTER(_vp)]),
@@ -147,6 +151,8 @@ SIGNATURES = {
     "ltm_icp_default_params": (None, [C.POINTER(IcpParams)]),
     "ltm_icp_align": (_i, [_vp, _sz, C.POINTER(_vp), _pu64, _vp, C.POINTER(IcpParams), _vp, _vp]),
     "ltm_icp_align_scanset": (_i, [_vp, _sz, C.POINTER(_vp), _u64, _vp, _vp, C.POINTER(IcpParams), _vp, _vp]),
+    "ltm_icp_align_plane": (_i, [_vp, _sz, C.POINTER(_vp), _pu64, _vp, C.POINTER(IcpParams), _vp, _vp]),
+    "ltm_icp_align_plane_scanset": (_i, [_vp, _sz, C.POINTER(_vp), _u64, _vp, _vp, C.POINTER(IcpParams), _vp, _vp]),
     "ltm_pose6d_to_affine3f": (_i, [_vp, _sz, _vp]),
     "ltm_submaps_assemble": (_i, [_vp, _u64, _vp, _vp, _sz, _i, _f, _i, _pu64]),
     "ltm_search_build_scanset": (_i, [_vp, _u64, _sz, _sz, C.POINTER(_vp)]),
@@ -555,6 +561,26 @@ class Context:
         self._ck(self.lib.ltm_search_build_scanset(self.h, scanset.h, kf_begin, ke, hs))
         return [SearchIndex(self, hs[i]) for i in range(n)]
 
+    def estimate_normals(self, indices, k=10, viewpoints=None):
+        """ltm_search_estimate_normals: pcl::NormalEstimation (setKSearch(k), setViewPoint) over the targets of all `indices` (SearchIndex objects of this
+        context, each at most once) in one launch; viewpoints: (n, 3) or None = the origin for all.  The normals stay with the indices
+        (SearchIndex.normals downloads them, icp_align(method="plane") uses them)."""
+        indices = list(indices)
+        k = _normals_k(k)
+        for x in indices:
+            if not isinstance(x, SearchIndex):
+                raise TypeError("estimate_normals takes SearchIndex objects (Context.search_index)")
+        if len({id(x) for x in indices}) != len(indices):
+            raise ValueError("an index is listed twice")
+        n = len(indices)
+        vp = None
+        if viewpoints is not None:
+            vp = np.ascontiguousarray(viewpoints, dtype=np.float32).reshape(-1)
+            if vp.size != 3 * n:
+                raise ValueError("one viewpoint (x, y, z) per index")
+        hs = (_vp * max(n, 1))(*[x.h for x in indices])
+        self._ck(self.lib.ltm_search_estimate_normals(self.h, n, hs, k, None if vp is None else vp.ctypes.data))
+
     # ---- loop submaps
     def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
         """ltm_submaps_assemble: Session::loopFindNearKeyframesLocalCoord (affines=None) / CentralCoord (affines: (n_kf, 3, 4) float32, see
@@ -573,12 +599,17 @@ class Context:
         return ScanSet(self, out.value)
 
     def verify_loops(self, target_scans, source_scans, pairs, target_affines=None, source_affines=None, search_num=25, leaf=0.3,
-                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, **icp):
+                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, method="point", normal_k=10, **icp):
         """The body of LTslam::addSCloops' loop (LTslam.cpp:370-416) for all `pairs` = (target key, source key): the target submap (+-search_num
         keyframes) and its search index are made ONCE per distinct target key, the source submap is the source keyframe alone (searchNum = 0), every
         source is aligned to its target by icp_align, and a pair is accepted iff converged and fitness <= fitness_threshold (loopFitnessScoreThreshold,
         0.5 by default: ltslam/src/RosParamServer.cpp:23).  The work is cut into batches of consecutive pairs whose submaps hold at most max_batch_points
-        points before the grid (estimated from the scan sets' offsets).  Returns (ICP_RESULT records, accept mask), one entry per pair."""
+        points before the grid (estimated from the scan sets' offsets).  method="plane" verifies with point-to-plane ICP: the normals of each batch of
+        target indices are estimated in one call (normal_k neighbours), the viewpoint at the key keyframe's translation (the origin without affines).
+        Returns (ICP_RESULT records, accept mask), one entry per pair."""
+        method = _icp_method(method)
+        if method == "plane":
+            normal_k = _normals_k(normal_k)
         pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
         res = np.zeros(len(pairs), dtype=ICP_RESULT)
         t_off = target_scans.offsets().astype(np.int64)
@@ -607,7 +638,12 @@ class Context:
             ssub = self.loop_submaps(source_scans, [int(pairs[i, 1]) for i in b], 0, leaf, source_affines, order)
             idx = self.search_index_batch(tsub)
             try:
-                res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], (ssub, j)) for j, i in enumerate(b)], **icp)
+                if method == "plane":
+                    vp = None
+                    if target_affines is not None:
+                        vp = np.asarray(target_affines, dtype=np.float32).reshape(-1, 3, 4)[tkeys, :, 3]
+                    self.estimate_normals(idx, normal_k, vp)
+                res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], (ssub, j)) for j, i in enumerate(b)], method=method, **icp)
             finally:
                 for x in idx:
                     x.close()
@@ -634,13 +670,17 @@ class Context:
         return ScanContexts(self, h.value, p)
 
     # ---- icp
-    def icp_align(self, pairs, init=None, trace=False, **params):
-        """ltm_icp_align: point-to-point ICP of every (target, source) of `pairs` in one batch -- target a SearchIndex of this context (one index
+    def icp_align(self, pairs, init=None, trace=False, method="point", **params):
+        """ltm_icp_align (method="point", the default) / ltm_icp_align_plane (method="plane": every target must carry normals, see estimate_normals;
+        state 5 = degenerate system): ICP of every (target, source) of `pairs` in one batch -- target a SearchIndex of this context (one index
         may serve many pairs), source a Cloud of this context, an (n, 3) / (n, 4) array or (ScanSet, keyframe) -- when every source is a keyframe of one
         ScanSet they are read in place (ltm_icp_align_scanset).  init: (n, 4, 4) source->target start transforms
         (None: identity); params: the fields of ltm_icp_params, the reference's values by default.  Returns a record array of dtype ICP_RESULT
         (T, fitness, last_mse, converged, iterations, state, n_corr), one record per pair; with trace=True also the (n, max_iterations, 2)
         array of (n_corr, mse) per iteration, NaN where no iteration ran."""
+        plane = _icp_method(method) == "plane"
+        align_clouds = self.lib.ltm_icp_align_plane if plane else self.lib.ltm_icp_align
+        align_scanset = self.lib.ltm_icp_align_plane_scanset if plane else self.lib.ltm_icp_align_scanset
         p = icp_params(**params)
         pairs = list(pairs)
         n = len(pairs)
@@ -661,7 +701,7 @@ class Context:
                 if all(in_set) and all(s_[0] is pairs[0][1][0] for _, s_ in pairs):
                     # every source a keyframe of ONE scan set (the submaps of loop_submaps): read in place
                     kf = np.ascontiguousarray([s_[1] for _, s_ in pairs], dtype=np.uint32)
-                    self._ck(self.lib.ltm_icp_align_scanset(self.h, n, th, pairs[0][1][0].h, kf.ctypes.data, None if i16 is None else i16.ctypes.data,
+                    self._ck(align_scanset(self.h, n, th, pairs[0][1][0].h, kf.ctypes.data, None if i16 is None else i16.ctypes.data,
                                                             C.byref(p), res.ctypes.data, tr.ctypes.data if trace and tr.size else None))
                     return (res, tr) if trace else res
                 src = []
@@ -674,7 +714,7 @@ class Context:
                         made.append(s_)
                     src.append(s_)
                 sh = (C.c_uint64 * n)(*[s_.h for s_ in src])
-                self._ck(self.lib.ltm_icp_align(self.h, n, th, sh, None if i16 is None else i16.ctypes.data, C.byref(p), res.ctypes.data,
+                self._ck(align_clouds(self.h, n, th, sh, None if i16 is None else i16.ctypes.data, C.byref(p), res.ctypes.data,
                                                 tr.ctypes.data if trace and tr.size else None))
             finally:
                 for s_ in made:
@@ -858,6 +898,22 @@ class SearchIndex:
             self.ctx.lib.ltm_search_result_free(self.ctx.h, res)
         return off, idx, d2
 
+    def estimate_normals(self, k=10, viewpoint=None):
+        """ltm_search_estimate_normals for this index alone: setKSearch(k), setViewPoint(*viewpoint) (None: the origin), compute"""
+        self.ctx.estimate_normals([self], k, None if viewpoint is None else np.asarray(viewpoint, dtype=np.float32).reshape(1, 3))
+
+    def normals_k(self):
+        """k of the normals the index carries, 0 if none"""
+        k, p = _i(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_search_normals_info(self.ctx.h, self.h, C.byref(k), C.byref(p)))
+        return k.value
+
+    def normals(self):
+        """ltm_search_normals_download: (n_target, 4) float32 (nx, ny, nz, curvature) in the target's original order; NaN rows for non-finite points"""
+        out = np.empty((self.info()[0], 4), np.float32)
+        self.ctx._ck(self.ctx.lib.ltm_search_normals_download(self.ctx.h, self.h, out.ctypes.data))
+        return out
+
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.ltm_search_free(self.ctx.h, self.h)
@@ -874,6 +930,19 @@ class SearchIndex:
             self.close()
         except Exception:
             pass
+
+
+def _icp_method(method):
+    if method not in ICP_METHODS:
+        raise ValueError(f"method must be one of {ICP_METHODS}, not {method!r}")
+    return method
+
+
+def _normals_k(k):
+    k = int(k)
+    if not 3 <= k <= 64:
+        raise ValueError("k must be in [3, 64]")
+    return k
 
 
 def icp_params(**over):

@@ -1,6 +1,6 @@
-// ltm_api_icp.cpp -- C ABI: batched point-to-point ICP of source clouds against search indices, the counterpart of the pcl::IterativeClosestPoint runs
+// ltm_api_icp.cpp -- C ABI: batched point-to-point and point-to-plane ICP of source clouds against search indices, the counterpart of the pcl::IterativeClosestPoint runs
 // of LTslam::doICPVirtualRelative / doICPGlobalRelative (ltslam/src/LTslam.cpp:187-301) for all the pairs of addSCloops / addRSloops (:370-416, :508-560)
-// at once.  Kernels in ltm_k_icp.hip; the arithmetic is stated in include/ltm.h, "icp".
+// at once.  Kernels in ltm_k_icp.hip; the arithmetic is stated in include/ltm.h, "icp" and "icp, point-to-plane" (one driver, the method is a switch).
 #include "ltm_internal.h"
 
 namespace {
@@ -23,7 +23,7 @@ void check_params(const ltm_icp_params& p)
 // the routine behind both entry points: source_of(i) names the points of pair i's source (a cloud, or a keyframe of a scan set read in place)
 struct IcpSource { const float4* d; size_t n; };
 template <class SourceOf>
-void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, SourceOf&& source_of, const double* init16, const ltm_icp_params* params,
+void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* targets, SourceOf&& source_of, const double* init16, const ltm_icp_params* params,
                     ltm_icp_result* results, double* trace)
 {
     ltm_icp_params prm;
@@ -47,6 +47,11 @@ void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, Sour
         IcpPair& P = pairs[i];
         memset(&P, 0, sizeof P);
         search_view(c, targets[i], &P.t, &P.f);
+        if (plane) {
+            int nk = 0;
+            P.nrm = search_normals(c, targets[i], &nk);
+            LTM_REQUIRE(nk != 0, "a target has no normals (ltm_search_estimate_normals)");
+        }
         const IcpSource src = source_of(i);
         LTM_REQUIRE(src.n < 0x80000000ull, "a source must have fewer than 2^31 points");
         const bool run = src.n && P.t.Mf && max_it >= 1;
@@ -75,7 +80,7 @@ void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, Sour
 
     if (active) {
         DevBuf d_pairs(c, n_pairs * sizeof(IcpPair)), d_st(c, n_pairs * sizeof(IcpState)), d_off(c, (n_pairs + 1) * 8), d_bp(c, (size_t)n_blocks * 4);
-        DevBuf d_sorted(c, total * sizeof(float4)), d_part(c, (size_t)n_blocks * kIcpPartial * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
+        DevBuf d_sorted(c, total * sizeof(float4)), d_part(c, (size_t)n_blocks * (plane ? kIcpPlanePartial : kIcpPartial) * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
         h2d(c, d_pairs.p, pairs.data(), n_pairs * sizeof(IcpPair));
         h2d(c, d_st.p, st.data(), n_pairs * sizeof(IcpState));
         h2d(c, d_off.p, off.data(), (n_pairs + 1) * 8);
@@ -103,9 +108,9 @@ void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, Sour
                 ProfScope ps(c, "icp_iter", (double)total * chunk, 16.0 * (double)total * chunk, -1.0, false);
                 if (ps.cls >= 0) c->prof[ps.cls].launches += 2 * (uint64_t)chunk;
                 for (int k = 0; k < chunk; ++k) {
-                    LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), max2, 0, d_part.as<double>(), c->stream));
+                    LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), max2, plane ? kIcpPlane : kIcpPoint, d_part.as<double>(), c->stream));
                     LTM_HIP(icp_update(dp, ds, n_pairs, d_part.as<double>(), max_it, prm.transformation_epsilon, prm.euclidean_fitness_epsilon,
-                                       trace_n ? d_trace.as<double>() : nullptr, d_unf.as<uint32_t>(), c->stream));
+                                       trace_n ? d_trace.as<double>() : nullptr, d_unf.as<uint32_t>(), c->stream, plane ? 1 : 0));
                 }
             }
             it += chunk;
@@ -117,7 +122,7 @@ void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, Sour
         {
             ProfScope ps(c, "icp_fitness", (double)total, 16.0 * (double)total, -1.0, false);
             if (ps.cls >= 0) c->prof[ps.cls].launches += 2;
-            LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), 0.0, 1, d_part.as<double>(), c->stream));
+            LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), 0.0, kIcpScore, d_part.as<double>(), c->stream));
             LTM_HIP(icp_fitness(dp, ds, n_pairs, d_part.as<double>(), c->stream));
         }
         d2h(c, st.data(), d_st.p, n_pairs * sizeof(IcpState));
@@ -137,6 +142,28 @@ void icp_align_impl(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, Sour
     }
 }
 
+// the two forms of the sources, shared by both methods
+int align_clouds(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16,
+                 const ltm_icp_params* params, ltm_icp_result* results, double* trace)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(!n_pairs || sources, "null argument");
+        icp_align_impl(c, plane, n_pairs, targets, [&](size_t i) { const Cloud& src = get_cloud(c, sources[i]); return IcpSource{src.d, src.n}; }, init16, params, results, trace);
+    });
+}
+int align_scanset(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
+                  const ltm_icp_params* params, ltm_icp_result* results, double* trace)
+{
+    return guarded(c, [&] {
+        const ScanSet& ss = get_ss(c, sources);
+        LTM_REQUIRE(!n_pairs || source_kf, "null argument");
+        icp_align_impl(c, plane, n_pairs, targets, [&](size_t i) {
+            LTM_REQUIRE(source_kf[i] < ss.nkf(), "source keyframe out of range");
+            return IcpSource{ss.d + ss.off[source_kf[i]], (size_t)(ss.off[source_kf[i] + 1] - ss.off[source_kf[i]])};
+        }, init16, params, results, trace);
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -153,23 +180,25 @@ void ltm_icp_default_params(ltm_icp_params* p)
 int ltm_icp_align(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16, const ltm_icp_params* params,
                   ltm_icp_result* results, double* trace)
 {
-    return guarded(c, [&] {
-        LTM_REQUIRE(!n_pairs || sources, "null argument");
-        icp_align_impl(c, n_pairs, targets, [&](size_t i) { const Cloud& src = get_cloud(c, sources[i]); return IcpSource{src.d, src.n}; }, init16, params, results, trace);
-    });
+    return align_clouds(c, false, n_pairs, targets, sources, init16, params, results, trace);
 }
 
 int ltm_icp_align_scanset(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
                           const ltm_icp_params* params, ltm_icp_result* results, double* trace)
 {
-    return guarded(c, [&] {
-        const ScanSet& ss = get_ss(c, sources);
-        LTM_REQUIRE(!n_pairs || source_kf, "null argument");
-        icp_align_impl(c, n_pairs, targets, [&](size_t i) {
-            LTM_REQUIRE(source_kf[i] < ss.nkf(), "source keyframe out of range");
-            return IcpSource{ss.d + ss.off[source_kf[i]], (size_t)(ss.off[source_kf[i] + 1] - ss.off[source_kf[i]])};
-        }, init16, params, results, trace);
-    });
+    return align_scanset(c, false, n_pairs, targets, sources, source_kf, init16, params, results, trace);
+}
+
+int ltm_icp_align_plane(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16, const ltm_icp_params* params,
+                        ltm_icp_result* results, double* trace)
+{
+    return align_clouds(c, true, n_pairs, targets, sources, init16, params, results, trace);
+}
+
+int ltm_icp_align_plane_scanset(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
+                                const ltm_icp_params* params, ltm_icp_result* results, double* trace)
+{
+    return align_scanset(c, true, n_pairs, targets, sources, source_kf, init16, params, results, trace);
 }
 
 } // extern "C"

@@ -10,9 +10,21 @@ struct SearchBatch {
     ~SearchBatch() { for (void* b : blocks) c->pool.free(b); }
     SearchBatch(const SearchBatch&) = delete; SearchBatch& operator=(const SearchBatch&) = delete;
 };
+// the pool block that holds the normals of the indices of one ltm_search_estimate_normals: back in the pool when the last of them is released or
+// estimated again
+struct NormalsBlock {
+    ltm_ctx* c;
+    void* p;
+    NormalsBlock(ltm_ctx* c_, size_t bytes) : c(c_), p(c_->pool.alloc(bytes)) {}
+    ~NormalsBlock() { c->pool.free(p); }
+    NormalsBlock(const NormalsBlock&) = delete; NormalsBlock& operator=(const NormalsBlock&) = delete;
+};
 struct ltm_search {
     ltm_ctx* owner = nullptr;
     std::shared_ptr<SearchBatch> batch;   // set: pts / idx / keys / box point into the batch's blocks
+    std::shared_ptr<NormalsBlock> nblock; // set: normals points into it
+    float4* normals = nullptr;            // (nx, ny, nz, curvature) of pts[j], Mf of them
+    int normals_k = 0;                    // 0: none estimated
     size_t n_target = 0;
     uint32_t Mf = 0, L = 0, P = 0;      // finite points, leaves, leaves rounded up to a power of two
     SearchFrame f{};
@@ -194,7 +206,96 @@ void ltm_detail::search_view(ltm_ctx* c, ltm_search* s, SearchTree* tree, Search
     *frame = s->f;
 }
 
+const float4* ltm_detail::search_normals(ltm_ctx* c, ltm_search* s, int* k)
+{
+    get_search(c, s);
+    if (k) *k = s->normals_k;
+    return s->normals;
+}
+
 extern "C" {
+
+int ltm_search_estimate_normals(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, int k, const float* viewpoints3)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(k >= 3 && k <= kNormalsMaxK, "k must be in [3, 64]");
+        if (!n_idx) return;
+        LTM_REQUIRE(idx, "null argument");
+        LTM_REQUIRE(n_idx < 0x7fffffffull, "too many indices");
+        // everything is checked before anything changes: an error leaves every index as it was
+        std::vector<ltm_search*> seen(idx, idx + n_idx);
+        for (size_t i = 0; i < n_idx; ++i) get_search(c, idx[i]);
+        std::sort(seen.begin(), seen.end());
+        LTM_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "an index is listed twice");
+        const uint32_t block = (uint32_t)normals_block(k);
+        std::vector<NormalsSeg> segs(n_idx);
+        std::vector<uint32_t> block_seg;
+        uint64_t total = 0;
+        for (size_t i = 0; i < n_idx; ++i) {
+            NormalsSeg& S = segs[i];
+            memset(&S, 0, sizeof S);
+            S.t = idx[i]->tree();
+            for (int d = 0; d < 3; ++d) {
+                S.vp[d] = viewpoints3 ? (double)viewpoints3[3 * i + d] : 0.0;
+                LTM_REQUIRE(std::isfinite(S.vp[d]), "a viewpoint is not finite");
+            }
+            S.block0 = (uint32_t)block_seg.size();
+            S.pad = (uint32_t)0;
+            const uint32_t nb = (S.t.Mf + block - 1) / block;
+            LTM_REQUIRE((uint64_t)block_seg.size() + nb < 0x7fffffffull, "too many target points in one call");
+            block_seg.insert(block_seg.end(), nb, (uint32_t)i);
+            total += S.t.Mf;
+        }
+        std::shared_ptr<NormalsBlock> nb;
+        if (total) {
+            nb = std::make_shared<NormalsBlock>(c, total * sizeof(float4));
+            uint64_t at = 0;
+            for (size_t i = 0; i < n_idx; ++i) { segs[i].out = reinterpret_cast<float4*>(nb->p) + at; at += segs[i].t.Mf; }
+            const uint32_t n_blocks = (uint32_t)block_seg.size();
+            ProfScope ps(c, "normals", (double)total, (double)total * (32.0 + 16.0 * k));
+            DevBuf d_segs(c, n_idx * sizeof(NormalsSeg)), d_bs(c, (size_t)n_blocks * 4);
+            h2d(c, d_segs.p, segs.data(), n_idx * sizeof(NormalsSeg));
+            h2d(c, d_bs.p, block_seg.data(), (size_t)n_blocks * 4);
+            LTM_HIP(estimate_normals(d_segs.as<NormalsSeg>(), d_bs.as<uint32_t>(), n_blocks, k, c->stream));
+        }
+        for (size_t i = 0; i < n_idx; ++i) {
+            ltm_search* s = idx[i];
+            s->normals = segs[i].t.Mf ? segs[i].out : nullptr;
+            s->nblock = segs[i].t.Mf ? nb : nullptr;      // the block of an earlier estimate loses this reference
+            s->normals_k = k;
+        }
+    });
+}
+
+int ltm_search_normals_info(ltm_ctx* c, ltm_search* s, int* k, const void** normals_dev)
+{
+    return guarded(c, [&] {
+        get_search(c, s);
+        if (k) *k = s->normals_k;
+        if (normals_dev) *normals_dev = s->normals;
+    });
+}
+
+int ltm_search_normals_download(ltm_ctx* c, ltm_search* s, float* nxyzc_host)
+{
+    return guarded(c, [&] {
+        get_search(c, s);
+        LTM_REQUIRE(s->normals_k != 0, "the index has no normals (ltm_search_estimate_normals)");
+        if (!s->n_target) return;
+        LTM_REQUIRE(nxyzc_host, "null argument");
+        const float q = std::nanf("");
+        for (size_t i = 0; i < s->n_target * 4; ++i) nxyzc_host[i] = q;      // non-finite target points are not in the index
+        if (!s->Mf) return;
+        std::vector<float4> n(s->Mf);
+        std::vector<uint32_t> at(s->Mf);
+        d2h(c, n.data(), s->normals, (size_t)s->Mf * sizeof(float4));
+        d2h(c, at.data(), s->idx, (size_t)s->Mf * 4);
+        for (uint32_t j = 0; j < s->Mf; ++j) {
+            if (at[j] >= s->n_target) throw Err{LTM_E_DEVICE, "a position of the index is outside the target"};
+            memcpy(nxyzc_host + 4 * (size_t)at[j], &n[j], sizeof(float4));
+        }
+    });
+}
 
 int ltm_search_build(ltm_ctx* c, ltm_cloud htarget, ltm_search** out)
 {

@@ -672,6 +672,7 @@ void vgs_release_all(ltm_ctx* c);                                               
 int voxel_grid_scanset_ordered(ltm_ctx* c, ltm_scanset in, float leaf, int order, ltm_scanset* out);   // ltm_api_voxel.cpp: ltm_voxel_grid_scanset with the order as an argument (1 PCL, 0 input)
 void search_release_all(ltm_ctx* c);                                              // ltm_api_search.cpp: open search indices and results, at ltm_destroy
 void search_view(ltm_ctx* c, struct ltm_search* s, SearchTree* tree, SearchFrame* frame);   // ltm_api_search.cpp: tree and frame of an index OF THIS CONTEXT (throws otherwise)
+const float4* search_normals(ltm_ctx* c, struct ltm_search* s, int* k);             // ltm_api_search.cpp: the normals of an index of this context (aligned with its tree's pts; null and *k = 0: none)
 void sc_release_all(ltm_ctx* c);                                                  // ltm_api_scancontext.cpp: open descriptor sets, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp

@@ -1,4 +1,4 @@
-// ltm_k_icp.hip -- batched point-to-point ICP of source clouds against search indices: the counterpart of the pcl::IterativeClosestPoint runs of
+// ltm_k_icp.hip -- batched point-to-point (and point-to-plane) ICP of source clouds against search indices: the counterpart of the pcl::IterativeClosestPoint runs of
 // LTslam::doICPVirtualRelative / doICPGlobalRelative (ltslam/src/LTslam.cpp:187-301), one batch for all the loop pairs of addSCloops / addRSloops.
 // (gfx950 / CDNA4, wave64; part of libltm_hip.so -- shared definitions in ltm_kernels_common.h, launch wrappers declared in ltm_kernels.h)
 //
@@ -11,6 +11,9 @@
 // batch.  k_icp_update runs one workgroup per pair: the pair's records added in block order, the rigid transform by a one-sided Jacobi SVD of the 3 x 3
 // cross-covariance in double, T <- T_iter T, PCL's stop tests, the trace row and the done flag.  The fitness score is one more pass of the first kernel
 // in score mode (every finite point, no distance limit) and k_icp_fitness.
+// Point-to-plane (ltm_icp_align_plane; include/ltm.h "icp, point-to-plane") is a third mode of the same two kernels: the correspondence kernel reads the target
+// point's normal (ltm_k_normals.hip) and accumulates the 6 x 6 normal equations in a record of kIcpPlanePartial doubles, in the same fixed order; the update
+// kernel solves them by Cholesky (plane_step) where the point-to-point mode takes the SVD.  Everything else -- transform, 1-NN, stop tests, trace -- is shared.
 #include "ltm_kernels_common.h"
 #include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -22,8 +25,8 @@ namespace {
 
 // sums over the workgroup of NV doubles per thread, in a fixed order: xor butterfly inside each wave, then waves 0..3 in order.  Thread c < NV returns the
 // total of value c (the other threads return 0)
-template <int NV>
-__device__ __forceinline__ double block_sum(double (&v)[NV], double (*lds)[kIcpPartial])
+template <int NV, int STRIDE>
+__device__ __forceinline__ double block_sum(double (&v)[NV], double (*lds)[STRIDE])
 {
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
@@ -107,6 +110,51 @@ __device__ void rotation_from_covariance(const double* H, double* R)
         for (int k = 0; k < 3; ++k) R[3 * r + k] = (V[r][k0] * u1[k] + V[r][k1] * u2[k]) + sg * V[r][k2] * u3[k];
 }
 
+// One point-to-plane step from the normal equations (ata: upper triangle of A^T A row-major, 21 entries; atb: A^T b): Cholesky without pivoting in
+// double, x = (alpha, beta, gamma, t'), R = Rz(gamma) Ry(beta) Rx(alpha) as PCL's constructTransformationMatrix writes it, t = t' + o - R o (the system
+// was formed about o).  false: a zero diagonal entry or a pivot d_j <= 1e-12 (A^T A)_jj -- the system does not determine all six unknowns.
+__device__ bool plane_step(const double* ata, const double* atb, const double* o, double* R, double* t)
+{
+    double L[6][6];
+    {
+        int e = 0;
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c) { L[c][r] = ata[e]; L[r][c] = ata[e]; ++e; }
+    }
+    for (int j = 0; j < 6; ++j) {
+        const double ajj = L[j][j];
+        double d = ajj;
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(ajj > 0.0) || !(d > 1.0e-12 * ajj)) return false;
+        const double l = sqrt(d);
+        L[j][j] = l;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = L[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / l;
+        }
+    }
+    double x[6];
+    for (int i = 0; i < 6; ++i) {      // L y = A^T b
+        double v = atb[i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * x[k];
+        x[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {     // L^T x = y
+        double v = x[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!isfinite(x[i])) return false;
+    const double sa = sin(x[0]), ca = cos(x[0]), sb = sin(x[1]), cb = cos(x[1]), sg = sin(x[2]), cg = cos(x[2]);
+    R[0] = cg * cb; R[1] = -sg * ca + cg * sb * sa; R[2] = sg * sa + cg * sb * ca;
+    R[3] = sg * cb; R[4] = cg * ca + sg * sb * sa;  R[5] = -cg * sa + sg * sb * ca;
+    R[6] = -sb;     R[7] = cb * sa;                 R[8] = cb * ca;
+    for (int r = 0; r < 3; ++r) t[r] = (x[3 + r] + o[r]) - ((R[3 * r] * o[0] + R[3 * r + 1] * o[1]) + R[3 * r + 2] * o[2]);
+    return true;
+}
+
 } // namespace
 
 // -------------------------------------------------------------------------------------------------- source order
@@ -155,21 +203,25 @@ hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, ui
 }
 
 // ------------------------------------------------------------------------------------------------ correspondences
-template <bool SCORE>
+// MODE (IcpMode): kIcpPoint the moments of the SVD estimate, kIcpScore the fitness pass, kIcpPlane the normal equations of the point-to-plane estimate
+// (include/ltm.h "icp, point-to-plane"): row [p x n, n], right side n . (q - p), with p, q about the pair's origin and n the target point's normal
+template <int MODE>
 __global__ void __launch_bounds__(kIcpBlock)
 k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__ st, const uint32_t* __restrict__ block_pair, const float4* __restrict__ sorted,
                  double max_corr2, double* __restrict__ partials)
 {
-    __shared__ double lds[kIcpBlock / 64][kIcpPartial];
+    constexpr bool SCORE = MODE == kIcpScore;
+    constexpr int NP = MODE == kIcpPlane ? kIcpPlanePartial : kIcpPartial;      // doubles per record
+    __shared__ double lds[kIcpBlock / 64][NP];
     const uint32_t pi = block_pair[blockIdx.x];
     const IcpState& S = st[pi];
     if (!SCORE && S.done) return;      // the whole workgroup: the flag was written by an earlier launch
     const IcpPair& P = pairs[pi];
     const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
-    constexpr int NV = SCORE ? 2 : kIcpPartial;
-    double v[kIcpPartial];
+    constexpr int NV = SCORE ? 2 : NP;
+    double v[NP];
 #pragma unroll
-    for (int c = 0; c < kIcpPartial; ++c) v[c] = 0.0;
+    for (int c = 0; c < NP; ++c) v[c] = 0.0;
     if (local < P.n) {
         const float4 p = sorted[P.first + local];
         if (finite3(p.x, p.y, p.z)) {
@@ -196,8 +248,28 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
                 seed_leaves(t, search_key(P.f, qx, qy, qz), 1u, sa, sb);
                 for (uint32_t l = sa; l <= sb; ++l) visit(l);
                 walk(t, qx, qy, qz, sa, sb, [&](double lb) { return lb > (double)bd; }, visit);
-                if (SCORE) {
+                if constexpr (SCORE) {
                     if (bi != INT_MAX) { v[0] = 1.0; v[1] = (double)bd; }
+                } else if constexpr (MODE == kIcpPlane) {
+                    if (bi != INT_MAX && (double)bd <= max_corr2) {
+                        const float4 tp = t.pts[bj], tn = P.nrm[bj];
+                        if (finite3(tn.x, tn.y, tn.z)) {      // a correspondence without a normal is dropped
+                            const double px = (double)qx - P.o[0], py = (double)qy - P.o[1], pz = (double)qz - P.o[2];
+                            const double tx = (double)tp.x - P.o[0], ty = (double)tp.y - P.o[1], tz = (double)tp.z - P.o[2];
+                            const double nx = (double)tn.x, ny = (double)tn.y, nz = (double)tn.z;
+                            const double a[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+                            const double b = (nx * (tx - px) + ny * (ty - py)) + nz * (tz - pz);
+                            v[0] = 1.0;
+                            int e = 1;
+#pragma unroll
+                            for (int r = 0; r < 6; ++r)
+#pragma unroll
+                                for (int c = r; c < 6; ++c) v[e++] = a[r] * a[c];
+#pragma unroll
+                            for (int r = 0; r < 6; ++r) v[22 + r] = a[r] * b;
+                            v[NP - 1] = (double)bd;
+                        }
+                    }
                 } else if (bi != INT_MAX && (double)bd <= max_corr2) {
                     const float4 tp = t.pts[bj];
                     const double px = (double)qx - P.o[0], py = (double)qy - P.o[1], pz = (double)qz - P.o[2];
@@ -213,45 +285,48 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
             }
         }
     }
-    double* out = partials + (size_t)blockIdx.x * kIcpPartial;
-    if (SCORE) {
+    double* out = partials + (size_t)blockIdx.x * NP;
+    if constexpr (SCORE) {
         double w[NV] = {v[0], v[1]};
         const double r = block_sum<NV>(w, lds);
         if (threadIdx.x < (unsigned)NV) out[threadIdx.x == 0 ? 0 : 16] = r;
     } else {
-        const double r = block_sum<kIcpPartial>(v, lds);
-        if (threadIdx.x < (unsigned)kIcpPartial) out[threadIdx.x] = r;
+        const double r = block_sum<NP>(v, lds);
+        if (threadIdx.x < (unsigned)NP) out[threadIdx.x] = r;
     }
 }
 hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32_t* block_pair, uint32_t n_blocks, const float4* sorted, double max_corr2,
-                          int score, double* partials, hipStream_t s)
+                          int mode, double* partials, hipStream_t s)
 {
     if (!n_blocks) return hipSuccess;
-    if (score) k_icp_correspond<true><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
-    else k_icp_correspond<false><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
+    if (mode == kIcpScore) k_icp_correspond<kIcpScore><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
+    else if (mode == kIcpPlane) k_icp_correspond<kIcpPlane><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
+    else k_icp_correspond<kIcpPoint><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
     return hipGetLastError();
 }
 
 // --------------------------------------------------------------------------------------------------------- update
+template <bool PLANE>
 __global__ void __launch_bounds__(64)
 k_icp_update(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const double* __restrict__ partials, int max_iterations, double eps_t, double eps_mse,
              double* __restrict__ trace, uint32_t* __restrict__ unfinished)
 {
-    __shared__ double m[kIcpPartial];
+    constexpr int NP = PLANE ? kIcpPlanePartial : kIcpPartial;
+    __shared__ double m[NP];
     const uint32_t pi = blockIdx.x;
     IcpState& S = st[pi];
     if (S.done) return;
     const IcpPair& P = pairs[pi];
-    if (threadIdx.x < (unsigned)kIcpPartial) {
+    if (threadIdx.x < (unsigned)NP) {
         double a = 0.0;
-        for (uint32_t b = 0; b < P.n_blocks; ++b) a += partials[(size_t)(P.block0 + b) * kIcpPartial + threadIdx.x];      // block order
+        for (uint32_t b = 0; b < P.n_blocks; ++b) a += partials[(size_t)(P.block0 + b) * NP + threadIdx.x];      // block order
         m[threadIdx.x] = a;
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
     const double n = m[0];
     const int it = S.iterations;
-    const double mse = n > 0.0 ? m[16] / n : DBL_MAX;
+    const double mse = n > 0.0 ? m[NP - 1] / n : DBL_MAX;
     S.n_corr = (uint32_t)n;
     S.last_mse = mse;
     if (trace && it < max_iterations) {
@@ -260,10 +335,15 @@ k_icp_update(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const
         if (n > 0.0) row[1] = mse;      // otherwise the NaN the buffer was filled with stays
     }
     int state = -1;
-    if (n < 3.0) {
+    double R[9], t[3];
+    bool solved = n >= 3.0;
+    if (!solved) {
         state = 0;
+    } else if constexpr (PLANE) {
+        solved = plane_step(m + 1, m + 22, P.o, R, t);
+        if (!solved) state = 5;      // the system does not determine the step: T and the iteration count stay
     } else {
-        double pm[3], qm[3], H[9], R[9], t[3];
+        double pm[3], qm[3], H[9];
         for (int k = 0; k < 3; ++k) { pm[k] = m[1 + k] / n; qm[k] = m[4 + k] / n; }
         for (int r = 0; r < 3; ++r)
             for (int k = 0; k < 3; ++k) H[3 * r + k] = m[7 + 3 * r + k] / n - pm[r] * qm[k];
@@ -273,6 +353,8 @@ k_icp_update(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const
             const double px = pm[0] + P.o[0], py = pm[1] + P.o[1], pz = pm[2] + P.o[2];
             t[r] = (qm[r] + P.o[r]) - ((R[3 * r] * px + R[3 * r + 1] * py) + R[3 * r + 2] * pz);
         }
+    }
+    if (solved) {
         double Tn[12];
         for (int r = 0; r < 3; ++r) {
             for (int k = 0; k < 4; ++k) Tn[4 * r + k] = (R[3 * r] * S.T[k] + R[3 * r + 1] * S.T[4 + k]) + R[3 * r + 2] * S.T[8 + k];
@@ -291,16 +373,17 @@ k_icp_update(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const
     }
     if (state >= 0) {
         S.state = state;
-        S.converged = state > 0 ? 1 : 0;
+        S.converged = state > 0 && state < 5 ? 1 : 0;
         S.done = 1;
         atomicSub(unfinished, 1u);
     }
 }
 hipError_t icp_update(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, int max_iterations, double transformation_epsilon,
-                      double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s)
+                      double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s, int plane)
 {
     if (!n_pairs) return hipSuccess;
-    k_icp_update<<<dim3((unsigned)n_pairs), dim3(64), 0, s>>>(pairs, st, partials, max_iterations, transformation_epsilon, euclidean_fitness_epsilon, trace, unfinished);
+    if (plane) k_icp_update<true><<<dim3((unsigned)n_pairs), dim3(64), 0, s>>>(pairs, st, partials, max_iterations, transformation_epsilon, euclidean_fitness_epsilon, trace, unfinished);
+    else k_icp_update<false><<<dim3((unsigned)n_pairs), dim3(64), 0, s>>>(pairs, st, partials, max_iterations, transformation_epsilon, euclidean_fitness_epsilon, trace, unfinished);
     return hipGetLastError();
 }
 

@@ -268,6 +268,16 @@ hipError_t search_sort_gather_seg(const SearchSeg* segs, const uint32_t* block_s
 // the box trees of all segments in one launch (one workgroup per segment): box + box0 of a segment is what search_tree_boxes gives for its points
 hipError_t search_tree_boxes_seg(const SearchSeg* segs, size_t n_segs, const float4* sorted, float4* box, hipStream_t s);
 
+// ---- normals of the target points of search indices (ltm_k_normals.hip; include/ltm.h "normals") ----
+static constexpr int kNormalsBlockReg = 256;    // target points per workgroup, lists in registers (k <= 16)
+static constexpr int kNormalsBlockLds = 64;     // ... lists in LDS (16 < k <= 64): one wavefront
+static constexpr int kNormalsMaxK = 64;
+// one index of the batch: its tree, where its Mf normals go (aligned with t.pts), the viewpoint, and its workgroups [block0, block0 + ceil(Mf / block))
+struct NormalsSeg { SearchTree t; float4* out; double vp[3]; uint32_t block0, pad; };
+int        normals_block(int k);                // target points per workgroup of the kernel that k selects
+// out[j] = (nx, ny, nz, curvature) of target point t.pts[j] from its min(k, Mf) nearest target points, for every index of the table in one launch
+hipError_t estimate_normals(const NormalsSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, int k, hipStream_t s);
+
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
 // one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; workgroups [block0, block0 + ceil(n / 256))
 struct SubmapPiece { uint64_t src, dst; uint32_t n, block0, affine, pad; };
@@ -277,9 +287,12 @@ hipError_t submap_gather(const float4* scans, const SubmapPiece* pieces, const u
 // ---- batched point-to-point ICP over search indices (ltm_k_icp.hip; LTslam.cpp:187-301) ----
 static constexpr int kIcpBlock = 256;           // source points per workgroup of the correspondence kernel = per partial record
 static constexpr int kIcpPartial = 17;          // doubles per partial record: count, sum p (3), sum q (3), sum p q^T (9, row-major), sum d2
+static constexpr int kIcpPlanePartial = 29;     // point-to-plane: count, A^T A (21, upper triangle row-major), A^T b (6), sum d2
+enum IcpMode { kIcpPoint = 0, kIcpScore = 1, kIcpPlane = 2 };
 // one pair of the batch: the target's tree and frame, the source as given (src, n points), its slice [first, first + n) of the batch's sorted sources and
-// its workgroups [block0, block0 + n_blocks) of the correspondence grid; o: the origin the moments are taken about (the corner of the target's frame)
-struct IcpPair { SearchTree t; SearchFrame f; const float4* src; double o[3]; uint64_t first; uint32_t n, block0, n_blocks, pad; };
+// its workgroups [block0, block0 + n_blocks) of the correspondence grid; o: the origin the moments are taken about (the corner of the target's frame);
+// nrm: the target's normals, aligned with t.pts (point-to-plane only)
+struct IcpPair { SearchTree t; SearchFrame f; const float4* src; double o[3]; uint64_t first; uint32_t n, block0, n_blocks, pad; const float4* nrm; };
 // what k_icp_update keeps per pair between iterations (T: rows 0..2 of the accumulated transform, row-major)
 struct IcpState { double T[12]; double prev_mse, last_mse, fitness; int32_t iterations, state, converged, done; uint32_t n_corr, pad; };
 // codes of every source point under its target's frame (keys) and its position in its source (idx); grid over the blocks of block_pair
@@ -289,13 +302,15 @@ size_t     icp_sort_temp_bytes(size_t total, size_t n_pairs);
 hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
                             const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes,
                             hipStream_t s);
-// one record of kIcpPartial doubles per workgroup; score = 0: correspondences within max_corr2 of the pairs not done yet, 1: count and sum d2 of every
-// finite point of every pair, no limit
+// one record per workgroup.  mode kIcpPoint: kIcpPartial doubles, correspondences within max_corr2 of the pairs not done yet; kIcpScore: count and sum d2
+// of every finite point of every pair, no limit (in a record of kIcpPartial); kIcpPlane: kIcpPlanePartial doubles, the normal equations of the
+// correspondences within max_corr2 whose target normal is finite
 hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32_t* block_pair, uint32_t n_blocks, const float4* sorted, double max_corr2,
-                          int score, double* partials, hipStream_t s);
-// per pair: partials added in block order, transform estimate, stop tests; trace (nullable): n_pairs x max_iterations x 2; unfinished: one counter
+                          int mode, double* partials, hipStream_t s);
+// per pair: partials added in block order, transform estimate (plane: the 6 x 6 solve of the kIcpPlane records), stop tests; trace (nullable):
+// n_pairs x max_iterations x 2; unfinished: one counter
 hipError_t icp_update(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, int max_iterations, double transformation_epsilon,
-                      double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s);
+                      double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s, int plane = 0);
 hipError_t icp_fitness(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, hipStream_t s);
 
 // ---- scan context (ltm_k_scancontext.hip; Scancontext.cpp:69-324) ----

@@ -5,6 +5,8 @@
 // original source).  setInputTarget builds a search index on the device, which align and alignAll reuse until the next setInputTarget: addSCloops'
 // loop over many sources against one submap becomes ONE alignAll.  The swap for the member of LTslam is shown in INTEGRATION.md.
 // Every member reports a failure by throwing (std::runtime_error with the context's message, std::logic_error for a call out of order).
+// setMethod(PointToPlane) switches to pcl::IterativeClosestPointWithNormals' error (include/ltm.h, "icp, point-to-plane"): the target's normals are then
+// estimated on the device (setKSearch / setViewPoint as on pcl::NormalEstimation) before the first alignment against a target.
 // Not here: the Euler / gtsam::Pose3 conversions of the result stay on the host as they are (the submaps: DeviceLoopSubmaps.h).
 #pragma once
 #include <initializer_list>
@@ -31,6 +33,13 @@ public:
     void setTransformationEpsilon(double e) { params_.transformation_epsilon = e; }
     void setEuclideanFitnessEpsilon(double e) { params_.euclidean_fitness_epsilon = e; }
     const ltm_icp_params& params() const { return params_; }
+
+    enum Method { PointToPoint, PointToPlane };
+    void setMethod(Method m) { method_ = m; }
+    Method method() const { return method_; }
+    // the normals of the point-to-plane method: neighbours and viewpoint of pcl::NormalEstimation
+    void setKSearch(int k) { normal_k_ = k; have_normals_ = false; }
+    void setViewPoint(float vx, float vy, float vz) { viewpoint_[0] = vx; viewpoint_[1] = vy; viewpoint_[2] = vz; have_normals_ = false; }
 
     // pcl::Registration::setInputSource: the cloud is copied (the reference keeps a shared pointer)
     void setInputSource(const Cloud& source) { source_ = source; }
@@ -98,7 +107,13 @@ private:
         std::vector<ltm_search*> t(n, index_);
         int rc = LTM_OK;
         for (size_t i = 0; i < n && rc == LTM_OK; ++i) rc = ltm_cloud_upload(ctx_, sources[i]->data(), sources[i]->size(), sizeof(PointType), &h[i]);
-        if (rc == LTM_OK) rc = ltm_icp_align(ctx_, n, t.data(), h.data(), one_guess ? one_guess->data() : guesses, &params_, out.data(), nullptr);
+        if (rc == LTM_OK && method_ == PointToPlane && !have_normals_) {
+            rc = ltm_search_estimate_normals(ctx_, 1, &index_, normal_k_, viewpoint_);
+            have_normals_ = rc == LTM_OK;
+        }
+        if (rc == LTM_OK)
+            rc = (method_ == PointToPlane ? ltm_icp_align_plane : ltm_icp_align)(ctx_, n, t.data(), h.data(), one_guess ? one_guess->data() : guesses, &params_,
+                                                                                 out.data(), nullptr);
         std::string msg = rc != LTM_OK ? ltm_last_error(ctx_) : "";
         for (ltm_cloud c : h) if (c) ltm_cloud_free(ctx_, c);
         if (rc != LTM_OK) throw std::runtime_error("DeviceICP: " + msg);
@@ -113,6 +128,7 @@ private:
     {
         if (index_) ltm_search_free(ctx_, index_);
         index_ = nullptr;
+        have_normals_ = false;
     }
     void reset_result()
     {
@@ -129,6 +145,10 @@ private:
     Cloud source_;
     ltm_search* index_ = nullptr;
     ltm_icp_result result_;
+    Method method_ = PointToPoint;
+    int normal_k_ = 10;
+    float viewpoint_[3] = {0.0f, 0.0f, 0.0f};
+    bool have_normals_ = false;      // of index_, with the current k and viewpoint
 };
 
 } // namespace ltremovert
