@@ -615,6 +615,13 @@ int ltm_debug_voxel_key_bits(const float* mn3, const float* mx3, float leaf, uin
  * for a workgroup with nothing to do): (b >> 6) / n_tile_groups is taken as mulhi(b & ~63, magic) >> shift, exact for every b < 2^32. */
 int ltm_debug_proj_launch(float vfov, float hfov, float res_alpha, const double* base2lidar16_or_null, size_t map_points, size_t n_keyframes, int on_device,
                           float* out_f32, uint32_t* out_u32, uint32_t first_block, size_t n_blocks, uint32_t* out_tile, uint32_t* out_kf);
+/* The workgroup mapping of the range-culled vote kernel (k_vote_map_cull): one workgroup takes a run of `tile_run` consecutive 4096-point map tiles
+ * for one keyframe (context switch LTM_VOTE_TILE_RUN, 1 .. 16, default 4, read by ltm_create; 1 = one tile per workgroup, the mapping
+ * ltm_debug_proj_launch reports).  Run r covers tiles [r * run_len, min((r + 1) * run_len, n_tiles)).  For the workgroups [first_block, first_block + n_blocks) of a launch over
+ * `map_points` points and `n_keyframes` keyframes: the run and the keyframe each one works on (0xffffffff in both for a workgroup with nothing to do),
+ * the run length after clamping and the grid size.  Needs no context and no device; exact for every block index below 2^32. */
+int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_run, uint32_t first_block, size_t n_blocks, uint32_t* out_run, uint32_t* out_kf,
+                              uint32_t* out_run_len, uint32_t* out_grid);
 /* checks the bounded-error projection that the range-culled vote kernel uses to decide which points need the exact
  * arithmetic: counts points (host xyz, n*3 floats; global frame if inv_pose16 is given, else local) whose exact pixel /
  * range fall outside its candidate set / bounds.  Must be 0. */

@@ -167,6 +167,7 @@ SIGNATURES = {
     "ltm_debug_cull_check": (_i, [_vp, _vp, _sz, _vp, _f, _pu64]),
     "ltm_debug_cull_stats": (_i, [_vp, _pu64, _pu64, _i]),
     "ltm_debug_proj_launch": (_i, [_f, _f, _f, _vp, _sz, _sz, _i, _vp, _vp, C.c_uint32, _sz, _vp, _vp]),
+    "ltm_debug_vote_run_launch": (_i, [_sz, _sz, _i, C.c_uint32, _sz, _vp, _vp, _vp, _vp]),
     "ltm_debug_cull_validation": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_occlusion_stats": (_i, [_vp, _pu64, _pu64, _pu64, _i]),
     "ltm_debug_voxel_stats": (_i, [_vp, _pu64, _pu64, _i]),
@@ -237,6 +238,19 @@ def proj_launch(vfov, hfov, alpha, base2lidar=None, map_points=0, n_keyframes=1,
     if rc != 0:
         raise LtmError(rc, "ltm_debug_proj_launch")
     return dict(zip(PROJ_LAUNCH_F32, f)), {k: int(v) for k, v in zip(PROJ_LAUNCH_U32, u)}, tile[:n_blocks], kf[:n_blocks]
+
+
+def vote_run_launch(map_points, n_keyframes, tile_run, first_block=0, n_blocks=0):
+    """ltm_debug_vote_run_launch: (run[n_blocks], keyframe[n_blocks], run length, grid size) -- which run of `tile_run` consecutive map tiles and which
+    keyframe each workgroup of a range-culled vote launch works on (0xffffffff: idle).  Needs no context and no device."""
+    run = np.zeros(max(n_blocks, 1), dtype=np.uint32)
+    kf = np.zeros(max(n_blocks, 1), dtype=np.uint32)
+    run_len, grid = C.c_uint32(0), C.c_uint32(0)
+    rc = load_library().ltm_debug_vote_run_launch(int(map_points), int(n_keyframes), int(tile_run), int(first_block), int(n_blocks), run.ctypes.data,
+                                                  kf.ctypes.data, C.byref(run_len), C.byref(grid))
+    if rc != 0:
+        raise LtmError(rc, "ltm_debug_vote_run_launch")
+    return run[:n_blocks], kf[:n_blocks], run_len.value, grid.value
 
 
 def inverse4x4(m):

@@ -321,7 +321,7 @@ void do_vote(ltm_ctx* c, const Cloud& map, uint64_t ss_handle, const ScanSet& ss
             }
             ProfScope p(c, cull ? "vote_map_cull" : "vote_map_exact", pts, bytes, bytes_c);
             if (cull) {
-                HeavyScope hs(c, n_tiles * nb);
+                HeavyScope hs(c, vote_run_blocks(map.n, nb, c->kopts.vote_tile_run));
                 LTM_HIP(vote_map_range_images(map.d, map.n, ps.inv_dev, ps.approx_dev, kb, nb, c->B2L, c->b2l_identity, g, qbound, tb.as<float>(), smax, thr, mode,
                                               map_img.as<uint64_t>(), hs.stream(), c->kopts));
                 hs.done();
@@ -610,6 +610,17 @@ int ltm_debug_proj_launch(float vfov, float hfov, float alpha, const double* bas
     if (base2lidar16) { b2l = to34(base2lidar16); ident = mat_is_identity(base2lidar16) ? 1 : 0; }
     if (proj_launch_debug(g, b2l, ident, map_points, n_keyframes, on_device, out_f32, out_u32) != hipSuccess) return LTM_E_DEVICE;
     if (n_blocks) proj_launch_blocks(map_points, n_keyframes, first_block, n_blocks, out_tile, out_kf);
+    return LTM_OK;
+}
+
+int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_run, uint32_t first_block, size_t n_blocks, uint32_t* out_run, uint32_t* out_kf,
+                              uint32_t* out_run_len, uint32_t* out_grid)
+{
+    if (map_points >= 0xffffffffull || n_keyframes >= 0xffffffffull || tile_run < 1 || (n_blocks && (!out_run || !out_kf))) return LTM_E_INVALID;
+    uint32_t len = 0;
+    const unsigned grid = vote_run_launch_blocks(map_points, n_keyframes, tile_run, first_block, n_blocks, out_run, out_kf, &len);
+    if (out_run_len) *out_run_len = len;
+    if (out_grid) *out_grid = grid;
     return LTM_OK;
 }
 

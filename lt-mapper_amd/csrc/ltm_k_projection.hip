@@ -536,140 +536,188 @@ static constexpr int kCullSlots = 512;   // survivors are ~10 % of a workgroup's
 template <bool B2L_IDENTITY, bool EL3>     // EL3: fitted elevation polynomial (Geom::el_fit), see cull_candidates
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, const float* __restrict__ approx_poses,
-                uint32_t kb, uint32_t nb, HostMat34 b2l_h, ProjLaunch pl, const float* __restrict__ qbound_img,
+                uint32_t kb, uint32_t nb, HostMat34 b2l_h, ProjLaunch pl, RunLaunch rl, const float* __restrict__ qbound_img,
                 const float* __restrict__ tile_bounds, const uint32_t* __restrict__ smax_bits, float thr, uint64_t* __restrict__ img)
 {
     __shared__ uint64_t vals[kCullSlots];
     __shared__ uint32_t tags[kCullSlots];
-    // survivors of phase 1, one word each: tile-local index (12 bits) | row (9) | column (11); row field 511 = pixel not certain,
-    // needs the full exact projection (images with >= 511 rows or > 2048 columns mark every survivor that way)
+    // survivors of phase 1 of the current tile, one word each: tile-local index (12 bits) | row (9) | column (11); row field 511 = pixel not
+    // certain, needs the full exact projection (images with >= 511 rows or > 2048 columns mark every survivor that way)
     __shared__ uint32_t queue[kCullQueue];
-    __shared__ uint16_t uqueue[kCullQueue];    // the uncertain ones, re-queued densely in phase 2
-    __shared__ uint32_t qcount, ucount;
+    // the uncertain ones of the whole run, re-queued densely in phase 2: (tile in run) << 12 | tile-local index = the offset from the run's first point
+    __shared__ uint16_t uqueue[kCullQueue];
+    __shared__ uint32_t qcount, ucount;      // qcount is never reset: a tile's entries are counted from its value at the tile's start (qbase)
+    static_assert(kMaxTileRun * kBlock * kPtsPerThread <= 65536, "uqueue entries are 16 bits");
     const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
-    const TileKf tk = tile_kf_of_block(blockIdx.x, pl, nb);
-    if (!tk.valid) return;
-    if (tile_bounds && tile_out_of_reach(approx_poses + 16 * (size_t)(kb + tk.kfb), tile_bounds + 6 * (size_t)tk.tile, u2f(smax_bits[tk.kfb]), thr)) return;
+    // One workgroup = a run of rl.T consecutive tiles against one keyframe.  Whatever depends on the keyframe only -- pose, image bases, the pixel
+    // table and its flush -- happens once per run; the tiles of the run are visited in order, each as before.
+    const RunKf rk = run_kf_of_block(blockIdx.x, rl, nb);
+    if (!rk.valid) return;
+    const RimgGeom& g = pl.g;
+    const uint32_t npx = pl.npx;
+    const uint32_t kf = kb + rk.kfb;
+    const uint32_t first_tile = rk.run * rl.T;
+    const uint32_t run_base = first_tile * per_block;
+    uint64_t* __restrict__ imgk = img + (size_t)rk.kfb * npx;
+    const float* __restrict__ qk = qbound_img + (size_t)rk.kfb * npx;
+    const float* __restrict__ ap = approx_poses + 16 * (size_t)kf;
+    // The reach test of all tiles of the run at once: lane t of every wave tests tile t, and the ballot -- the same in every wave -- is the set of
+    // tiles to visit.  (One evaluation per run instead of one per tile, on values that are uniform and so would cost every lane its issue slots; and
+    // neither the bounds nor the scan's reach have to stay in registers through the tile loop.)
+    uint32_t todo;
+    {
+        const uint32_t t = threadIdx.x & 63u;
+        bool visit = (t < rl.T) & (first_tile + t < pl.n_tiles);
+        if (visit && tile_bounds) visit = !tile_out_of_reach(ap, tile_bounds + 6 * (size_t)(first_tile + t), u2f(smax_bits[rk.kfb]), thr);
+        todo = (uint32_t)__builtin_amdgcn_ballot_w64(visit);
+    }
+    if (!todo) return;
     for (int s = threadIdx.x; s < kCullSlots; s += kBlock) { tags[s] = kEmptyTag; vals[s] = ~0ull; }
     if (threadIdx.x == 0) { qcount = 0; ucount = 0; }
     __syncthreads();
-    const RimgGeom& g = pl.g;
-    const uint32_t npx = pl.npx;
-    const uint32_t block_base = tk.tile * per_block;
-    const float4* __restrict__ mapb = map + block_base;
-    const uint32_t nloc = min(per_block, M - block_base);
-    const uint32_t kf = kb + tk.kfb;
-    uint64_t* __restrict__ imgk = img + (size_t)tk.kfb * npx;
-    const float* __restrict__ qk = qbound_img + (size_t)tk.kfb * npx;
-    // ---- phase 1: who can matter?  (bounded-error arithmetic only).  Four points per lane are in flight at once so the
-    // dependent scan-image load of one overlaps the arithmetic of the others.  Only full tiles: the one partial tile at the end
-    // of the map takes the exact path as a whole (below), which keeps bounds tests and clamped indices out of this loop.
-    // Neither does an image whose rows / columns do not fit the queue word (9 + 11 bits) nor a keyframe whose approximate pose is not usable (ap[15] == 0):
-    // every point of such a tile used to be queued as "uncertain", which overflowed the queue and sent the tile down the exact path anyway.
-    const float* __restrict__ ap = approx_poses + 16 * (size_t)kf;
-    const bool full_tile = (nloc == per_block) & pl.packable & (ap[15] != 0.0f);
-    if (full_tile) {
-        constexpr int kInFlight = 4;
-        constexpr bool kPrefetch = true;     // software pipelining: the next group's points are requested before this group's arithmetic
-        float4 nxt[kInFlight];
-        if (kPrefetch) {
+    const bool fast_ok = pl.packable & ((f2u(ap[15]) << 1) != 0u);      // ap[15] != 0.0f, as an integer test: the scalar unit has no float compare
+    const double* __restrict__ inv_pose = inv_poses + 12 * (size_t)kf;      // (loaded where the exact arithmetic starts: 24 scalar registers that phase 1 has no room for)
+    bool flush = false;                 // some tile queued a survivor: the table may hold pixels
+    uint32_t qbase = 0;                 // (uniform, like everything else that the loop carries)
+    for (; todo; todo &= todo - 1u) {
+        const uint32_t tile = first_tile + (uint32_t)__builtin_ctz(todo);
+        const uint32_t block_base = tile * per_block;
+        const float4* __restrict__ mapb = map + block_base;
+        const uint32_t nloc = min(per_block, M - block_base);
+        // ---- phase 1: who can matter?  (bounded-error arithmetic only).  Four points per lane are in flight at once so the
+        // dependent scan-image load of one overlaps the arithmetic of the others.  Only full tiles: the one partial tile at the end
+        // of the map takes the exact path as a whole (below), which keeps bounds tests and clamped indices out of this loop.
+        // Neither does an image whose rows / columns do not fit the queue word (9 + 11 bits) nor a keyframe whose approximate pose is not usable (ap[15] == 0):
+        // every point of such a tile used to be queued as "uncertain", which overflowed the queue and sent the tile down the exact path anyway.
+        const bool full_tile = (nloc == per_block) & fast_ok;
+        if (full_tile) {
+            constexpr int kInFlight = 4;
+            constexpr bool kPrefetch = true;     // software pipelining: the next group's points are requested before this group's arithmetic
+            float4 nxt[kInFlight];
+            if (kPrefetch) {
 #pragma unroll
-            for (int u = 0; u < kInFlight; ++u) nxt[u] = mapb[(uint32_t)u * kBlock + threadIdx.x];
-        }
-        const uint32_t lane_word = threadIdx.x << 20;            // queue word: tile-local index (12 bits) | row (9) | column (11)
+                for (int u = 0; u < kInFlight; ++u) nxt[u] = mapb[(uint32_t)u * kBlock + threadIdx.x];
+            }
+            const uint32_t lane_word = threadIdx.x << 20;            // queue word: tile-local index (12 bits) | row (9) | column (11)
 #pragma unroll
-        for (uint32_t j0 = 0; j0 < (uint32_t)kPtsPerThread; j0 += kInFlight) {
-            float4 pt[kInFlight];
-            CullCand cc[kInFlight];
-            float q0[kInFlight];
+            for (uint32_t j0 = 0; j0 < (uint32_t)kPtsPerThread; j0 += kInFlight) {
+                float4 pt[kInFlight];
+                CullCand cc[kInFlight];
+                float q0[kInFlight];
 #pragma unroll
-            for (int u = 0; u < kInFlight; ++u) {
-                const uint32_t li = (j0 + u) * kBlock + threadIdx.x;
-                if (kPrefetch) {
-                    pt[u] = nxt[u];
-                    if (j0 + kInFlight < (uint32_t)kPtsPerThread) nxt[u] = mapb[li + kInFlight * kBlock];
-                } else {
-                    pt[u] = mapb[li];
+                for (int u = 0; u < kInFlight; ++u) {
+                    const uint32_t li = (j0 + u) * kBlock + threadIdx.x;
+                    if (kPrefetch) {
+                        pt[u] = nxt[u];
+                        if (j0 + kInFlight < (uint32_t)kPtsPerThread) nxt[u] = mapb[li + kInFlight * kBlock];
+                    } else {
+                        pt[u] = mapb[li];
+                    }
                 }
-            }
 #pragma unroll
-            for (int u = 0; u < kInFlight; ++u) {
-                bool ok;      // (uniform, part of full_tile)
-                const float3 p = xform_approx(ap, pt[u], ok);
-                cc[u] = cull_candidates<EL3>(pl, p);
-                // not certain of the pixel (within cull_eps_px of a rounding boundary, ~1 % of the points): straight to the exact path
-                cc[u].unusual |= cc[u].multi | (B2L_IDENTITY ? false : (cc[u].r2 < pl.rmin2));
-                q0[u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(qk) + ((__umul24((uint32_t)cc[u].rb, (uint32_t)g.cols) + (uint32_t)cc[u].cb) << 2));   // uniform base + 32-bit offset
-            }
-            bool mt[kInFlight];
+                for (int u = 0; u < kInFlight; ++u) {
+                    bool ok;      // (uniform, part of full_tile)
+                    const float3 p = xform_approx(ap, pt[u], ok);
+                    cc[u] = cull_candidates<EL3>(pl, p);
+                    // not certain of the pixel (within cull_eps_px of a rounding boundary, ~1 % of the points): straight to the exact path
+                    cc[u].unusual |= cc[u].multi | (B2L_IDENTITY ? false : (cc[u].r2 < pl.rmin2));
+                    q0[u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(qk) + ((__umul24((uint32_t)cc[u].rb, (uint32_t)g.cols) + (uint32_t)cc[u].cb) << 2));   // uniform base + 32-bit offset
+                }
+                bool mt[kInFlight];
 #pragma unroll
-            for (int u = 0; u < kInFlight; ++u) {
-                // qbound[px] = an upper bound of the SQUARED range below which a point of that pixel could be flagged (k_scan_qbound):
-                // one compare decides; empty pixels hold 0
-                mt[u] = cc[u].unusual | (cc[u].r2 < q0[u]);
-            }
-            // One LDS atomic per wave for the four points of every lane (hand-rolled ballot/mbcnt aggregation: letting the compiler
-            // aggregate four separate atomicAdd(&qcount, 1) costs ~40 instructions each and one of them is taken almost always).
-            const uint64_t b0 = __builtin_amdgcn_ballot_w64(mt[0]), b1 = __builtin_amdgcn_ballot_w64(mt[1]),
-                           b2 = __builtin_amdgcn_ballot_w64(mt[2]), b3 = __builtin_amdgcn_ballot_w64(mt[3]);
-            const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1), n2 = (uint32_t)__popcll(b2), n3 = (uint32_t)__popcll(b3);
-            const uint32_t total = n0 + n1 + n2 + n3;
-            if (total) {
-                uint32_t base = 0;
-                if ((threadIdx.x & 63u) == 0u) base = atomicAdd(&qcount, total);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-                // overflow (rare) is decided per wave and group, on the scalar unit: the whole tile takes the exact path below then
-                if (base + total <= (uint32_t)kCullQueue) {
-                    const uint64_t bal[kInFlight] = {b0, b1, b2, b3};
-                    const uint32_t off[kInFlight] = {0u, n0, n0 + n1, n0 + n1 + n2};
+                for (int u = 0; u < kInFlight; ++u) {
+                    // qbound[px] = an upper bound of the SQUARED range below which a point of that pixel could be flagged (k_scan_qbound):
+                    // one compare decides; empty pixels hold 0
+                    mt[u] = cc[u].unusual | (cc[u].r2 < q0[u]);
+                }
+                // One LDS atomic per wave for the four points of every lane (hand-rolled ballot/mbcnt aggregation: letting the compiler
+                // aggregate four separate atomicAdd(&qcount, 1) costs ~40 instructions each and one of them is taken almost always).
+                const uint64_t b0 = __builtin_amdgcn_ballot_w64(mt[0]), b1 = __builtin_amdgcn_ballot_w64(mt[1]),
+                               b2 = __builtin_amdgcn_ballot_w64(mt[2]), b3 = __builtin_amdgcn_ballot_w64(mt[3]);
+                const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1), n2 = (uint32_t)__popcll(b2), n3 = (uint32_t)__popcll(b3);
+                const uint32_t total = n0 + n1 + n2 + n3;
+                if (total) {
+                    uint32_t base = 0;
+                    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(&qcount, total);
+                    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base) - qbase;
+                    // overflow (rare) is decided per wave and group, on the scalar unit: the whole tile takes the exact path below then
+                    if (base + total <= (uint32_t)kCullQueue) {
+                        const uint64_t bal[kInFlight] = {b0, b1, b2, b3};
+                        const uint32_t off[kInFlight] = {0u, n0, n0 + n1, n0 + n1 + n2};
 #pragma unroll
-                    for (int u = 0; u < kInFlight; ++u) {
-                        if (!mt[u]) continue;
-                        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[u], 0u));
-                        const uint32_t rowq = cc[u].unusual ? 511u : (uint32_t)cc[u].rb;
-                        queue[base + off[u] + below] = (((rowq << 11) | (uint32_t)cc[u].cb) | lane_word) | (((j0 + u) * kBlock) << 20);
+                        for (int u = 0; u < kInFlight; ++u) {
+                            if (!mt[u]) continue;
+                            const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[u], 0u));
+                            const uint32_t rowq = cc[u].unusual ? 511u : (uint32_t)cc[u].rb;
+                            queue[base + off[u] + below] = (((rowq << 11) | (uint32_t)cc[u].cb) | lane_word) | (((j0 + u) * kBlock) << 20);
+                        }
                     }
                 }
             }
         }
-    }
-    __syncthreads();
-    // ---- phase 2: survivors.  Certain pixel: only the exact range is computed; the ~1 % others are re-queued densely at the
-    // top of the same array and get the full exact projection afterwards (keeps both loops free of divergence).
-    const uint32_t nq_all = full_tile ? qcount : (uint32_t)kCullQueue + 1u;
-    if (nloc == per_block && threadIdx.x == 0 && (blockIdx.x & 63u) == 0u) {   // sampled 1/64: same-address atomics from every workgroup would serialise the grid
-        atomicAdd(&g_cull_stats[0], (unsigned long long)nq_all);
-        atomicAdd(&g_cull_stats[1], (unsigned long long)nloc);
-    }
-    if (nq_all) {
-        const Mat34 Tinv = load_mat(inv_poses + 12 * (size_t)kf);
-        if (__builtin_expect(nq_all > (uint32_t)kCullQueue, 0)) {      // queue overflow: a superset is always correct (min is idempotent)
-            for (uint32_t li = threadIdx.x; li < nloc; li += kBlock)
-                exact_insert<B2L_IDENTITY, 8, 64>(map, block_base + li, Tinv, b2l_h, g, vals, tags, imgk);
-        } else {
-            for (uint32_t q = threadIdx.x; q < nq_all; q += kBlock) {
-                const uint32_t e = queue[q];
-                const int row = (int)((e >> 11) & 511u), col = (int)(e & 2047u);
-                if (row == 511) { uqueue[atomicAdd(&ucount, 1u)] = (uint16_t)(e >> 20); continue; }
-                const uint32_t i = block_base + (e >> 20);
-                const uint32_t px = (uint32_t)(row * g.cols + col);
-                const uint64_t v = ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i;
-                const int slot = table_claim<8, 64>(tags, row, col, px);
-                if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
-                else img_min_u64(imgk + px, v);
+        // (read on this side of the barrier: ucount last changed before the barrier that ended the tile before, and changes again right after this one)
+        const uint32_t nu_waiting = (uint32_t)__builtin_amdgcn_readfirstlane((int)ucount);
+        __syncthreads();
+        // ---- phase 2: survivors.  Certain pixel: only the exact range is computed; the ~1 % others are re-queued densely in uqueue
+        // and get the full exact projection after the last tile of the run (keeps both loops free of divergence, and fills the waves of the second).
+        const uint32_t qend = (uint32_t)__builtin_amdgcn_readfirstlane((int)qcount);
+        const uint32_t nq_all = full_tile ? qend - qbase : (uint32_t)kCullQueue + 1u;
+        qbase = qend;
+        if (nloc == per_block && threadIdx.x == 0 && (blockIdx.x & 63u) == 0u) {   // sampled 1/64: same-address atomics from every workgroup would serialise the grid
+            atomicAdd(&g_cull_stats[0], (unsigned long long)nq_all);
+            atomicAdd(&g_cull_stats[1], (unsigned long long)nloc);
+        }
+        if (nq_all) {
+            flush = true;
+            const Mat34 Tinv = load_mat(inv_pose);
+            if (__builtin_expect(nq_all > (uint32_t)kCullQueue, 0)) {      // queue overflow: a superset is always correct (min is idempotent)
+                for (uint32_t li = threadIdx.x; li < nloc; li += kBlock)
+                    exact_insert<B2L_IDENTITY, 8, 64>(map, block_base + li, Tinv, b2l_h, g, vals, tags, imgk);
+            } else {
+                // the uncertain ones wait for the end of the run -- unless this tile's could overflow their queue (a tile queues at most nq_all of
+                // them): then the waiting ones go first
+                if (__builtin_expect(nu_waiting + nq_all > (uint32_t)kCullQueue, 0)) {
+                    uint32_t q0 = threadIdx.x;
+                    asm volatile("" : "+v"(q0));      // opaque: keeps this rare path's addresses from being hoisted into registers that live through phase 1
+                    for (uint32_t q = q0; q < nu_waiting; q += kBlock)
+                        exact_insert<B2L_IDENTITY, 8, 64>(map, run_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
+                    __syncthreads();
+                    if (threadIdx.x == 0) ucount = 0;
+                    __syncthreads();
+                }
+                const uint32_t tile_word = (tile - first_tile) << 12;
+                for (uint32_t q = threadIdx.x; q < nq_all; q += kBlock) {
+                    const uint32_t e = queue[q];
+                    const int row = (int)((e >> 11) & 511u), col = (int)(e & 2047u);
+                    if (row == 511) { uqueue[atomicAdd(&ucount, 1u)] = (uint16_t)(tile_word | (e >> 20)); continue; }
+                    const uint32_t i = block_base + (e >> 20);
+                    const uint32_t px = (uint32_t)(row * g.cols + col);
+                    const uint64_t v = ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i;
+                    const int slot = table_claim<8, 64>(tags, row, col, px);
+                    if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
+                    else img_min_u64(imgk + px, v);
+                }
             }
-            __syncthreads();
-            const uint32_t nu = ucount;
-            for (uint32_t q = threadIdx.x; q < nu; q += kBlock)
-                exact_insert<B2L_IDENTITY, 8, 64>(map, block_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
         }
+        // This tile's image atomics retire here.  The vector memory counter also counts them, and they may retire out of order with loads: with
+        // some still in flight at the top of the loop every wait for a point of phase 1 would have to be a wait for ALL loads in flight, the
+        // prefetched ones included (that is what the compiler emits then), and phase 1 loses its software pipelining.  (Waiting only when another
+        // tile follows measured no better.)
+        __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) only
+        __syncthreads();      // the queue is free for the next tile, ucount is final for this one
+    }
+    if (!flush) return;
+    const uint32_t nu = ucount;
+    if (nu) {
+        const Mat34 Tinv = load_mat(inv_pose);
+        for (uint32_t q = threadIdx.x; q < nu; q += kBlock)
+            exact_insert<B2L_IDENTITY, 8, 64>(map, run_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
     }
     __syncthreads();
-    if (nq_all)
-        for (int s = threadIdx.x; s < kCullSlots; s += kBlock) {
-            const uint32_t t = tags[s];
-            if (t != kEmptyTag) img_min_u64(imgk + t, vals[s]);
-        }
+    for (int s = threadIdx.x; s < kCullSlots; s += kBlock) {
+        const uint32_t t = tags[s];
+        if (t != kEmptyTag) img_min_u64(imgk + t, vals[s]);
+    }
 }
 
 hipError_t cull_stats(unsigned long long* out2, int reset, hipStream_t s, int which_kernel)
@@ -690,12 +738,12 @@ hipError_t vote_map_range_images(const float4* map, size_t M, const double* inv_
 {
     if (!M || !nb) return hipSuccess;
     if (mode != 0 || !ko.vote_cull || !approx_poses_dev || !qbound_img) return map_range_images(map, M, inv_poses_dev, approx_poses_dev, kb, nb, b2l, b2l_identity, g, map_img, s, ko);
-    const size_t per_block = (size_t)kBlock * kPtsPerThread;
-    dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb));
     const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);
+    const RunLaunch rl = make_run_launch(pl.n_tiles, (uint32_t)std::max(ko.vote_tile_run, 1));
+    dim3 grid(run_kf_grid(rl, nb));
     const float* tb = (ko.tile_cull && smax_bits_dev) ? tile_bounds_dev : nullptr;
     const bool el3 = g.el_fit != 0;
-#define LTM_LAUNCH_CULL(ID, E) k_vote_map_cull<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, qbound_img, tb, smax_bits_dev, thr, map_img)
+#define LTM_LAUNCH_CULL(ID, E) k_vote_map_cull<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, rl, qbound_img, tb, smax_bits_dev, thr, map_img)
     if (!b2l_identity) { if (el3) LTM_LAUNCH_CULL(false, true); else LTM_LAUNCH_CULL(false, false); }
     else { if (el3) LTM_LAUNCH_CULL(true, true); else LTM_LAUNCH_CULL(true, false); }
 #undef LTM_LAUNCH_CULL
@@ -1338,6 +1386,23 @@ void proj_launch_blocks(size_t M, size_t nb, uint32_t first_block, size_t n, uin
         tile[i] = t.valid ? t.tile : 0xffffffffu;
         kf[i] = t.valid ? t.kfb : 0xffffffffu;
     }
+}
+size_t vote_run_blocks(size_t M, size_t nb, int tile_run)
+{
+    const size_t per_block = (size_t)kBlock * kPtsPerThread;
+    return (size_t)make_run_launch((uint32_t)((M + per_block - 1) / per_block), (uint32_t)std::max(tile_run, 1)).n_runs * nb;
+}
+unsigned vote_run_launch_blocks(size_t M, size_t nb, int tile_run, uint32_t first_block, size_t n, uint32_t* run, uint32_t* kf, uint32_t* run_len)
+{
+    const size_t per_block = (size_t)kBlock * kPtsPerThread;
+    const RunLaunch rl = make_run_launch((uint32_t)((M + per_block - 1) / per_block), (uint32_t)std::max(tile_run, 1));
+    for (size_t i = 0; i < n; ++i) {
+        const RunKf t = run_kf_of_block(first_block + (uint32_t)i, rl, (uint32_t)nb);
+        run[i] = t.valid ? t.run : 0xffffffffu;
+        kf[i] = t.valid ? t.kfb : 0xffffffffu;
+    }
+    if (run_len) *run_len = rl.T;
+    return run_kf_grid(rl, nb);
 }
 
 } // namespace ltm

@@ -52,6 +52,17 @@ struct ProjLaunch {
     bool steep_clamps;                 // vfov < 88: every elevation beyond +-45 deg clamps into the first / last row
     bool packable;                     // rows < 511 and cols <= 2048: row and column fit the 9 + 11 bits of a queue word
 };
+// (b >> 6) / n_groups == mulhi(b & ~63, magic) >> shift for every b < 2^32:
+// q = b >> 6 < 2^26 and d = n_groups <= 2^s: with m = floor(2^(26+s) / d) + 1 = (2^(26+s) + e) / d, 0 < e <= d, q m / 2^(26+s) = q/d + q e / (d 2^(26+s)) and
+// q e < 2^(26+s), so the floor is floor(q / d); m < 2^27 + 1.  q m / 2^26 is the high word of (q << 6) m.
+__host__ __device__ inline void group_quotient_magic(uint32_t n_groups, uint32_t& magic, uint32_t& shift)
+{
+    const uint32_t d = n_groups ? n_groups : 1u;
+    uint32_t s = 0;
+    while (((uint64_t)1 << s) < d) ++s;
+    shift = s;
+    magic = (uint32_t)((((uint64_t)1 << (26u + s)) / d) + 1u);
+}
 __host__ __device__ inline ProjLaunch make_proj_launch(Geom gg, const HostMat34& b2l, int b2l_identity, size_t M)
 {
     ProjLaunch pl;
@@ -72,13 +83,7 @@ __host__ __device__ inline ProjLaunch make_proj_launch(Geom gg, const HostMat34&
     const size_t per_block = (size_t)kBlock * 16;
     pl.n_tiles = (uint32_t)((M + per_block - 1) / per_block);
     pl.n_tg = (pl.n_tiles + 7u) >> 3;
-    // q = b >> 6 < 2^26 and d = n_tg <= 2^s: with m = floor(2^(26+s) / d) + 1 = (2^(26+s) + e) / d, 0 < e <= d, q m / 2^(26+s) = q/d + q e / (d 2^(26+s)) and
-    // q e < 2^(26+s), so the floor is floor(q / d); m < 2^27 + 1.  q m / 2^26 is the high word of (q << 6) m.
-    const uint32_t d = pl.n_tg ? pl.n_tg : 1u;
-    uint32_t s = 0;
-    while (((uint64_t)1 << s) < d) ++s;
-    pl.tg_shift = s;
-    pl.tg_magic = (uint32_t)((((uint64_t)1 << (26u + s)) / d) + 1u);
+    group_quotient_magic(pl.n_tg, pl.tg_magic, pl.tg_shift);
     return pl;
 }
 
@@ -106,6 +111,39 @@ static inline unsigned tile_kf_grid(size_t n_tiles, size_t nb)
     const size_t n_tg = (n_tiles + 7) / 8, n_kg = (nb + kKfPerTile - 1) / kKfPerTile;
     return (unsigned)(n_tg * 8 * kKfPerTile * n_kg);
 }
+
+// The vote kernel's form of the mapping: a workgroup takes a RUN of T consecutive map tiles for one keyframe, so what depends on the keyframe only (pose,
+// image bases, the LDS pixel table and its flush) is paid once per run.  Run r covers tiles [r T, min((r + 1) T, n_tiles)); the runs take the place
+// of the tiles in the mapping above (same XCD placement, same 8 keyframes per run on an XCD), so T = 1 is tile_kf_of_block.
+static constexpr uint32_t kMaxTileRun = 16;    // the deferred-survivor queue holds (tile in run) << 12 | (point in tile) in 16 bits
+struct RunLaunch {
+    uint32_t T;                        // tiles per run, 1 .. kMaxTileRun
+    uint32_t n_runs, n_rg;             // runs of T tiles, groups of 8 runs
+    uint32_t rg_magic, rg_shift;       // (b >> 6) / n_rg, see group_quotient_magic
+};
+__host__ __device__ inline RunLaunch make_run_launch(uint32_t n_tiles, uint32_t T)
+{
+    RunLaunch rl;
+    rl.T = T < 1u ? 1u : (T > kMaxTileRun ? kMaxTileRun : T);
+    rl.n_runs = n_tiles / rl.T + (n_tiles % rl.T ? 1u : 0u);
+    rl.n_rg = (rl.n_runs + 7u) >> 3;
+    group_quotient_magic(rl.n_rg, rl.rg_magic, rl.rg_shift);
+    return rl;
+}
+struct RunKf { uint32_t run, kfb; bool valid; };
+__host__ __device__ inline RunKf run_kf_of_block(uint32_t b, const RunLaunch& rl, uint32_t nb)
+{
+    static_assert(kKfPerTile == 8, "the shifts below are log2(8 XCDs) + log2(kKfPerTile)");
+    const uint32_t x = b & 7u, kfl = (b >> 3) & (kKfPerTile - 1u), q = b >> 6;
+    const uint32_t kg = (uint32_t)(((uint64_t)(b & ~63u) * rl.rg_magic) >> 32) >> rl.rg_shift;
+    const uint32_t rg = q - kg * rl.n_rg;
+    RunKf t;
+    t.run = rg * 8u + x;
+    t.kfb = kg * kKfPerTile + kfl;
+    t.valid = (t.run < rl.n_runs) & (t.kfb < nb);
+    return t;
+}
+static inline unsigned run_kf_grid(const RunLaunch& rl, size_t nb) { return tile_kf_grid(rl.n_runs, nb); }
 
 inline unsigned grid_for(size_t n, int block = kBlock)
 {
