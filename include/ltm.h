@@ -622,6 +622,12 @@ int ltm_debug_proj_launch(float vfov, float hfov, float res_alpha, const double*
  * the run length after clamping and the grid size.  Needs no context and no device; exact for every block index below 2^32. */
 int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_run, uint32_t first_block, size_t n_blocks, uint32_t* out_run, uint32_t* out_kf,
                               uint32_t* out_run_len, uint32_t* out_grid);
+/* The survivor queue word of k_vote_map_cull carries a pixel as a linear index in 18 bits (all ones: pixel not certain); row and column come back from it
+ * as row = mulhi(px << 6, magic) >> shift, col = px - row * cols.  For the image shape a fresh context derives from (vfov, hfov, res_alpha):
+ *   out_u32[8] = rows, cols, rows * cols, 1 if the shape may take the kernel's fast path (rows * cols <= out_u32[7]), magic, shift, pixel bits (18),
+ *                largest rows * cols of the fast path (2^18 - 1)
+ * and the row and column the kernel derives from each of px[0 .. n_px) (every px below 2^26, the quotient's domain).  Needs no context and no device. */
+int ltm_debug_vote_queue_word(float vfov, float hfov, float res_alpha, uint32_t* out_u32, size_t n_px, const uint32_t* px, uint32_t* out_row, uint32_t* out_col);
 /* checks the bounded-error projection that the range-culled vote kernel uses to decide which points need the exact
  * arithmetic: counts points (host xyz, n*3 floats; global frame if inv_pose16 is given, else local) whose exact pixel /
  * range fall outside its candidate set / bounds.  Must be 0. */

@@ -168,6 +168,7 @@ SIGNATURES = {
     "ltm_debug_cull_stats": (_i, [_vp, _pu64, _pu64, _i]),
     "ltm_debug_proj_launch": (_i, [_f, _f, _f, _vp, _sz, _sz, _i, _vp, _vp, C.c_uint32, _sz, _vp, _vp]),
     "ltm_debug_vote_run_launch": (_i, [_sz, _sz, _i, C.c_uint32, _sz, _vp, _vp, _vp, _vp]),
+    "ltm_debug_vote_queue_word": (_i, [C.c_float, C.c_float, C.c_float, _vp, _sz, _vp, _vp, _vp]),
     "ltm_debug_cull_validation": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_occlusion_stats": (_i, [_vp, _pu64, _pu64, _pu64, _i]),
     "ltm_debug_voxel_stats": (_i, [_vp, _pu64, _pu64, _i]),
@@ -251,6 +252,23 @@ def vote_run_launch(map_points, n_keyframes, tile_run, first_block=0, n_blocks=0
     if rc != 0:
         raise LtmError(rc, "ltm_debug_vote_run_launch")
     return run[:n_blocks], kf[:n_blocks], run_len.value, grid.value
+
+
+VOTE_QUEUE_WORD_U32 = ("rows", "cols", "npx", "fast_path", "px_magic", "px_shift", "px_bits", "npx_limit")
+
+
+def vote_queue_word(vfov, hfov, alpha, px=None):
+    """ltm_debug_vote_queue_word: ({name: int}, row[n], col[n]) -- the pixel field of the range-culled vote kernel's survivor queue word for the image
+    shape of (vfov, hfov, alpha), and the row and column the kernel derives from the pixel indices `px`.  Needs no context and no device."""
+    u = np.zeros(len(VOTE_QUEUE_WORD_U32), dtype=np.uint32)
+    p = np.ascontiguousarray(np.zeros(0) if px is None else px, dtype=np.uint32)
+    row = np.zeros(max(len(p), 1), dtype=np.uint32)
+    col = np.zeros(max(len(p), 1), dtype=np.uint32)
+    rc = load_library().ltm_debug_vote_queue_word(float(vfov), float(hfov), float(alpha), u.ctypes.data, len(p), p.ctypes.data if len(p) else None,
+                                                  row.ctypes.data, col.ctypes.data)
+    if rc != 0:
+        raise LtmError(rc, "ltm_debug_vote_queue_word")
+    return {k: int(v) for k, v in zip(VOTE_QUEUE_WORD_U32, u)}, row[:len(p)], col[:len(p)]
 
 
 def inverse4x4(m):

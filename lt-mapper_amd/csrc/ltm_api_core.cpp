@@ -244,7 +244,7 @@ int ltm_create(const ltm_config* cfg, ltm_ctx** out)
     c->kopts.map_kernel_variant = env_int("LTM_MAP_KERNEL", 2);
     c->kopts.vote_cull = env_int("LTM_VOTE_CULL", 1);
     c->kopts.tile_cull = env_int("LTM_TILE_CULL", 1);
-    c->kopts.vote_tile_run = std::min(std::max(env_int("LTM_VOTE_TILE_RUN", 4), 1), 16);
+    c->kopts.vote_tile_run = std::min(std::max(env_int("LTM_VOTE_TILE_RUN", 4), 1), 16);      // 4: the best of 1 / 2 / 4 / 8 / 16 with the wave-private queues too
     c->kopts.stats_blockmin = env_int("LTM_STATS_BLOCKMIN", 0);
     // Exhaustive (2^32 inputs, a few ms) device check of the fast rad2deg / divide-by-FOV forms for THIS context's
     // constants; they are enabled only if they reproduce the exact IEEE results for every input.

@@ -624,6 +624,20 @@ int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_ru
     return LTM_OK;
 }
 
+int ltm_debug_vote_queue_word(float vfov, float hfov, float alpha, uint32_t* out_u32, size_t n_px, const uint32_t* px, uint32_t* out_row, uint32_t* out_col)
+{
+    if (!(vfov > 0.0f) || !(hfov > 0.0f) || !(alpha > 0.0f) || !out_u32 || (n_px && (!px || !out_row || !out_col))) return LTM_E_INVALID;
+    float el_c[4];
+    double err = 0.0;
+    const int el_fit = elevation_fit_for(vfov, el_c, &err);
+    const Geom g = geom_from(vfov, hfov, alpha, 0, el_fit, el_c, 0.0f, 1.0e-3f);      // as ltm_debug_proj_launch
+    if (g.rows <= 0 || g.cols <= 0) return LTM_E_INVALID;
+    for (size_t i = 0; i < n_px; ++i)
+        if (px[i] >= (1u << 26)) return LTM_E_INVALID;      // the domain of the multiply-high quotient
+    vote_queue_word_debug(g, out_u32, n_px, px, out_row, out_col);
+    return LTM_OK;
+}
+
 int ltm_debug_cull_stats(ltm_ctx* c, uint64_t* survivors, uint64_t* points, int reset)
 {
     return guarded(c, [&] {

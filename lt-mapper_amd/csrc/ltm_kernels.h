@@ -52,7 +52,7 @@ struct KernelOpts {
     int map_kernel_variant = 2;   // LTM_MAP_KERNEL   exact arg-min image: 0 one global atomic per point, 1 LDS pre-reduction, 2 + workgroup-local arg-min pre-filter
     int vote_cull = 1;            // LTM_VOTE_CULL    1: mode-0 votes use k_vote_map_cull, 0: the exact-image kernel
     int tile_cull = 1;            // LTM_TILE_CULL    whole-tile range cull inside k_vote_map_cull
-    int vote_tile_run = 4;        // LTM_VOTE_TILE_RUN  consecutive map tiles that one workgroup of k_vote_map_cull takes for its keyframe (1 .. 16; 1, 2 and 8 measured slower)
+    int vote_tile_run = 4;        // LTM_VOTE_TILE_RUN  consecutive map tiles that one workgroup of k_vote_map_cull takes for its keyframe (1 .. 16; 1, 2, 8 and 16 measured slower, profiles/vote_wave_queue_ab_kernels.txt)
     int stats_blockmin = 0;       // LTM_STATS_BLOCKMIN  ltm_debug_cull_stats reports the exact-image kernel's survivor counts instead of the vote kernel's
 };
 // transformGlobalMapToLocal + map2RangeImg: map_img[(kf-kb)*npx+px] = min (range_bits<<32 | idx)
@@ -89,6 +89,10 @@ void proj_launch_blocks(size_t M, size_t nb, uint32_t first_block, size_t n, uin
 // length after clamping, and the grid size as its return value
 size_t vote_run_blocks(size_t M, size_t nb, int tile_run);
 unsigned vote_run_launch_blocks(size_t M, size_t nb, int tile_run, uint32_t first_block, size_t n, uint32_t* run, uint32_t* kf, uint32_t* run_len);
+// debug (ltm_debug_vote_queue_word): u = rows, cols, rows * cols, fast path allowed, pixel-divisor magic, shift, pixel bits, largest rows * cols of the fast path;
+// row / col of the pixel indices px[0 .. n) as the kernel's drain derives them
+static constexpr int kVoteQueueWords = 8;
+void vote_queue_word_debug(Geom g, uint32_t* u, size_t n, const uint32_t* px, uint32_t* row, uint32_t* col);
 hipError_t cull_stats(unsigned long long* out2, int reset, hipStream_t s, int which_kernel);   // {survivors, points} since the last reset; 0 vote kernel, 1 exact-image kernel
 hipError_t cull_check(const float* xyz_dev, size_t n, const HostMat34* T, const HostMat34* b2l, int b2l_identity, const float* approx_pose_dev,
                       Geom g, unsigned long long* bad_dev, hipStream_t s);

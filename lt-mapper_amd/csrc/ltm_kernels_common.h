@@ -50,8 +50,24 @@ struct ProjLaunch {
     uint32_t n_tiles, n_tg;            // 4096-point map tiles, groups of 8 tiles (tile_kf_of_block)
     uint32_t tg_magic, tg_shift;       // (b >> 6) / n_tg == mulhi(b & ~63, tg_magic) >> tg_shift for every b < 2^32
     bool steep_clamps;                 // vfov < 88: every elevation beyond +-45 deg clamps into the first / last row
-    bool packable;                     // rows < 511 and cols <= 2048: row and column fit the 9 + 11 bits of a queue word
+    bool packable;                     // rows < 511 and cols <= 2048: row and column fit the 9 + 11 bits of a queue word (k_map_rimg_blockmin)
+    // k_vote_map_cull's queue word carries the pixel as a linear index in kVoteQueuePxBits bits, all ones = "pixel not certain":
+    bool vote_queueable;               // npx <= kVoteQueuePxLimit, i.e. every pixel index is below the all-ones value; other shapes take the exact path per tile
+    uint32_t px_magic, px_shift;       // px / cols == mulhi(px << 6, px_magic) >> px_shift for every px < 2^26 (group_quotient_magic with d = cols): the row of a queued pixel
 };
+// The queue word of k_vote_map_cull: (tile in run) 4 bits | (group of 256 points in the tile) 4 bits | lane 6 bits | pixel 18 bits.  The wave is implied: a wave
+// drains only what it queued.  The field widths do not depend on the run length, so neither does the condition: npx <= 2^18 - 1 = 262143 (the largest
+// pixel index npx - 1 stays below the all-ones value).  With hfov 360 that admits vfov 50 up to alpha 1372 / 360 = 3.811 (191 x 1372 = 262052; 191 x 1373 = 262243
+// is the first shape that does not fit) and vfov 90 x 2.5 (225 x 900 = 202500); the shipped workloads use vfov 50 with alpha <= 2.5 (125 x 900 = 112500).
+static constexpr uint32_t kVoteQueuePxBits = 18u;
+static constexpr uint32_t kVoteQueuePxUncertain = (1u << kVoteQueuePxBits) - 1u;
+static constexpr uint32_t kVoteQueuePxLimit = kVoteQueuePxUncertain;      // largest npx of the fast path
+// row and column of a queued pixel index: one multiply-high, one shift, one multiply-subtract (px < 2^18 << 2^26, so group_quotient_magic's proof covers it)
+__host__ __device__ inline void vote_queue_row_col(uint32_t px, uint32_t cols, uint32_t px_magic, uint32_t px_shift, uint32_t& row, uint32_t& col)
+{
+    row = (uint32_t)(((uint64_t)(px << 6) * px_magic) >> 32) >> px_shift;
+    col = px - row * cols;
+}
 // (b >> 6) / n_groups == mulhi(b & ~63, magic) >> shift for every b < 2^32:
 // q = b >> 6 < 2^26 and d = n_groups <= 2^s: with m = floor(2^(26+s) / d) + 1 = (2^(26+s) + e) / d, 0 < e <= d, q m / 2^(26+s) = q/d + q e / (d 2^(26+s)) and
 // q e < 2^(26+s), so the floor is floor(q / d); m < 2^27 + 1.  q m / 2^26 is the high word of (q << 6) m.
@@ -80,6 +96,8 @@ __host__ __device__ inline ProjLaunch make_proj_launch(Geom gg, const HostMat34&
     pl.npx = (uint32_t)(g.rows * g.cols);
     pl.steep_clamps = g.vfov < 88.0f;
     pl.packable = g.rows < 511 && g.cols <= 2048;
+    pl.vote_queueable = g.rows > 0 && g.cols > 0 && (uint64_t)g.rows * (uint64_t)g.cols <= kVoteQueuePxLimit;
+    group_quotient_magic((uint32_t)g.cols, pl.px_magic, pl.px_shift);
     const size_t per_block = (size_t)kBlock * 16;
     pl.n_tiles = (uint32_t)((M + per_block - 1) / per_block);
     pl.n_tg = (pl.n_tiles + 7u) >> 3;
