@@ -619,7 +619,13 @@ int ltm_debug_proj_launch(float vfov, float hfov, float res_alpha, const double*
  * for one keyframe (context switch LTM_VOTE_TILE_RUN, 1 .. 16, default 4, read by ltm_create; 1 = one tile per workgroup, the mapping
  * ltm_debug_proj_launch reports).  Run r covers tiles [r * run_len, min((r + 1) * run_len, n_tiles)).  For the workgroups [first_block, first_block + n_blocks) of a launch over
  * `map_points` points and `n_keyframes` keyframes: the run and the keyframe each one works on (0xffffffff in both for a workgroup with nothing to do),
- * the run length after clamping and the grid size.  Needs no context and no device; exact for every block index below 2^32. */
+ * the run length after clamping and the grid size.  Needs no context and no device; exact for every block index below 2^32.
+ * The plain launch of the exact arg-min image kernel (reprojection, mode-1 votes; k_map_rimg_blockmin_run) uses the same mapping with a run length of its own:
+ * context switch LTM_MAP_TILE_RUN, 1 .. 16, read by ltm_create (pass it as `tile_run` to see that launch's mapping); when it is not given the run
+ * length is 2, halved for a launch that would keep fewer than 16384 workgroups.  Images, labels and reprojected
+ * scans are the same bits for every value.  Two A/B switches of that kernel, also read by ltm_create: LTM_MAP_TILE_PERSIST=0 flushes and resets its LDS tables
+ * behind every tile of a run, LTM_MAP_TILE_BARRIER=1 puts a barrier between the two halves of its pre-filter; both measured slower.  The list-driven launch
+ * behind the occlusion cull keeps one (tile, keyframe) pair per workgroup. */
 int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_run, uint32_t first_block, size_t n_blocks, uint32_t* out_run, uint32_t* out_kf,
                               uint32_t* out_run_len, uint32_t* out_grid);
 /* The survivor queue word of k_vote_map_cull carries a pixel as a linear index in 18 bits (all ones: pixel not certain); row and column come back from it

@@ -245,6 +245,9 @@ int ltm_create(const ltm_config* cfg, ltm_ctx** out)
     c->kopts.vote_cull = env_int("LTM_VOTE_CULL", 1);
     c->kopts.tile_cull = env_int("LTM_TILE_CULL", 1);
     c->kopts.vote_tile_run = std::min(std::max(env_int("LTM_VOTE_TILE_RUN", 4), 1), 16);      // 4: the best of 1 / 2 / 4 / 8 / 16 with the wave-private queues too
+    c->kopts.map_tile_run = getenv("LTM_MAP_TILE_RUN") ? std::min(std::max(env_int("LTM_MAP_TILE_RUN", 4), 1), 16) : 0;      // 0: chosen per launch (map_range_images), 2 unless the launch is short
+    c->kopts.map_tile_persist = env_int("LTM_MAP_TILE_PERSIST", 1);
+    c->kopts.map_tile_barrier = env_int("LTM_MAP_TILE_BARRIER", 0);
     c->kopts.stats_blockmin = env_int("LTM_STATS_BLOCKMIN", 0);
     // Exhaustive (2^32 inputs, a few ms) device check of the fast rad2deg / divide-by-FOV forms for THIS context's
     // constants; they are enabled only if they reproduce the exact IEEE results for every input.

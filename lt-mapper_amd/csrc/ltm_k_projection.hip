@@ -1028,6 +1028,241 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
     }
 }
 
+// The plain launch of the same pre-filter: one workgroup = a run of rl.T consecutive tiles against one keyframe (RunLaunch, as k_vote_map_cull), so the mapping,
+// the image and pose pointers, the initialisation of the three tables, the fp64 pose, the flush and the statistics sample are paid once per run.  tags / vals
+// live for the run (a slot never changes owner), and so does amin: a bound published by an earlier tile comes from a real map point of the same exact
+// pixel, so a strictly farther point of a later tile is no arg-min either.  amin therefore has LDS of its own (4 KB more); the queues pay for it.
+// Each wave queues the survivors of its own lanes in its own segment and counts them in a scalar register (no shared counter); it gives them their exact
+// range, on full 64-lane iterations and without a barrier, when a group of 4 x 64 points does not fit what is left of the segment, and once behind the
+// run's last tile.  A segment always takes a group behind a drain (<= 256 words), so no tile ever falls back to the exact path for lack of room.
+// The points of the next group of 4 x 256 -- of the next tile behind a tile's last group -- are requested before the arithmetic of the current one.
+// The queue word is the vote kernel's (tile in run 4 | point group 4 | lane 6 | linear pixel 18, all ones = pixel not certain): fast path iff
+// ProjLaunch::vote_queueable, else every tile takes the whole-tile exact path like the partial last tile and a keyframe without a usable approximate pose
+// (map_range_images sends the shapes that fit the one-tile kernel's record but not this word to the one-tile kernel instead).
+// 8 KB vals + 4 tags + 4 amin + 5.9 queue + 0.5 uqueue = 22.4 KB: 7 workgroups per CU as the one-tile kernel, and 72 VGPRs for 7 waves per SIMD.
+// What was measured (profiles/blockmin_tile_run_ab_kernels.txt, NOTEBOOK): T = 4 best on the lot workload's full-map launches, T = 2 on the street's (the default); the tables kept over the run beat a reset per tile although more
+// pixels compete for the 1024 slots (survivors 8.7 % -> 14.6 %); without the barrier between phase 1a and 1b a wave tests against what is published so far,
+// keeps 0.1 % more survivors and the launch is 2.5 % faster.
+static constexpr uint32_t kBmRunSeg = 376;      // queue words per wave
+static constexpr int kBmRunUQueue = 256;        // uncertain-pixel survivors of a run that wait for its end; a ticket past it is served on the spot
+static constexpr uint32_t kBmRunDefaultT = 2;    // tiles per run when LTM_MAP_TILE_RUN is not given.  Full-map launches of the lot workload: 8.51 ms at 2, 8.34 at 4 (10.29 the one-tile kernel); the plain launches of a street step: 34.3 ms at 2, 34.8 at 1, 39.4 at 4 (37.2 the one-tile kernel) -- 2 is the one value that wins on both
+static constexpr uint64_t kBmRunMinBlocks = 16384;   // ... and the workgroups a launch keeps at least (map_range_images); one choice, about nine times what the device holds at once, not swept
+static constexpr uint32_t kBmRunNoBarrier = 1u, kBmRunResetPerTile = 2u;      // KernelOpts::map_tile_barrier / map_tile_persist, see flags below
+
+// flags: kBmRunNoBarrier (the default) -- no barrier between a tile's phase 1a and 1b: a wave tests against what the others have published so far (a superset
+//        survives); kBmRunResetPerTile (A/B form) -- the tables do not outlive a tile: drain, flush and re-initialise behind every tile (two more barriers per tile)
+template <bool B2L_IDENTITY, bool EL3>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(7, 7)))      // 7 workgroups per CU by LDS: 72 VGPRs
+k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, const float* __restrict__ approx_poses,
+                        uint32_t kb, uint32_t nb, HostMat34 b2l_h, ProjLaunch pl, RunLaunch rl, uint32_t flags, uint64_t* __restrict__ img)
+{
+    constexpr int kRows = 16, kSlots = kRows * 64;
+    static_assert(kSlots <= kBmSlotsMax, "");
+    __shared__ uint64_t vals[kSlots];
+    __shared__ uint32_t tags[kSlots];
+    __shared__ uint32_t amin[kSlots];
+    __shared__ uint32_t queue[kBmRunSeg * (kBlock / 64)];
+    __shared__ uint16_t uqueue[kBmRunUQueue];       // (tile in run) << 12 | tile-local index
+    __shared__ uint32_t ucount;
+    static_assert(kMaxTileRun <= 16 && kPtsPerThread == 16 && kBlock == 256, "queue word: 4 bits of tile, 4 of group, 6 of lane; the wave is implied");
+    static_assert(kBmRunSeg >= 4u * 64u && kSlots <= (1 << (32 - kVoteQueuePxBits)), "a group fits an empty segment; slot and pixel share a record");
+    const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
+    const RunKf rk = run_kf_of_block(blockIdx.x, rl, nb);
+    if (!rk.valid) return;
+    const RimgGeom& g = pl.g;
+    const uint32_t kf = kb + rk.kfb;
+    const uint32_t first_tile = rk.run * rl.T;
+    const uint32_t run_base = first_tile * per_block;
+    const uint32_t n_run = min(rl.T, pl.n_tiles - first_tile);      // >= 1: rk.run < rl.n_runs
+    uint64_t* __restrict__ imgk = img + (size_t)rk.kfb * pl.npx;
+    const float* __restrict__ ap = approx_poses + 16 * (size_t)kf;
+    const double* __restrict__ inv_pose = inv_poses + 12 * (size_t)kf;      // (loaded where the exact arithmetic starts)
+    for (int s = threadIdx.x; s < kSlots; s += kBlock) { tags[s] = kEmptyTag; amin[s] = 0x7f800000u; vals[s] = ~0ull; }
+    if (threadIdx.x == 0) ucount = 0;
+    __syncthreads();
+    // Fast path: the full tiles of the run -- all of them, or all but the map's partial last tile -- if the pixels fit the queue word and the approximate pose
+    // is usable (ap[15] != 0.0f as an integer test).  Tiles [0, n_fast) of the run are fast, [n_fast, n_run) take the exact path as a whole.
+    const uint32_t n_full = (first_tile + n_run == pl.n_tiles && (M & (per_block - 1u)) != 0u) ? n_run - 1u : n_run;
+    const uint32_t n_fast = (pl.vote_queueable & ((f2u(ap[15]) << 1) != 0u)) ? n_full : 0u;
+    const float4* __restrict__ mapr = map + run_base;
+    uint32_t* __restrict__ seg = queue + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kBmRunSeg;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave_off = threadIdx.x & 192u;
+    uint32_t nq = 0, nsurv = 0;      // uniform: entries in this wave's segment, survivors it has drained
+    // phase 2, by wave: the exact range of the wave's queued survivors.  No barrier: min is idempotent, a superset of survivors is correct, and the tables
+    // are touched through LDS atomics and reads that tolerate staleness only.
+    auto drain = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the segment's words were written by other lanes of this wave
+        const Mat34 Tinv = load_mat(inv_pose);
+        for (uint32_t q = lane; q < nq; q += 64u) {
+            const uint32_t e = seg[q];
+            const uint32_t off = ((e >> 24) << 8) | wave_off | ((e >> kVoteQueuePxBits) & 63u);
+            const uint32_t px = e & kVoteQueuePxUncertain;
+            if (px == kVoteQueuePxUncertain) {
+                const uint32_t ticket = atomicAdd(&ucount, 1u);
+                if (ticket < (uint32_t)kBmRunUQueue) uqueue[ticket] = (uint16_t)off;
+                else exact_insert<B2L_IDENTITY, kRows, 64>(map, run_base + off, Tinv, b2l_h, g, vals, tags, imgk);
+                continue;
+            }
+            const uint32_t i = run_base + off;
+            uint32_t row, col;
+            vote_queue_row_col(px, (uint32_t)g.cols, pl.px_magic, pl.px_shift, row, col);
+            const uint64_t v = ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i;
+            const int slot = table_claim<kRows, 64>(tags, (int)row, (int)col, px);
+            if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
+            else img_min_u64(imgk + px, v);
+        }
+        nsurv += nq;
+        nq = 0;
+        // the drain's image atomics retire here: the vector memory counter also counts them, and with some still in flight every wait for a point of the
+        // next tile's phase 1a would have to be a wait for all loads in flight (as in k_vote_map_cull)
+        __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) only
+    };
+    float4 nxt[4];                   // the next group of 4 x 256 points, requested before the arithmetic of the current one
+    if (n_fast) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) nxt[u] = mapr[(uint32_t)u * kBlock + threadIdx.x];
+    }
+    // What a lane keeps of its 16 points of a tile between phase 1b's test and the queue: amin slot (bits 18+) | pixel, and one survivor bit each.  A
+    // drain inside a tile (resume) keeps nothing else alive.
+    uint32_t rec[kPtsPerThread];
+    uint32_t svm = 0;
+    bool resume = false;             // uniform: the queue of tile t is being filled from group jstart on, behind a drain
+    uint32_t jstart = 0;
+    for (uint32_t t = 0;;) {
+        const float4* __restrict__ mapt = mapr + t * per_block;
+        // The drain stands once in the code: taken when a group of a tile's survivors does not fit the segment (then the tile's queue is resumed at that
+        // group), behind the run's last tile, and at every tile's top in the A/B form that resets the tables behind every tile.
+        const bool last = t == n_fast;
+        const bool reset = ((flags & kBmRunResetPerTile) != 0u) & (t != 0u) & !resume;
+        if (resume | ((last | reset) & (nq != 0u))) {
+            drain();
+            if (!last) {      // the prefetched points were dropped: requested again behind the drain's full wait
+                const float4* __restrict__ nx = !resume ? mapt : (t + 1u < n_fast ? mapt + per_block : mapt + 12 * kBlock);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) nxt[u] = nx[(uint32_t)u * kBlock + threadIdx.x];
+            }
+        }
+        if (last) break;
+        if (!resume) {
+        if (__builtin_expect(reset, 0)) {
+            __syncthreads();
+            for (int s = threadIdx.x; s < kSlots; s += kBlock) {
+                const uint32_t tg = tags[s];
+                if (tg != kEmptyTag && vals[s] != ~0ull) img_min_u64(imgk + tg, vals[s]);
+                tags[s] = kEmptyTag; amin[s] = 0x7f800000u; vals[s] = ~0ull;
+            }
+            __syncthreads();
+        }
+        // the range lower bound of the points that own an amin slot; -1 for the others, which no table entry can beat (their slot field is 0: any valid index)
+        float rlo[kPtsPerThread];
+        // ---- phase 1a (four points per lane in flight, the next four requested): every point of the tile publishes its range upper bound before the
+        // tile's points are tested
+#pragma unroll
+        for (int j0 = 0; j0 < kPtsPerThread; j0 += 4) {
+            float3 p[4];
+            CullCand cc[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                bool ok;      // (uniform, part of n_fast)
+                p[u] = xform_approx(ap, nxt[u], ok);
+            }
+            // (the request goes out behind the last use of this group's coordinates.  Behind the run's last group the same group is requested once more
+            // and dropped: cheaper than a request under a condition)
+            const float4* __restrict__ nx = j0 < 12 ? mapt + (j0 + 4) * kBlock : (t + 1u < n_fast ? mapt + per_block : mapt + 12 * kBlock);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) nxt[u] = nx[(uint32_t)u * kBlock + threadIdx.x];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cc[u] = cull_candidates<EL3>(pl, p[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + u;
+                const float r_lo = cull_r_lo(cc[u].r2);
+                rlo[j] = -1.0f;
+                const bool certain = !cc[u].unusual & !cc[u].multi & !(cc[u].r2 < pl.rmin2);
+                const uint32_t px = __umul24((uint32_t)cc[u].rb, (uint32_t)g.cols) + (uint32_t)cc[u].cb;
+                rec[j] = certain ? px : kVoteQueuePxUncertain;
+                if (!certain) continue;
+                const int slot = table_claim<kRows, 64>(tags, cc[u].rb, cc[u].cb, px);
+                if (slot < 0) continue;                                    // slot owned by another pixel: survive unconditionally
+                rlo[j] = r_lo;
+                rec[j] |= (uint32_t)slot << kVoteQueuePxBits;
+                // upper bound of the exact range (r_lo = r_approx*(1-1.5e-6)).  amin only ever decreases, so a plain read that is
+                // already smaller makes the (same-address, hence serialised) atomic unnecessary for most points of a pixel
+                const uint32_t hi = f2u(r_lo * (1.0f + 3.5e-6f));
+                if (hi < amin[slot]) atomicMin(&amin[slot], hi);
+            }
+        }
+        if (!(flags & kBmRunNoBarrier)) __syncthreads();      // (A/B form) the one barrier of a tile; a wave may be anywhere else in the run when another one waits here
+        // ---- phase 1b: a point survives unless it owns a slot and some point of the run so far is provably nearer in the same pixel
+        svm = 0;
+#pragma unroll
+        for (int j0 = 0; j0 < kPtsPerThread; j0 += 4) {
+            // the four table reads go out together and nothing branches on them (the slot index is valid whatever the flags say)
+            float am[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) am[u] = u2f(amin[rec[j0 + u] >> kVoteQueuePxBits]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) svm |= (rlo[j0 + u] > am[u]) ? 0u : (1u << (j0 + u));
+        }
+        jstart = 0;
+        }
+        // ---- the survivors' queue words, group by group; a group that does not fit sends the wave to the drain above and back here
+        const uint32_t word = (t << 28) | (lane << kVoteQueuePxBits);
+        resume = false;
+#pragma unroll
+        for (int j0 = 0; j0 < kPtsPerThread; j0 += 4) {
+            if ((uint32_t)j0 < jstart) continue;      // uniform
+            bool sv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) sv[u] = ((svm >> (j0 + u)) & 1u) != 0u;
+            const uint64_t b0 = __builtin_amdgcn_ballot_w64(sv[0]), b1 = __builtin_amdgcn_ballot_w64(sv[1]),
+                           b2 = __builtin_amdgcn_ballot_w64(sv[2]), b3 = __builtin_amdgcn_ballot_w64(sv[3]);
+            const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1), n2 = (uint32_t)__popcll(b2), n3 = (uint32_t)__popcll(b3);
+            const uint32_t total = n0 + n1 + n2 + n3;
+            if (!total) continue;
+            if (__builtin_expect(nq + total > kBmRunSeg, 0)) { jstart = (uint32_t)j0; resume = true; break; }      // decided on the scalar unit; behind a drain total <= 256 fits
+            const uint64_t bal[4] = {b0, b1, b2, b3};
+            const uint32_t off[4] = {nq, nq + n0, nq + n0 + n1, nq + n0 + n1 + n2};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (!sv[u]) continue;
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[u], 0u));
+                seg[off[u] + below] = (word | ((uint32_t)(j0 + u) << 24)) | (rec[j0 + u] & kVoteQueuePxUncertain);
+            }
+            nq += total;
+        }
+        if (!resume) ++t;
+    }
+    // ---- tiles that are not on the fast path: every point takes the exact projection, each thread its own, no barrier
+    if (__builtin_expect(n_fast < n_run, 0)) {
+        const Mat34 Tinv = load_mat(inv_pose);
+        for (uint32_t t = n_fast; t < n_run; ++t) {
+            const uint32_t block_base = run_base + t * per_block;
+            const uint32_t nloc = min(per_block, M - block_base);
+            for (uint32_t li = threadIdx.x; li < nloc; li += kBlock)
+                exact_insert<B2L_IDENTITY, kRows, 64>(map, block_base + li, Tinv, b2l_h, g, vals, tags, imgk);
+            if (nloc == per_block) nsurv += per_block / (kBlock / 64);      // statistics: a full tile down the exact path counts every point as a survivor
+        }
+    }
+    if ((blockIdx.x & 63u) == 0u) {      // sampled diagnostic: the points of the run's full tiles, the survivors per wave
+        if (threadIdx.x == 0) atomicAdd(&g_cull_stats[3], (unsigned long long)(n_full * per_block));
+        if (lane == 0u && nsurv) atomicAdd(&g_cull_stats[2], (unsigned long long)nsurv);
+    }
+    __syncthreads();     // ucount and uqueue are final: every wave is behind its last drain
+    // ---- the uncertain-pixel survivors of the whole run, by all 256 threads
+    const uint32_t nu = min(ucount, (uint32_t)kBmRunUQueue);
+    if (nu) {
+        const Mat34 Tinv = load_mat(inv_pose);
+        for (uint32_t q = threadIdx.x; q < nu; q += kBlock)
+            exact_insert<B2L_IDENTITY, kRows, 64>(map, run_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
+    }
+    __syncthreads();
+    for (int s = threadIdx.x; s < kSlots; s += kBlock) {
+        const uint32_t tg = tags[s];
+        if (tg != kEmptyTag && vals[s] != ~0ull) img_min_u64(imgk + tg, vals[s]);
+    }
+}
 
 
 hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses_dev, const float* approx_poses_dev, size_t kb, size_t nb,
@@ -1035,10 +1270,31 @@ hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses
 {
     if (!M || !nb) return hipSuccess;
     const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);      // once per launch, on the host
-    if (ko.map_kernel_variant >= 2 && approx_poses_dev) {
+    if (ko.map_kernel_variant >= 2 && approx_poses_dev && pl.packable && !pl.vote_queueable) {
+        // An image whose rows and columns fit the one-tile kernel's 9 + 11-bit record but whose pixel count is beyond the run kernel's 18-bit pixel field
+        // (vfov 90 at alpha 3: 270 x 1080 = 291 600): the run kernel would send every tile down the exact path, the one-tile kernel keeps its pre-filter.
         const size_t per_block = (size_t)kBlock * kPtsPerThread;
         dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb));
-#define LTM_LAUNCH_BM(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img, nullptr, 0u, nullptr)
+#define LTM_LAUNCH_BM1(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img, nullptr, 0u, nullptr)
+        const bool el3 = g.el_fit != 0;
+        if (!b2l_identity) { if (el3) LTM_LAUNCH_BM1(false, true); else LTM_LAUNCH_BM1(false, false); }
+        else { if (el3) LTM_LAUNCH_BM1(true, true); else LTM_LAUNCH_BM1(true, false); }
+#undef LTM_LAUNCH_BM1
+        return hipGetLastError();
+    }
+    if (ko.map_kernel_variant >= 2 && approx_poses_dev) {
+        // a run of map_tile_run consecutive tiles per workgroup (the list-driven launch, map_range_images_pairs, keeps the one-tile kernel: its pairs are
+        // sorted by (tile, keyframe) and hold no runs of tiles for one keyframe)
+        // A run of T tiles divides the workgroups of a launch by T.  Unless the run length is given (LTM_MAP_TILE_RUN), a short launch -- one keyframe, a small
+        // map -- halves it until kBmRunMinBlocks workgroups are left, about nine rounds of the 1792 that the device holds at once: with a fixed run of four, the
+        // launches of a step other than the full-map ones were slower than with the one-tile kernel (the shortest 127 -> 211 us in the one-lane trace).
+        uint32_t T = ko.map_tile_run > 0 ? (uint32_t)ko.map_tile_run : kBmRunDefaultT;
+        if (ko.map_tile_run <= 0)
+            while (T > 1u && (uint64_t)((pl.n_tiles + T - 1u) / T) * nb < kBmRunMinBlocks) T >>= 1;
+        const RunLaunch rl = make_run_launch(pl.n_tiles, T);
+        dim3 grid(run_kf_grid(rl, nb));
+        const uint32_t flags = (ko.map_tile_barrier ? 0u : kBmRunNoBarrier) | (ko.map_tile_persist ? 0u : kBmRunResetPerTile);
+#define LTM_LAUNCH_BM(ID, E) k_map_rimg_blockmin_run<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, rl, flags, map_img)
         const bool el3 = g.el_fit != 0;
         if (!b2l_identity) { if (el3) LTM_LAUNCH_BM(false, true); else LTM_LAUNCH_BM(false, false); }
         else { if (el3) LTM_LAUNCH_BM(true, true); else LTM_LAUNCH_BM(true, false); }

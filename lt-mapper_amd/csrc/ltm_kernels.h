@@ -53,7 +53,10 @@ struct KernelOpts {
     int vote_cull = 1;            // LTM_VOTE_CULL    1: mode-0 votes use k_vote_map_cull, 0: the exact-image kernel
     int tile_cull = 1;            // LTM_TILE_CULL    whole-tile range cull inside k_vote_map_cull
     int vote_tile_run = 4;        // LTM_VOTE_TILE_RUN  consecutive map tiles that one workgroup of k_vote_map_cull takes for its keyframe (1 .. 16; 1, 2, 8 and 16 measured slower, profiles/vote_wave_queue_ab_kernels.txt)
-    int stats_blockmin = 0;       // LTM_STATS_BLOCKMIN  ltm_debug_cull_stats reports the exact-image kernel's survivor counts instead of the vote kernel's
+    int map_tile_run = 0;         // LTM_MAP_TILE_RUN  consecutive map tiles that one workgroup of the exact-image kernel's plain launch (k_map_rimg_blockmin_run) takes for its keyframe: 1 .. 16, or 0 (not given) = 2, halved for launches that would keep fewer than 16384 workgroups (4 is 2 % faster on the lot workload's full-map launches and slower than the one-tile kernel on the street's plain launches; 1, 8 and 16 slower on both, profiles/blockmin_tile_run_ab_kernels.txt)
+    int map_tile_persist = 1;     // LTM_MAP_TILE_PERSIST  0: that kernel's tables (pixel owners, range bounds, minima) are flushed and reset behind every tile of a run (A/B form: 9.06 against 8.55 ms)
+    int map_tile_barrier = 0;     // LTM_MAP_TILE_BARRIER  1: a barrier between a tile's phase 1a and 1b in that kernel (A/B form: 8.55 against 8.34 ms per full-map launch)
+    int stats_blockmin = 0;      // LTM_STATS_BLOCKMIN  ltm_debug_cull_stats reports the exact-image kernel's survivor counts instead of the vote kernel's
 };
 // transformGlobalMapToLocal + map2RangeImg: map_img[(kf-kb)*npx+px] = min (range_bits<<32 | idx)
 // inv_poses_dev: 12 doubles per keyframe (3x4 row-major).  b2l: 12 doubles, b2l_identity skips the arithmetic.
