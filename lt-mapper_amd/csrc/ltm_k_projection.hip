@@ -255,61 +255,7 @@ k_map_rimg(const float4* __restrict__ map, size_t M, const double* __restrict__ 
     img_min_u64(img + (size_t)blockIdx.y * (size_t)pl.npx + px, v);
 }
 
-// Same contract as k_map_rimg, with a per-workgroup LDS pre-reduction.  Map points are stored in octree (Morton)
-// order, so the 4096 consecutive points of a workgroup cover a compact patch of the range image and many of
-// them share a pixel: they are first min-reduced in a 2048-slot direct-mapped LDS table (slot = low bits of
-// row/col, 64-bit ds_min), and only one global atomic per touched pixel leaves the CU.  A point whose slot
-// is owned by another pixel goes straight to the global image.  uint64 min is associative and commutative,
-// so the final image is identical to the serial reference result.
-static constexpr int kLdsSlots = 2048;
-static constexpr int kPtsPerThread = 16;
-static constexpr uint32_t kEmptyTag = 0xffffffffu;
-
-// (the XCD-aware workgroup -> (map tile, keyframe) mapping, tile_kf_of_block, is in ltm_kernels_common.h)
-template <bool B2L_IDENTITY>
-__global__ void __launch_bounds__(kBlock)
-k_map_rimg_lds(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, uint32_t kb, uint32_t nb,
-               HostMat34 b2l_h, ProjLaunch pl, uint64_t* __restrict__ img)
-{
-    __shared__ uint64_t vals[kLdsSlots];
-    __shared__ uint32_t tags[kLdsSlots];
-    const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
-    const TileKf tk = tile_kf_of_block(blockIdx.x, pl, nb);
-    if (!tk.valid) return;
-    for (int s = threadIdx.x; s < kLdsSlots; s += kBlock) { tags[s] = kEmptyTag; vals[s] = ~0ull; }
-    __syncthreads();
-    const RimgGeom& g = pl.g;
-    const uint32_t npx = pl.npx;
-    const uint32_t block_base = tk.tile * per_block;
-    const float4* __restrict__ mapb = map + block_base;
-    const uint32_t nloc = min(per_block, M - block_base);
-    const Mat34 Tinv = load_mat(inv_poses + 12 * (size_t)(kb + tk.kfb));
-    uint64_t* __restrict__ imgk = img + (size_t)tk.kfb * npx;
-#pragma unroll 2
-    for (uint32_t li = threadIdx.x; li < nloc; li += kBlock) {
-        const float4 p4 = mapb[li];
-        float3 p = xform(Tinv, make_float3(p4.x, p4.y, p4.z));
-        if (B2L_IDENTITY) p = xform_identity(p); else p = xform(to_dev(b2l_h), p);
-        const Sph s = cart2sph(p.x, p.y, p.z);
-        int row, col;
-        pixel_row_col(g, s.az, s.el, row, col);
-        const uint32_t px = (uint32_t)(row * g.cols + col);
-        const uint64_t v = ((uint64_t)f2u(s.r) << 32) | (uint64_t)(block_base + li);
-        const int slot = ((row & 15) << 7) | (col & 127);
-        uint32_t t = tags[slot];
-        if (t == kEmptyTag) {
-            const uint32_t old = atomicCAS(&tags[slot], kEmptyTag, px);
-            t = (old == kEmptyTag) ? px : old;
-        }
-        if (t == px) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
-        else img_min_u64(imgk + px, v);
-    }
-    __syncthreads();
-    for (int s = threadIdx.x; s < kLdsSlots; s += kBlock) {
-        const uint32_t t = tags[s];
-        if (t != kEmptyTag) img_min_u64(imgk + t, vals[s]);
-    }
-}
+static constexpr int kPtsPerThread = 16;      // a map tile = kBlock * kPtsPerThread = 4096 consecutive points
 
 hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses_dev, const float* approx_poses_dev, size_t kb, size_t nb,
                             HostMat34 b2l, int b2l_identity, Geom g, uint64_t* map_img, hipStream_t s, const KernelOpts& ko);
@@ -323,8 +269,8 @@ hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses
 // Phase 1 (every point): exact fp64 transform, then a bounded-error projection (atan2 within 3e-6 rad, native
 // sqrt) gives the pixel up to +-Geom::cull_eps_px; the point survives if for ANY candidate pixel the scan range exceeds a
 // lower bound of its range by more than thr minus a margin (or if it is in a domain the fast forms do not cover).
-// Survivors (typically 10-20 %) are queued in LDS.  Phase 2: survivors get the exact arithmetic and the same LDS
-// pre-reduction as k_map_rimg_lds.  Labels are identical to the un-culled path (parity tests); the map image is
+// Survivors (typically 10-20 %) are queued in LDS.  Phase 2: survivors get the exact arithmetic and go through the
+// workgroup's pixel table ("building blocks" below: ballot4, drain_segment, exact_tiles, uncertain_tail, table_*).  Labels are identical to the un-culled path (parity tests); the map image is
 // not (culled points are absent), which is why ltm_debug_range_image / reprojection / mode 1 use k_map_rimg_lds.
 
 // rb/cb: the pixel if it is certain; multi: within cull_eps_px of a rounding boundary (candidates r0..r1 x c0..c1, filled by
@@ -433,7 +379,23 @@ __device__ unsigned long long g_cull_stats[4];   // {survivors, points} of k_vot
 
 static constexpr int kCullQueue = 2048;   // survivor queue capacity: four wave-private segments in k_vote_map_cull (drained before they can overflow); one queue per tile in k_map_rimg_blockmin (~370 of 4096 expected, overflow sends the whole tile down the exact path)
 
-// Direct-mapped pixel table of a workgroup: tags[slot] = the pixel that owns the slot (first come), slot = low bits of row / column.
+// ---------------------------------------------------------------------------------------------------------------
+// Building blocks of the tile pipelines (k_map_rimg_lds, k_vote_map_cull, k_map_rimg_blockmin, k_map_rimg_blockmin_run).  The kernels differ in what they select
+// and in their control flow; what reaches an image always comes from exact_insert / exact_range_insert and leaves through table_min / table_flush.
+// Direct-mapped pixel table of a workgroup in LDS: ROWS x COLS slots, slot = low bits of row / column, tags[slot] = the pixel that owns the slot (first
+// come), vals[slot] = the minimum of the 64-bit (range bits << 32 | point index) words of that pixel so far; the exact-image pre-filter keeps a third
+// array beside them, amin[slot] = float bits of the smallest range upper bound published for the pixel (publish_bound).  table_init: pass null for an
+// array that the caller does not (re)initialise.
+static constexpr uint32_t kEmptyTag = 0xffffffffu;
+template <int SLOTS>
+__device__ __forceinline__ void table_init(uint32_t* __restrict__ tags, uint64_t* __restrict__ vals, uint32_t* __restrict__ amin)
+{
+    for (int s = threadIdx.x; s < SLOTS; s += kBlock) {
+        if (tags) tags[s] = kEmptyTag;
+        if (amin) amin[s] = 0x7f800000u;      // +inf
+        if (vals) vals[s] = ~0ull;
+    }
+}
 // Returns the slot if `px` owns it, or -1 (then the caller goes to the global image).  A slot never changes owner.
 // (Tried: a second chance in the (ROWS/2) x (2 COLS) cut of the coordinates.  It turns ~7 % of misses into ~2 % on octree-ordered
 // map tiles, but the extra probe costs as much as the saved global atomics: no change in either kernel.)
@@ -448,9 +410,31 @@ __device__ __forceinline__ int table_claim(uint32_t* __restrict__ tags, int row,
     }
     return (t == px) ? slot : -1;
 }
-
+// v into the minimum of pixel px: through the table if the pixel owns its slot, else straight to the global image.  uint64 min is associative,
+// commutative and idempotent, so the final image does not depend on which way a word takes, on the order, or on a word arriving twice.
+template <int ROWS, int COLS>
+__device__ __forceinline__ void table_min(uint64_t* __restrict__ vals, uint32_t* __restrict__ tags, uint64_t* __restrict__ imgk, int row, int col, uint32_t px,
+                                          uint64_t v)
+{
+    const int slot = table_claim<ROWS, COLS>(tags, row, col, px);
+    // vals only decreases: skip hopeless same-address atomics.  (Workgroup scope is all an LDS word needs, and it keeps the compiler from folding this
+    // atomic and the image's into one flat instruction on a selected address.)
+    if (slot >= 0) { if (v < vals[slot]) __hip_atomic_fetch_min(&vals[slot], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    else img_min_u64(imgk + px, v);
+}
+// One global atomic per touched pixel leaves the CU.  In the exact-image pre-filter a slot is claimed in phase 1a and may never get a word (its points
+// were all dropped): a slot that still holds all ones is skipped.  A minimum with all ones changes nothing in the image, so the test is only a saving
+// there and is harmless in the two kernels whose claimed slots always hold a word.
+template <int SLOTS>
+__device__ __forceinline__ void table_flush(const uint32_t* __restrict__ tags, const uint64_t* __restrict__ vals, uint64_t* __restrict__ imgk)
+{
+    for (int s = threadIdx.x; s < SLOTS; s += kBlock) {
+        const uint32_t t = tags[s];
+        if (t != kEmptyTag && vals[s] != ~0ull) img_min_u64(imgk + t, vals[s]);
+    }
+}
 // exact projection of one map point into image `imgk`, reduced through the workgroup's LDS table
-template <bool B2L_IDENTITY, int SLOTS_R, int SLOTS_C>
+template <bool B2L_IDENTITY, int ROWS, int COLS>
 __device__ __forceinline__ void exact_insert(const float4* __restrict__ map, uint32_t i, const Mat34& Tinv, const HostMat34& b2l_h, const RimgGeom& g,
                                              uint64_t* __restrict__ vals, uint32_t* __restrict__ tags, uint64_t* __restrict__ imgk)
 {
@@ -460,13 +444,8 @@ __device__ __forceinline__ void exact_insert(const float4* __restrict__ map, uin
     const Sph s = cart2sph(p.x, p.y, p.z);
     int row, col;
     pixel_row_col(g, s.az, s.el, row, col);
-    const uint32_t px = (uint32_t)(row * g.cols + col);
-    const uint64_t v = ((uint64_t)f2u(s.r) << 32) | (uint64_t)i;
-    const int slot = table_claim<SLOTS_R, SLOTS_C>(tags, row, col, px);
-    if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
-    else img_min_u64(imgk + px, v);
+    table_min<ROWS, COLS>(vals, tags, imgk, row, col, (uint32_t)(row * g.cols + col), ((uint64_t)f2u(s.r) << 32) | (uint64_t)i);
 }
-
 // Exact range of a map point whose pixel is already certain (single candidate of the bounded-error projection, which
 // ltm_debug_cull_check validates to contain the exact pixel): the reference arithmetic up to sqrtf only --
 // r = sqrtf((x*x + y*y) + z*z) on the float-rounded fp64 transform -- without the atan2f / rad2deg / pixel chain.
@@ -477,6 +456,149 @@ __device__ __forceinline__ uint32_t exact_range_bits(const float4 p4, const Mat3
     if (B2L_IDENTITY) p = xform_identity(p); else p = xform(to_dev(b2l_h), p);
     const float xy = p.x * p.x + p.y * p.y;
     return f2u(__builtin_sqrtf(xy + p.z * p.z));
+}
+// ... and into the minimum of that pixel
+template <bool B2L_IDENTITY, int ROWS, int COLS>
+__device__ __forceinline__ void exact_range_insert(const float4* __restrict__ map, uint32_t i, int row, int col, uint32_t px, const Mat34& Tinv,
+                                                   const HostMat34& b2l_h, uint64_t* __restrict__ vals, uint32_t* __restrict__ tags, uint64_t* __restrict__ imgk)
+{
+    table_min<ROWS, COLS>(vals, tags, imgk, row, col, px, ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i);
+}
+// Queue positions of a group of four points per lane, of which m[u] says which ones are queued: four ballots and their popcounts on the scalar unit,
+// nothing shared with another wave.  The wave's entries of the group are dense and ordered by (u, lane); the caller supplies the base (a count it
+// keeps in a scalar register, or one LDS atomic per wave and group), decides what happens when base + total does not fit, and stores its word at
+// base + ballot4_pos(q, u) for every m[u].  (Letting the compiler aggregate four separate atomicAdd(&count, 1) costs ~40 instructions each.)
+struct Ballot4 { uint64_t b[4]; uint32_t total; };
+__device__ __forceinline__ Ballot4 ballot4(const bool (&m)[4])
+{
+    Ballot4 q;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q.b[u] = __builtin_amdgcn_ballot_w64(m[u]);
+    q.total = (uint32_t)__popcll(q.b[0]) + (uint32_t)__popcll(q.b[1]) + (uint32_t)__popcll(q.b[2]) + (uint32_t)__popcll(q.b[3]);
+    return q;
+}
+__device__ __forceinline__ uint32_t ballot4_pos(const Ballot4& q, int u)
+{
+    uint32_t before = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) before += (w < u) ? (uint32_t)__popcll(q.b[w]) : 0u;
+    return before + __builtin_amdgcn_mbcnt_hi((uint32_t)(q.b[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)q.b[u], 0u));
+}
+// Phase 2 of k_vote_map_cull, by wave: the exact range of the nq survivors queued in the wave's own segment `seg`, 64 per iteration, all lanes active.
+// The word is ltm_kernels_common.h's ( tile in run 4 bits | group 4 | lane 6 | pixel 18; the wave is implied).  Pixel all ones = not
+// certain: the point takes a ticket for the run's shared uqueue (UQ entries of (tile in run) << 12 | tile-local index, served behind the run by
+// uncertain_tail); a ticket past the capacity is served on the spot.  No barrier: min is idempotent, a superset of survivors is correct, and the table
+// is touched through LDS atomics and reads that tolerate staleness only.  (k_map_rimg_blockmin_run has its own copy, `drain`: NOTEBOOK 4.1.)
+template <bool B2L_IDENTITY, int ROWS, int COLS, int UQ>
+__device__ __forceinline__ void drain_segment(const uint32_t* __restrict__ seg, uint32_t nq, const float4* __restrict__ map, uint32_t run_base,
+                                              const double* __restrict__ inv_pose, const HostMat34& b2l_h, const ProjLaunch& pl, uint64_t* __restrict__ vals,
+                                              uint32_t* __restrict__ tags, uint64_t* __restrict__ imgk, uint16_t* __restrict__ uqueue, uint32_t* __restrict__ ucount)
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the segment's words were written by other lanes of this wave
+    const Mat34 Tinv = load_mat(inv_pose);
+    for (uint32_t q = threadIdx.x & 63u; q < nq; q += 64u) {
+        const uint32_t e = seg[q];
+        const uint32_t off = ((e >> 24) << 8) | (threadIdx.x & 192u) | ((e >> kVoteQueuePxBits) & 63u);
+        const uint32_t px = e & kVoteQueuePxUncertain;
+        if (px == kVoteQueuePxUncertain) {
+            const uint32_t ticket = atomicAdd(ucount, 1u);
+            if (ticket < (uint32_t)UQ) uqueue[ticket] = (uint16_t)off;
+            else exact_insert<B2L_IDENTITY, ROWS, COLS>(map, run_base + off, Tinv, b2l_h, pl.g, vals, tags, imgk);
+            continue;
+        }
+        uint32_t row, col;
+        vote_queue_row_col(px, (uint32_t)pl.g.cols, pl.px_magic, pl.px_shift, row, col);
+        exact_range_insert<B2L_IDENTITY, ROWS, COLS>(map, run_base + off, (int)row, (int)col, px, Tinv, b2l_h, vals, tags, imgk);
+    }
+    // The drain's image atomics retire here.  The vector memory counter also counts them, and they may retire out of order with loads: with
+    // some still in flight every wait for a point of phase 1 would have to be a wait for ALL loads in flight, the prefetched ones included.
+    __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) only
+}
+// The uncertain-pixel survivors of a whole run, by all 256 threads, behind the barrier that makes ucount and uqueue final
+template <bool B2L_IDENTITY, int ROWS, int COLS, int UQ>
+__device__ __forceinline__ void uncertain_tail(const uint16_t* __restrict__ uqueue, uint32_t ucount, const float4* __restrict__ map, uint32_t run_base,
+                                               const double* __restrict__ inv_pose, const HostMat34& b2l_h, const RimgGeom& g, uint64_t* __restrict__ vals,
+                                               uint32_t* __restrict__ tags, uint64_t* __restrict__ imgk)
+{
+    const uint32_t nu = min(ucount, (uint32_t)UQ);
+    if (!nu) return;
+    const Mat34 Tinv = load_mat(inv_pose);
+    for (uint32_t q = threadIdx.x; q < nu; q += kBlock)
+        exact_insert<B2L_IDENTITY, ROWS, COLS>(map, run_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
+}
+// The tiles of k_vote_map_cull's run that are not on the fast path (bit t of `tiles` = tile first_tile + t: the partial last tile of the map, a shape the
+// queue word does not hold, a keyframe without a usable approximate pose): every point takes the exact projection, each thread its own, no barrier.
+// Returns the statistics line: a full tile down the exact path counts every point as a survivor (per wave).
+template <bool B2L_IDENTITY, int ROWS, int COLS>
+__device__ __forceinline__ uint32_t exact_tiles(uint32_t tiles, uint32_t first_tile, const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_pose,
+                                                const HostMat34& b2l_h, const RimgGeom& g, uint64_t* __restrict__ vals, uint32_t* __restrict__ tags,
+                                                uint64_t* __restrict__ imgk)
+{
+    const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
+    const Mat34 Tinv = load_mat(inv_pose);
+    uint32_t nsurv = 0;
+    for (; tiles; tiles &= tiles - 1u) {
+        const uint32_t block_base = (first_tile + (uint32_t)__builtin_ctz(tiles)) * per_block;
+        const uint32_t nloc = min(per_block, M - block_base);
+        for (uint32_t li = threadIdx.x; li < nloc; li += kBlock)
+            exact_insert<B2L_IDENTITY, ROWS, COLS>(map, block_base + li, Tinv, b2l_h, g, vals, tags, imgk);
+        if (nloc == per_block) nsurv += per_block / (kBlock / 64);
+    }
+    return nsurv;
+}
+// Phase 1a of the exact-image pre-filter, one point.  pixel_certain: the bounded-error projection has one candidate pixel and the point is inside the
+// fast forms' domain.  publish_bound: such a point, if its pixel px owns its table slot, publishes an UPPER bound of its exact range into amin[slot],
+// puts the slot into its record (rec |= slot << SLOT_SHIFT; each kernel packs the pixel below that in its own way) and returns the LOWER bound of
+// its range.  Every other point returns -1, which no table entry can beat -- it survives unconditionally -- and keeps a slot field of 0, any valid
+// index, so that phase 1b can read amin without a branch.
+__device__ __forceinline__ bool pixel_certain(const ProjLaunch& pl, const CullCand& cc) { return !cc.unusual & !cc.multi & !(cc.r2 < pl.rmin2); }
+template <int ROWS, int COLS, int SLOT_SHIFT>
+__device__ __forceinline__ float publish_bound(const CullCand& cc, bool certain, uint32_t px, uint32_t* __restrict__ tags, uint32_t* __restrict__ amin, uint32_t& rec)
+{
+    const float r_lo = cull_r_lo(cc.r2);
+    if (!certain) return -1.0f;
+    const int slot = table_claim<ROWS, COLS>(tags, cc.rb, cc.cb, px);
+    if (slot < 0) return -1.0f;                                    // slot owned by another pixel
+    rec |= (uint32_t)slot << SLOT_SHIFT;
+    // upper bound of the exact range: r_e <= r_lo (1 + 3e-6) (k_cull_check) and a rounding.  amin only ever decreases, so a plain read that is
+    // already smaller makes the (same-address, hence serialised) atomic unnecessary for most points of a pixel
+    const uint32_t hi = f2u(r_lo * (1.0f + 3.5e-6f));
+    if (hi < amin[slot]) atomicMin(&amin[slot], hi);
+    return r_lo;
+}
+// The <B2L_IDENTITY, EL3> instantiation of a kernel template for a launch (identity extrinsic; fitted elevation polynomial, see cull_candidates)
+#define LTM_LAUNCH_ID_EL3(KERNEL, IDENT, EL3, GRID, STREAM, ...)                                                                                                       \
+    do { if (IDENT) { if (EL3) KERNEL<true, true><<<GRID, dim3(kBlock), 0, STREAM>>>(__VA_ARGS__); else KERNEL<true, false><<<GRID, dim3(kBlock), 0, STREAM>>>(__VA_ARGS__); } \
+         else { if (EL3) KERNEL<false, true><<<GRID, dim3(kBlock), 0, STREAM>>>(__VA_ARGS__); else KERNEL<false, false><<<GRID, dim3(kBlock), 0, STREAM>>>(__VA_ARGS__); }   \
+    } while (0)
+
+// Same contract as k_map_rimg, with a per-workgroup LDS pre-reduction.  Map points are stored in octree (Morton)
+// order, so the 4096 consecutive points of a workgroup cover a compact patch of the range image and many of
+// them share a pixel: they are first min-reduced in a 16 x 128-slot table (building blocks above), so the final image is
+// identical to the serial reference result.
+// (the XCD-aware workgroup -> (map tile, keyframe) mapping, tile_kf_of_block, is in ltm_kernels_common.h)
+static constexpr int kLdsSlots = 2048;
+template <bool B2L_IDENTITY>
+__global__ void __launch_bounds__(kBlock)
+k_map_rimg_lds(const float4* __restrict__ map, uint32_t M, const double* __restrict__ inv_poses, uint32_t kb, uint32_t nb,
+               HostMat34 b2l_h, ProjLaunch pl, uint64_t* __restrict__ img)
+{
+    __shared__ uint64_t vals[kLdsSlots];
+    __shared__ uint32_t tags[kLdsSlots];
+    const uint32_t per_block = (uint32_t)(kBlock * kPtsPerThread);
+    const TileKf tk = tile_kf_of_block(blockIdx.x, pl, nb);
+    if (!tk.valid) return;
+    table_init<kLdsSlots>(tags, vals, nullptr);
+    __syncthreads();
+    const uint32_t block_base = tk.tile * per_block;
+    const uint32_t nloc = min(per_block, M - block_base);
+    const Mat34 Tinv = load_mat(inv_poses + 12 * (size_t)(kb + tk.kfb));
+    uint64_t* __restrict__ imgk = img + (size_t)tk.kfb * pl.npx;
+#pragma unroll 2
+    for (uint32_t li = threadIdx.x; li < nloc; li += kBlock)
+        exact_insert<B2L_IDENTITY, 16, 128>(map, block_base + li, Tinv, b2l_h, pl.g, vals, tags, imgk);
+    __syncthreads();
+    table_flush<kLdsSlots>(tags, vals, imgk);
 }
 
 // Whole-tile range cull: no point of a tile can be nearer to the sensor than the distance from the sensor position to the tile's
@@ -577,7 +699,7 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
         todo = (uint32_t)__builtin_amdgcn_ballot_w64(visit);
     }
     if (!todo) return;
-    for (int s = threadIdx.x; s < kCullSlots; s += kBlock) { tags[s] = kEmptyTag; vals[s] = ~0ull; }
+    table_init<kCullSlots>(tags, vals, nullptr);
     if (threadIdx.x == 0) ucount = 0;
     __syncthreads();      // the only barrier in front of the exact-projection tail: from here to there no wave waits for another
     // Fast path: every full tile, if the image's pixels fit the queue word and the keyframe's approximate pose is usable (ap[15] != 0.0f, as an integer test:
@@ -598,7 +720,6 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
     const float4* __restrict__ mapr = map + run_base;
     uint32_t* __restrict__ seg = queue + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * kSeg;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave_off = threadIdx.x & 192u;
     // ---- the stream.  G counts groups of 4 x 256 points from the run's first point: tile in run = G >> 2, the lane's points of group G are
     // mapr[G * 1024 + u * 256 + threadIdx.x], u = 0..3, and (G << 2 | u) is the tile and group field of the queue word.  Everything the loop carries is uniform.
     bool more = fast != 0u;
@@ -611,34 +732,11 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
         for (int u = 0; u < kInFlight; ++u) nxt[u] = mapr[(G << 10) + (uint32_t)u * kBlock + threadIdx.x];
     }
     for (;;) {
-        // ---- phase 2, by wave: the exact range of this wave's survivors, 64 per iteration.  Taken when another group could overflow the segment, and once
-        // behind the last group.  No barrier in here; the prefetched points are dropped and requested again behind it.
+        // ---- phase 2, by wave: taken when another group could overflow the segment, and once behind the last group; the prefetched points are requested again
         if (__builtin_expect((nq > kDrainAt) | !more, 0)) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the segment's words were written by other lanes of this wave
-            const Mat34 Tinv = load_mat(inv_pose);
-            for (uint32_t q = lane; q < nq; q += 64u) {
-                const uint32_t e = seg[q];
-                const uint32_t off = ((e >> 24) << 8) | wave_off | ((e >> kVoteQueuePxBits) & 63u);
-                const uint32_t px = e & kVoteQueuePxUncertain;
-                if (px == kVoteQueuePxUncertain) {
-                    const uint32_t ticket = atomicAdd(&ucount, 1u);
-                    if (ticket < (uint32_t)kCullQueue) uqueue[ticket] = (uint16_t)off;
-                    else exact_insert<B2L_IDENTITY, 8, 64>(map, run_base + off, Tinv, b2l_h, g, vals, tags, imgk);
-                    continue;
-                }
-                const uint32_t i = run_base + off;
-                uint32_t row, col;
-                vote_queue_row_col(px, (uint32_t)g.cols, pl.px_magic, pl.px_shift, row, col);
-                const uint64_t v = ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i;
-                const int slot = table_claim<8, 64>(tags, (int)row, (int)col, px);
-                if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
-                else img_min_u64(imgk + px, v);
-            }
+            drain_segment<B2L_IDENTITY, 8, 64, kCullQueue>(seg, nq, map, run_base, inv_pose, b2l_h, pl, vals, tags, imgk, uqueue, &ucount);
             nsurv += nq;
             nq = 0;
-            // The drain's image atomics retire here.  The vector memory counter also counts them, and they may retire out of order with loads: with
-            // some still in flight every wait for a point of phase 1 would have to be a wait for ALL loads in flight, the prefetched ones included.
-            __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) only
             if (more) {
 #pragma unroll
                 for (int u = 0; u < kInFlight; ++u) nxt[u] = mapr[(G << 10) + (uint32_t)u * kBlock + threadIdx.x];
@@ -683,49 +781,21 @@ k_vote_map_cull(const float4* __restrict__ map, uint32_t M, const double* __rest
             // one compare decides; empty pixels hold 0
             mt[u] = cc[u].unusual | (cc[u].r2 < q0[u]);
         }
-        // the queue slots of the four points of every lane: ballots and popcounts on the scalar unit, nothing shared with another wave
-        const uint64_t b0 = __builtin_amdgcn_ballot_w64(mt[0]), b1 = __builtin_amdgcn_ballot_w64(mt[1]),
-                       b2 = __builtin_amdgcn_ballot_w64(mt[2]), b3 = __builtin_amdgcn_ballot_w64(mt[3]);
-        const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1), n2 = (uint32_t)__popcll(b2), n3 = (uint32_t)__popcll(b3);
-        const uint32_t total = n0 + n1 + n2 + n3;
-        if (total) {
-            const uint64_t bal[kInFlight] = {b0, b1, b2, b3};
-            const uint32_t off[kInFlight] = {nq, nq + n0, nq + n0 + n1, nq + n0 + n1 + n2};
+        const Ballot4 qg = ballot4(mt);
+        if (qg.total) {
             const uint32_t word = (Gcur << 26) | (lane << kVoteQueuePxBits);
 #pragma unroll
-            for (int u = 0; u < kInFlight; ++u) {
-                if (!mt[u]) continue;
-                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[u], 0u));
-                seg[off[u] + below] = (word | ((uint32_t)u << 24)) | (cc[u].unusual ? kVoteQueuePxUncertain : pxi[u]);
-            }
-            nq += total;      // <= kDrainAt + 64 * kInFlight = kSeg
+            for (int u = 0; u < kInFlight; ++u)
+                if (mt[u]) seg[nq + ballot4_pos(qg, u)] = (word | ((uint32_t)u << 24)) | (cc[u].unusual ? kVoteQueuePxUncertain : pxi[u]);
+            nq += qg.total;      // <= kDrainAt + 64 * kInFlight = kSeg
         }
     }
-    // ---- tiles that are not on the fast path: every point takes the exact projection, each thread its own, no barrier
-    if (__builtin_expect(slow != 0u, 0)) {
-        const Mat34 Tinv = load_mat(inv_pose);
-        for (uint32_t sl = slow; sl; sl &= sl - 1u) {
-            const uint32_t block_base = (first_tile + (uint32_t)__builtin_ctz(sl)) * per_block;
-            const uint32_t nloc = min(per_block, M - block_base);
-            for (uint32_t li = threadIdx.x; li < nloc; li += kBlock)
-                exact_insert<B2L_IDENTITY, 8, 64>(map, block_base + li, Tinv, b2l_h, g, vals, tags, imgk);
-            if (nloc == per_block) nsurv += per_block / (kBlock / 64);      // statistics: a full tile down the exact path counts every point as a survivor
-        }
-    }
+    if (__builtin_expect(slow != 0u, 0)) nsurv += exact_tiles<B2L_IDENTITY, 8, 64>(slow, first_tile, map, M, inv_pose, b2l_h, g, vals, tags, imgk);
     if (sampled && lane == 0u && nsurv) atomicAdd(&g_cull_stats[0], (unsigned long long)nsurv);
     __syncthreads();     // ucount and uqueue are final: every wave is behind its last drain
-    // ---- the uncertain-pixel survivors of the whole run, by all 256 threads
-    const uint32_t nu = min(ucount, (uint32_t)kCullQueue);
-    if (nu) {
-        const Mat34 Tinv = load_mat(inv_pose);
-        for (uint32_t q = threadIdx.x; q < nu; q += kBlock)
-            exact_insert<B2L_IDENTITY, 8, 64>(map, run_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
-    }
+    uncertain_tail<B2L_IDENTITY, 8, 64, kCullQueue>(uqueue, ucount, map, run_base, inv_pose, b2l_h, g, vals, tags, imgk);
     __syncthreads();
-    for (int s = threadIdx.x; s < kCullSlots; s += kBlock) {
-        const uint32_t t = tags[s];
-        if (t != kEmptyTag) img_min_u64(imgk + t, vals[s]);
-    }
+    table_flush<kCullSlots>(tags, vals, imgk);
 }
 
 hipError_t cull_stats(unsigned long long* out2, int reset, hipStream_t s, int which_kernel)
@@ -739,7 +809,6 @@ hipError_t cull_stats(unsigned long long* out2, int reset, hipStream_t s, int wh
     return e == hipSuccess ? hipStreamSynchronize(s) : e;
 }
 
-
 hipError_t vote_map_range_images(const float4* map, size_t M, const double* inv_poses_dev, const float* approx_poses_dev, size_t kb, size_t nb,
                                  HostMat34 b2l, int b2l_identity, Geom g, const float* qbound_img, const float* tile_bounds_dev,
                                  const uint32_t* smax_bits_dev, float thr, int mode, uint64_t* map_img, hipStream_t s, const KernelOpts& ko)
@@ -750,11 +819,8 @@ hipError_t vote_map_range_images(const float4* map, size_t M, const double* inv_
     const RunLaunch rl = make_run_launch(pl.n_tiles, (uint32_t)std::max(ko.vote_tile_run, 1));
     dim3 grid(run_kf_grid(rl, nb));
     const float* tb = (ko.tile_cull && smax_bits_dev) ? tile_bounds_dev : nullptr;
-    const bool el3 = g.el_fit != 0;
-#define LTM_LAUNCH_CULL(ID, E) k_vote_map_cull<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, rl, qbound_img, tb, smax_bits_dev, thr, map_img)
-    if (!b2l_identity) { if (el3) LTM_LAUNCH_CULL(false, true); else LTM_LAUNCH_CULL(false, false); }
-    else { if (el3) LTM_LAUNCH_CULL(true, true); else LTM_LAUNCH_CULL(true, false); }
-#undef LTM_LAUNCH_CULL
+    LTM_LAUNCH_ID_EL3(k_vote_map_cull, b2l_identity, g.el_fit != 0, grid, s, map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, rl,
+                      qbound_img, tb, smax_bits_dev, thr, map_img);
     return hipGetLastError();
 }
 
@@ -846,6 +912,7 @@ hipError_t cull_probe_points(Geom g, size_t n, const HostMat34* pose, float* xyz
 //   phase 1b  a point survives unless its pixel is certain, owns a table slot, and its range LOWER bound exceeds the
 //             table's minimum upper bound (then some other point of the tile is strictly nearer in the same exact pixel);
 //   phase 2   survivors (a few per pixel) get the exact arithmetic and the usual 64-bit LDS/global min.
+// Built from the blocks above: pixel_certain / publish_bound (1a), ballot4 (1b), exact_range_insert / exact_insert (2), table_init / table_flush.
 // The result is bit-identical to k_map_rimg_lds / the serial reference: discarded points are provably not arg-mins.
 static constexpr int kBmSlotsMax = 1024;   // LDS table of the pre-filter: SLOT_ROWS x 64 pixels.  8 rows (8 workgroups per CU instead of 6) were tried: 15.3 ms against 10.3 ms per full-map launch -- the misses of the smaller table cost far more than the occupancy brings
 static constexpr int kBmQueue = 2048;     // survivor queue capacity (~11 % of 4096 expected); overflow: the whole tile goes exact
@@ -853,7 +920,6 @@ static constexpr int kBmQueue = 2048;     // survivor queue capacity (~11 % of 4
 // (needs the full exact projection).  Images with >= 511 rows or >= 2048 columns mark every point that way.
 static constexpr uint32_t kBmRowUncertain = 511u;
 static constexpr int kBmUQueue = 1024;    // dense re-queue of the uncertain survivors (~1 % of the tile); beyond it they are handled in place
-
 
 // pairs != null: workgroup b processes the (tile, keyframe) pair pairs[b] = tile * nb + keyframe (occlusion-culled launch, see exact_images_occlusion_*)
 // (Round 5 tried three restructurings of phase 1 -- a wave-level combine of the lanes of one pixel, a single 64-bit {owner, minimum} table word, and
@@ -889,7 +955,7 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
         tk = tile_kf_of_block(blockIdx.x, pl, nb);
     }
     if (!tk.valid) return;
-    for (int s = threadIdx.x; s < kBmSlots; s += kBlock) { tags[s] = kEmptyTag; amin[s] = 0x7f800000u; }
+    table_init<kBmSlots>(tags, nullptr, amin);
     if (threadIdx.x == 0) { qcount = 0; ucount = 0; }
     __syncthreads();
     const RimgGeom& g = pl.g;
@@ -933,20 +999,9 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + u;
-                const float r_lo = cull_r_lo(cc[u].r2);
-                rlo[j] = -1.0f;
-                const bool certain = !cc[u].unusual & !cc[u].multi & !(cc[u].r2 < pl.rmin2);
+                const bool certain = pixel_certain(pl, cc[u]);
                 rec[j] = ((certain ? (uint32_t)cc[u].rb : kBmRowUncertain) << 11) | (uint32_t)(cc[u].cb & 2047);
-                if (!certain) continue;
-                const uint32_t px = (uint32_t)(cc[u].rb * g.cols + cc[u].cb);
-                const int slot = table_claim<SLOT_ROWS, 64>(tags, cc[u].rb, cc[u].cb, px);
-                if (slot < 0) continue;                                    // slot owned by another pixel: survive unconditionally
-                rlo[j] = r_lo;
-                rec[j] |= (uint32_t)slot << 20;
-                // upper bound of the exact range (r_lo = r_approx*(1-1.5e-6)).  amin only ever decreases, so a plain read that is
-                // already smaller makes the (same-address, hence serialised) atomic unnecessary for most points of a pixel
-                const uint32_t hi = f2u(r_lo * (1.0f + 3.5e-6f));
-                if (hi < amin[slot]) atomicMin(&amin[slot], hi);
+                rlo[j] = publish_bound<SLOT_ROWS, 64, 20>(cc[u], certain, (uint32_t)(cc[u].rb * g.cols + cc[u].cb), tags, amin, rec[j]);
             }
         }
         __syncthreads();
@@ -957,36 +1012,24 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
             // the four table reads go out together and nothing branches on them (the slot index is valid whatever the flags say)
             float am[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                am[u] = u2f(amin[rec[j0 + u] >> 20]);
-            }
+            for (int u = 0; u < 4; ++u) am[u] = u2f(amin[rec[j0 + u] >> 20]);
             bool sv[4];
             const bool quarter_live = ((quarters >> (j0 >> 2)) & 1u) != 0u;
 #pragma unroll
             for (int u = 0; u < 4; ++u) sv[u] = quarter_live & !(rlo[j0 + u] > am[u]);
-            // one LDS atomic per wave and group of four (hand-rolled ballot / mbcnt aggregation: letting the compiler aggregate four separate
-            // atomicAdd(&qcount, 1) costs ~40 instructions each and one of them is taken almost always)
-            const uint64_t b0 = __builtin_amdgcn_ballot_w64(sv[0]), b1 = __builtin_amdgcn_ballot_w64(sv[1]),
-                           b2 = __builtin_amdgcn_ballot_w64(sv[2]), b3 = __builtin_amdgcn_ballot_w64(sv[3]);
-            const uint32_t n0 = (uint32_t)__popcll(b0), n1 = (uint32_t)__popcll(b1), n2 = (uint32_t)__popcll(b2), n3 = (uint32_t)__popcll(b3);
-            const uint32_t total = n0 + n1 + n2 + n3;
-            if (!total) continue;
+            const Ballot4 qg = ballot4(sv);
+            if (!qg.total) continue;
             uint32_t base = 0;
-            if ((threadIdx.x & 63u) == 0u) base = atomicAdd(&qcount, total);
+            if ((threadIdx.x & 63u) == 0u) base = atomicAdd(&qcount, qg.total);      // one LDS atomic per wave and group of four
             base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if (base + total > (uint32_t)kBmQueue) continue;          // overflow, decided on the scalar unit: the whole tile goes exact in phase 2
-            const uint64_t bal[4] = {b0, b1, b2, b3};
-            const uint32_t off[4] = {0u, n0, n0 + n1, n0 + n1 + n2};
+            if (base + qg.total > (uint32_t)kBmQueue) continue;          // overflow, decided on the scalar unit: the whole tile goes exact in phase 2
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (!sv[u]) continue;
-                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[u], 0u));
-                queue[base + off[u] + below] = ((rec[j0 + u] & 0xfffffu) | lane_word) | ((uint32_t)((j0 + u) * kBlock) << 20);
-            }
+            for (int u = 0; u < 4; ++u)
+                if (sv[u]) queue[base + ballot4_pos(qg, u)] = ((rec[j0 + u] & 0xfffffu) | lane_word) | ((uint32_t)((j0 + u) * kBlock) << 20);
         }
     }
     __syncthreads();
-    for (int s = threadIdx.x; s < kBmSlots; s += kBlock) vals[s] = ~0ull;        // amin is dead from here on
+    table_init<kBmSlots>(nullptr, vals, nullptr);        // amin is dead from here on
     __syncthreads();
     // ---- phase 2: survivors.  Certain pixel: only the exact range; the others are re-queued densely and get the full exact projection
     const uint32_t nq = full_tile ? qcount : (uint32_t)kBmQueue + 1u;
@@ -1010,11 +1053,7 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
                 else exact_insert<B2L_IDENTITY, SLOT_ROWS, 64>(map, i, Tinv, b2l_h, g, vals, tags, imgk);
                 continue;
             }
-            const uint32_t px = (uint32_t)(row * g.cols + col);
-            const uint64_t v = ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i;
-            const int slot = table_claim<SLOT_ROWS, 64>(tags, row, col, px);
-            if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
-            else img_min_u64(imgk + px, v);
+            exact_range_insert<B2L_IDENTITY, SLOT_ROWS, 64>(map, i, row, col, (uint32_t)(row * g.cols + col), Tinv, b2l_h, vals, tags, imgk);
         }
         __syncthreads();
         const uint32_t nu = min(ucount, (uint32_t)kBmUQueue);
@@ -1022,27 +1061,21 @@ k_map_rimg_blockmin(const float4* __restrict__ map, uint32_t M, const double* __
             exact_insert<B2L_IDENTITY, SLOT_ROWS, 64>(map, block_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
     }
     __syncthreads();
-    for (int s = threadIdx.x; s < kBmSlots; s += kBlock) {
-        const uint32_t t = tags[s];
-        if (t != kEmptyTag && vals[s] != ~0ull) img_min_u64(imgk + t, vals[s]);
-    }
+    table_flush<kBmSlots>(tags, vals, imgk);
 }
 
 // The plain launch of the same pre-filter: one workgroup = a run of rl.T consecutive tiles against one keyframe (RunLaunch, as k_vote_map_cull), so the mapping,
 // the image and pose pointers, the initialisation of the three tables, the fp64 pose, the flush and the statistics sample are paid once per run.  tags / vals
 // live for the run (a slot never changes owner), and so does amin: a bound published by an earlier tile comes from a real map point of the same exact
 // pixel, so a strictly farther point of a later tile is no arg-min either.  amin therefore has LDS of its own (4 KB more); the queues pay for it.
-// Each wave queues the survivors of its own lanes in its own segment and counts them in a scalar register (no shared counter); it gives them their exact
-// range, on full 64-lane iterations and without a barrier, when a group of 4 x 64 points does not fit what is left of the segment, and once behind the
-// run's last tile.  A segment always takes a group behind a drain (<= 256 words), so no tile ever falls back to the exact path for lack of room.
+// Each wave queues the survivors of its own lanes in its own segment and counts them in a scalar register ; it drains the segment (the vote
+// kernel's queue word) when a group of 4 x 64 points does not fit what is left of it, and once behind the run's last tile.  A segment
+// always takes a group behind a drain (<= 256 words), so no tile ever falls back to the exact path for lack of room.
 // The points of the next group of 4 x 256 -- of the next tile behind a tile's last group -- are requested before the arithmetic of the current one.
-// The queue word is the vote kernel's (tile in run 4 | point group 4 | lane 6 | linear pixel 18, all ones = pixel not certain): fast path iff
-// ProjLaunch::vote_queueable, else every tile takes the whole-tile exact path like the partial last tile and a keyframe without a usable approximate pose
-// (map_range_images sends the shapes that fit the one-tile kernel's record but not this word to the one-tile kernel instead).
+// Fast path iff ProjLaunch::vote_queueable, else every tile takes the whole-tile exact path like the partial last tile and a keyframe without
+// a usable approximate pose (map_range_images sends the shapes that fit the one-tile kernel's record but not the queue word to the one-tile kernel instead).
 // 8 KB vals + 4 tags + 4 amin + 5.9 queue + 0.5 uqueue = 22.4 KB: 7 workgroups per CU as the one-tile kernel, and 72 VGPRs for 7 waves per SIMD.
-// What was measured (profiles/blockmin_tile_run_ab_kernels.txt, NOTEBOOK): T = 4 best on the lot workload's full-map launches, T = 2 on the street's (the default); the tables kept over the run beat a reset per tile although more
-// pixels compete for the 1024 slots (survivors 8.7 % -> 14.6 %); without the barrier between phase 1a and 1b a wave tests against what is published so far,
-// keeps 0.1 % more survivors and the launch is 2.5 % faster.
+// What was measured: NOTEBOOK 4.1, profiles/blockmin_tile_run_ab_kernels.txt.
 static constexpr uint32_t kBmRunSeg = 376;      // queue words per wave
 static constexpr int kBmRunUQueue = 256;        // uncertain-pixel survivors of a run that wait for its end; a ticket past it is served on the spot
 static constexpr uint32_t kBmRunDefaultT = 2;    // tiles per run when LTM_MAP_TILE_RUN is not given.  Full-map launches of the lot workload: 8.51 ms at 2, 8.34 at 4 (10.29 the one-tile kernel); the plain launches of a street step: 34.3 ms at 2, 34.8 at 1, 39.4 at 4 (37.2 the one-tile kernel) -- 2 is the one value that wins on both
@@ -1080,8 +1113,7 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
     for (int s = threadIdx.x; s < kSlots; s += kBlock) { tags[s] = kEmptyTag; amin[s] = 0x7f800000u; vals[s] = ~0ull; }
     if (threadIdx.x == 0) ucount = 0;
     __syncthreads();
-    // Fast path: the full tiles of the run -- all of them, or all but the map's partial last tile -- if the pixels fit the queue word and the approximate pose
-    // is usable (ap[15] != 0.0f as an integer test).  Tiles [0, n_fast) of the run are fast, [n_fast, n_run) take the exact path as a whole.
+    // Fast path as in k_vote_map_cull: tiles [0, n_fast) of the run are fast (all full tiles, or none), [n_fast, n_run) take the exact path as a whole.
     const uint32_t n_full = (first_tile + n_run == pl.n_tiles && (M & (per_block - 1u)) != 0u) ? n_run - 1u : n_run;
     const uint32_t n_fast = (pl.vote_queueable & ((f2u(ap[15]) << 1) != 0u)) ? n_full : 0u;
     const float4* __restrict__ mapr = map + run_base;
@@ -1089,10 +1121,9 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_off = threadIdx.x & 192u;
     uint32_t nq = 0, nsurv = 0;      // uniform: entries in this wave's segment, survivors it has drained
-    // phase 2, by wave: the exact range of the wave's queued survivors.  No barrier: min is idempotent, a superset of survivors is correct, and the tables
-    // are touched through LDS atomics and reads that tolerate staleness only.
+    // phase 2, by wave.  This kernel keeps its own copies of drain_segment and, below, of table_init / table_flush, ballot4 and exact_tiles: NOTEBOOK 4.1
     auto drain = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the segment's words were written by other lanes of this wave
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         const Mat34 Tinv = load_mat(inv_pose);
         for (uint32_t q = lane; q < nq; q += 64u) {
             const uint32_t e = seg[q];
@@ -1109,14 +1140,12 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
             vote_queue_row_col(px, (uint32_t)g.cols, pl.px_magic, pl.px_shift, row, col);
             const uint64_t v = ((uint64_t)exact_range_bits<B2L_IDENTITY>(map[i], Tinv, b2l_h) << 32) | (uint64_t)i;
             const int slot = table_claim<kRows, 64>(tags, (int)row, (int)col, px);
-            if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // vals only decreases: skip hopeless same-address atomics
+            if (slot >= 0) { if (v < vals[slot]) atomicMin(reinterpret_cast<unsigned long long*>(&vals[slot]), (unsigned long long)v); }   // (table_min)
             else img_min_u64(imgk + px, v);
         }
         nsurv += nq;
         nq = 0;
-        // the drain's image atomics retire here: the vector memory counter also counts them, and with some still in flight every wait for a point of the
-        // next tile's phase 1a would have to be a wait for all loads in flight (as in k_vote_map_cull)
-        __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) only
+        __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) only: the drain's image atomics retire here (drain_segment)
     };
     float4 nxt[4];                   // the next group of 4 x 256 points, requested before the arithmetic of the current one
     if (n_fast) {
@@ -1154,8 +1183,7 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
             }
             __syncthreads();
         }
-        // the range lower bound of the points that own an amin slot; -1 for the others, which no table entry can beat (their slot field is 0: any valid index)
-        float rlo[kPtsPerThread];
+        float rlo[kPtsPerThread];      // publish_bound's range lower bounds
         // ---- phase 1a (four points per lane in flight, the next four requested): every point of the tile publishes its range upper bound before the
         // tile's points are tested
 #pragma unroll
@@ -1167,8 +1195,7 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
                 bool ok;      // (uniform, part of n_fast)
                 p[u] = xform_approx(ap, nxt[u], ok);
             }
-            // (the request goes out behind the last use of this group's coordinates.  Behind the run's last group the same group is requested once more
-            // and dropped: cheaper than a request under a condition)
+            // (the request goes out behind the last use of this group's coordinates, as in k_vote_map_cull)
             const float4* __restrict__ nx = j0 < 12 ? mapt + (j0 + 4) * kBlock : (t + 1u < n_fast ? mapt + per_block : mapt + 12 * kBlock);
 #pragma unroll
             for (int u = 0; u < 4; ++u) nxt[u] = nx[(uint32_t)u * kBlock + threadIdx.x];
@@ -1177,20 +1204,10 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + u;
-                const float r_lo = cull_r_lo(cc[u].r2);
-                rlo[j] = -1.0f;
-                const bool certain = !cc[u].unusual & !cc[u].multi & !(cc[u].r2 < pl.rmin2);
+                const bool certain = pixel_certain(pl, cc[u]);
                 const uint32_t px = __umul24((uint32_t)cc[u].rb, (uint32_t)g.cols) + (uint32_t)cc[u].cb;
                 rec[j] = certain ? px : kVoteQueuePxUncertain;
-                if (!certain) continue;
-                const int slot = table_claim<kRows, 64>(tags, cc[u].rb, cc[u].cb, px);
-                if (slot < 0) continue;                                    // slot owned by another pixel: survive unconditionally
-                rlo[j] = r_lo;
-                rec[j] |= (uint32_t)slot << kVoteQueuePxBits;
-                // upper bound of the exact range (r_lo = r_approx*(1-1.5e-6)).  amin only ever decreases, so a plain read that is
-                // already smaller makes the (same-address, hence serialised) atomic unnecessary for most points of a pixel
-                const uint32_t hi = f2u(r_lo * (1.0f + 3.5e-6f));
-                if (hi < amin[slot]) atomicMin(&amin[slot], hi);
+                rlo[j] = publish_bound<kRows, 64, kVoteQueuePxBits>(cc[u], certain, px, tags, amin, rec[j]);
             }
         }
         if (!(flags & kBmRunNoBarrier)) __syncthreads();      // (A/B form) the one barrier of a tile; a wave may be anywhere else in the run when another one waits here
@@ -1198,8 +1215,7 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
         svm = 0;
 #pragma unroll
         for (int j0 = 0; j0 < kPtsPerThread; j0 += 4) {
-            // the four table reads go out together and nothing branches on them (the slot index is valid whatever the flags say)
-            float am[4];
+            float am[4];      // (read together, nothing branches on them, as in k_map_rimg_blockmin)
 #pragma unroll
             for (int u = 0; u < 4; ++u) am[u] = u2f(amin[rec[j0 + u] >> kVoteQueuePxBits]);
 #pragma unroll
@@ -1234,8 +1250,7 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
         }
         if (!resume) ++t;
     }
-    // ---- tiles that are not on the fast path: every point takes the exact projection, each thread its own, no barrier
-    if (__builtin_expect(n_fast < n_run, 0)) {
+    if (__builtin_expect(n_fast < n_run, 0)) {      // ---- tiles that are not on the fast path (as exact_tiles)
         const Mat34 Tinv = load_mat(inv_pose);
         for (uint32_t t = n_fast; t < n_run; ++t) {
             const uint32_t block_base = run_base + t * per_block;
@@ -1250,20 +1265,13 @@ k_map_rimg_blockmin_run(const float4* __restrict__ map, uint32_t M, const double
         if (lane == 0u && nsurv) atomicAdd(&g_cull_stats[2], (unsigned long long)nsurv);
     }
     __syncthreads();     // ucount and uqueue are final: every wave is behind its last drain
-    // ---- the uncertain-pixel survivors of the whole run, by all 256 threads
-    const uint32_t nu = min(ucount, (uint32_t)kBmRunUQueue);
-    if (nu) {
-        const Mat34 Tinv = load_mat(inv_pose);
-        for (uint32_t q = threadIdx.x; q < nu; q += kBlock)
-            exact_insert<B2L_IDENTITY, kRows, 64>(map, run_base + uqueue[q], Tinv, b2l_h, g, vals, tags, imgk);
-    }
+    uncertain_tail<B2L_IDENTITY, kRows, 64, kBmRunUQueue>(uqueue, ucount, map, run_base, inv_pose, b2l_h, g, vals, tags, imgk);
     __syncthreads();
     for (int s = threadIdx.x; s < kSlots; s += kBlock) {
         const uint32_t tg = tags[s];
         if (tg != kEmptyTag && vals[s] != ~0ull) img_min_u64(imgk + tg, vals[s]);
     }
 }
-
 
 hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses_dev, const float* approx_poses_dev, size_t kb, size_t nb,
                             HostMat34 b2l, int b2l_identity, Geom g, uint64_t* map_img, hipStream_t s, const KernelOpts& ko)
@@ -1275,11 +1283,8 @@ hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses
         // (vfov 90 at alpha 3: 270 x 1080 = 291 600): the run kernel would send every tile down the exact path, the one-tile kernel keeps its pre-filter.
         const size_t per_block = (size_t)kBlock * kPtsPerThread;
         dim3 grid(tile_kf_grid((M + per_block - 1) / per_block, nb));
-#define LTM_LAUNCH_BM1(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img, nullptr, 0u, nullptr)
-        const bool el3 = g.el_fit != 0;
-        if (!b2l_identity) { if (el3) LTM_LAUNCH_BM1(false, true); else LTM_LAUNCH_BM1(false, false); }
-        else { if (el3) LTM_LAUNCH_BM1(true, true); else LTM_LAUNCH_BM1(true, false); }
-#undef LTM_LAUNCH_BM1
+        LTM_LAUNCH_ID_EL3(k_map_rimg_blockmin, b2l_identity, g.el_fit != 0, grid, s, map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl,
+                          map_img, nullptr, 0u, nullptr);
         return hipGetLastError();
     }
     if (ko.map_kernel_variant >= 2 && approx_poses_dev) {
@@ -1294,11 +1299,8 @@ hipError_t map_range_images(const float4* map, size_t M, const double* inv_poses
         const RunLaunch rl = make_run_launch(pl.n_tiles, T);
         dim3 grid(run_kf_grid(rl, nb));
         const uint32_t flags = (ko.map_tile_barrier ? 0u : kBmRunNoBarrier) | (ko.map_tile_persist ? 0u : kBmRunResetPerTile);
-#define LTM_LAUNCH_BM(ID, E) k_map_rimg_blockmin_run<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, rl, flags, map_img)
-        const bool el3 = g.el_fit != 0;
-        if (!b2l_identity) { if (el3) LTM_LAUNCH_BM(false, true); else LTM_LAUNCH_BM(false, false); }
-        else { if (el3) LTM_LAUNCH_BM(true, true); else LTM_LAUNCH_BM(true, false); }
-#undef LTM_LAUNCH_BM
+        LTM_LAUNCH_ID_EL3(k_map_rimg_blockmin_run, b2l_identity, g.el_fit != 0, grid, s, map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl,
+                          rl, flags, map_img);
         return hipGetLastError();
     }
     if (ko.map_kernel_variant >= 1) {
@@ -1497,11 +1499,8 @@ hipError_t map_range_images_pairs(const float4* map, size_t M, const double* inv
     if (!n_pairs) return hipSuccess;
     dim3 grid((unsigned)(((n_pairs + 7) / 8) * 8));
     const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, M);
-#define LTM_LAUNCH_BMP(ID, E) k_map_rimg_blockmin<ID, E><<<grid, dim3(kBlock), 0, s>>>(map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl, map_img, pairs, (uint32_t)n_pairs, submask)
-    const bool el3 = g.el_fit != 0;
-    if (!b2l_identity) { if (el3) LTM_LAUNCH_BMP(false, true); else LTM_LAUNCH_BMP(false, false); }
-    else { if (el3) LTM_LAUNCH_BMP(true, true); else LTM_LAUNCH_BMP(true, false); }
-#undef LTM_LAUNCH_BMP
+    LTM_LAUNCH_ID_EL3(k_map_rimg_blockmin, b2l_identity, g.el_fit != 0, grid, s, map, (uint32_t)M, inv_poses_dev, approx_poses_dev, (uint32_t)kb, (uint32_t)nb, b2l, pl,
+                      map_img, pairs, (uint32_t)n_pairs, submask);
     return hipGetLastError();
 }
 
