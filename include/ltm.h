@@ -444,7 +444,7 @@ int  ltm_sc_free(ltm_ctx*, ltm_sc*);
  *  another context is LTM_E_INVALID).  init16_or_null: n_pairs row-major 4x4 doubles whose last row is taken to be 0 0 0 1, NULL = identity.  A NULL
  *  parameter pointer means the defaults.  Each source (< 2^31 points, < 2^31 in all) is copied in sorted order for the call; all device memory comes from
  *  the context's pool and is back when the call returns, on every error path too.  The call returns when the host arrays are written.
- *  The submaps themselves come from the section "loop submaps" below.  Point-to-plane ICP is the next section.  Out of scope: Euler / gtsam::Pose3 conversions and generalized ICP. */
+ *  The submaps themselves come from the section "loop submaps" below.  Point-to-plane and generalized ICP are the next two sections.  Out of scope: Euler / gtsam::Pose3 conversions. */
 typedef struct {
     double max_corr_dist;             /* 150.0  setMaxCorrespondenceDistance, LTslam.cpp:207 */
     int    max_iterations;            /* 100    :208 */
@@ -458,7 +458,7 @@ typedef struct {
     int32_t  converged;      /* hasConverged() */
     int32_t  iterations;
     int32_t  state;          /* why it stopped: 0 too few correspondences / nothing to do, 1 iterations, 2 transform, 3 absolute MSE, 4 relative MSE;
-                                point-to-plane only: 5 degenerate system */
+                                point-to-plane and generalized only: 5 degenerate system */
     uint32_t n_corr;         /* correspondences of the last iteration */
 } ltm_icp_result;
 void ltm_icp_default_params(ltm_icp_params*);     /* host only, needs no device */
@@ -498,6 +498,52 @@ int  ltm_icp_align_plane(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, c
                          const double* init16_or_null, const ltm_icp_params*, ltm_icp_result* results_host, double* trace_host_or_null);
 int  ltm_icp_align_plane_scanset(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf /* n_pairs */,
                                  const double* init16_or_null, const ltm_icp_params*, ltm_icp_result* results_host, double* trace_host_or_null);
+
+/* ------------------------------------------------------ icp, generalized ---- */
+/* The same batch with the plane-to-plane error of generalized ICP (Segal, Haehnel, Thrun; pcl::GeneralizedIterativeClosestPoint), as understood; the
+ * reference does not call it.  ltm_icp_params, ltm_icp_result and the trace are those of ltm_icp_align.  BOTH sides of a pair are search indices
+ * (ltm_search_build or ltm_search_build_scanset; the same handle may serve many pairs and may be the target of one pair and the source of another) and both
+ * must carry normals (ltm_search_estimate_normals, any k; PCL's k_correspondences_ is 20), else LTM_E_INVALID.  gicp_epsilon must be finite and in
+ * (0, 1] (PCL's default 0.001), else LTM_E_INVALID; so are a NULL handle, a handle of another context and NaN parameters.  Two kernel launches per
+ * iteration for the whole batch.  The sources are read in place from their indices: no per-call sort, no copy.  All device memory comes from the
+ * context's pool and is back when the call returns, on every error path too.  tools/icp_gicp_numpy.py restates the arithmetic below and the tests
+ * compare against it.
+ *  The covariances: GICP gives every point the covariance of its neighbourhood with the singular values replaced by (1, 1, epsilon), which is
+ *  C = I - (1 - epsilon) n n^T with n the unit eigenvector of the smallest eigenvalue -- the normal the index already holds (its sign does not matter).
+ *  No covariance is computed or stored: with w = 1 - epsilon, C_B + R C_A R^T = 2I - w (n_b n_b^T + m m^T), m = R n_a.
+ *  The source's points are the finite points of its index (non-finite points are not in an index and so are skipped everywhere, as in "icp").
+ *  Steps 1-3 of an iteration (transform of the ORIGINAL source point by T in double -> float query, exact 1-NN with ties to the smaller target index,
+ *  distance limit), the stop tests, mse, fitness, the trace and the edge cases are those of the section "icp", unchanged.  Then, all in double and
+ *  without fused multiply-adds:
+ *   4. a kept correspondence whose target normal n_b or source normal n_a is not finite is DROPPED: it counts neither in n_corr nor in the mse;
+ *   5. fewer than 3 correspondences: the pair stops, converged = 0, state = 0, as in "icp";
+ *   6. m = R_T n_a, R_T the upper-left 3 x 3 of the current T (taken to be a rotation; an init that is none is undefined in result, not a fault):
+ *        m_r = (T_r0 a_x + T_r1 a_y) + T_r2 a_z;
+ *      S = 2I - w (n_b n_b^T + m m^T), symmetric:  s00 = 2 - w (b_x b_x + m_x m_x), s01 = -w (b_x b_y + m_x m_y), ... s22 = 2 - w (b_z b_z + m_z m_z);
+ *      M = adj(S) / det(S), entry by entry:
+ *        c00 = s11 s22 - s12 s12    c01 = s02 s12 - s01 s22    c02 = s01 s12 - s02 s11
+ *        c11 = s00 s22 - s02 s02    c12 = s01 s02 - s00 s12    c22 = s00 s11 - s01 s01
+ *        det = (s00 c00 + s01 c01) + s02 c02,  M_ij = c_ij * (1 / det)   (M is symmetric and, for unit normals, positive definite: eigenvalues in
+ *        [1/2, 1/(2 epsilon)]);
+ *   7. with the query p and its target point q taken about the pair's origin o (the corner of the target's bounding box), d = q - p and
+ *      A = [-[p]x, I] (3 x 6: A x = omega x p + t' for x = (omega, t')), the pair minimises sum (d - A x)^T M (d - A x) over its correspondences:
+ *      the record is the count, the 21 upper entries of sum A^T M A, the 6 of sum A^T M d and sum d2 (the float d2 of the search) -- the layout of
+ *      the point-to-plane record.  With G = M (-[p]x) and g = M d:  A^T M A = [[p x G_0, p x G_1, p x G_2 | G^T], [G | M]] (G_k the columns of G),
+ *      A^T M d = [p x g, g].  SUMMATION ORDER: the source index's own order (its finite points in the code order of the source's OWN frame, the order
+ *      of its tree) read in place, 256 per partial sum (the 64 points of a wavefront by a butterfly, the four wavefronts in order), partial sums in
+ *      order.  It is a pure function of the pair's two handles: a pair's result does not depend on the rest of the batch, there are no floating-point
+ *      atomics, and a run is bit-reproducible;
+ *   8. solve and update exactly as point-to-plane steps 7-8: Cholesky without pivoting with the relative pivot test (state = 5 when it fails -- with M
+ *      positive definite that needs degenerate geometry, for instance all correspondences on one line; a single exact plane does NOT give state 5
+ *      here, epsilon constrains the in-plane unknowns weakly), x = (alpha, beta, gamma, t'), R = Rz Ry Rx, t = t' + o - R o, T <- [R t] T,
+ *      iterations += 1, the stop tests of "icp".
+ *  DEPARTURES from PCL: PCL minimises the same sum with BFGS over the correspondences of an outer iteration, recomputing M only per outer iteration,
+ *  and keeps float transforms; here it is ONE Gauss-Newton step per correspondence search, about o, with T in double.  PCL computes its own
+ *  covariances from k_correspondences_ neighbours by SVD; here they are those the index's normals imply (the same matrix whenever the smallest
+ *  eigenvalue is simple).  PCL's rotation-epsilon test differs from its ICP's; here the stop tests are those of "icp". */
+int  ltm_icp_align_gicp(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, ltm_search* const* sources,
+                        const double* init16_or_null, const ltm_icp_params*, double gicp_epsilon,
+                        ltm_icp_result* results_host, double* trace_host_or_null);
 
 /* ----------------------------------------------------------- loop submaps ---- */
 /* The step between a loop proposal and its ICP verification: the two clouds of every ICP run of LTslam::doICPVirtualRelative / doICPGlobalRelative
@@ -544,10 +590,10 @@ int ltm_search_build_scanset(ltm_ctx*, ltm_scanset, size_t kf_begin, size_t kf_e
  * :1445-1476 and the six reprojections of :1551-1577.  A LANE is a second context on the parent's device (own stream, own pool, the parent's
  * configuration and create-time self-check) that a second host thread drives; the projection kernels are bound by vector-instruction issue and the
  * grids / kNN stages by launch latency, so the two kinds of work fill each other's gaps.  The library keeps the lanes out of each other's way by
- * itself: the large projection launches of a context and its lanes are chained on the device (one at a time, in the order the hosts submit them) and
- * go to a stream of the lowest priority, so that one lane's partition + grids are dispatched ahead of -- and finish under -- the other lane's
- * projection instead of both lanes projecting together and then idling together.  Results do not depend on the schedule: every kernel sees the same
- * inputs as in the one-lane order.
+ * itself: the large projection launches of a context and its lanes are chained on the device (one at a time, in the order the hosts submit them),
+ * each on its own context's stream -- there is no separate stream and no stream priority --, so that one lane's partition + grids run beside the
+ * other lane's projection instead of both lanes projecting together and then idling together.  Results do not depend on the schedule: every kernel
+ * sees the same inputs as in the one-lane order.
  *
  *   ltm_lane_create           a context like `parent` (same device, field of view, extrinsic, kernel switches); destroy with ltm_destroy
  *   ltm_cloud_lend / _give    make a cloud of context `from` usable in context `to` WITHOUT copying: `lend` leaves ownership with `from` (the new handle

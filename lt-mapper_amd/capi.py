@@ -44,7 +44,16 @@ class IcpParams(C.Structure):
 ICP_RESULT = np.dtype([("T", np.float64, (4, 4)), ("fitness", np.float64), ("last_mse", np.float64), ("converged", np.int32),
                        ("iterations", np.int32), ("state", np.int32), ("n_corr", np.uint32)], align=True)
 ICP_STATES = ("too few correspondences", "iterations", "transform", "absolute mse", "relative mse", "degenerate system")
-ICP_METHODS = ("point", "plane")
+ICP_METHODS = ("point", "plane", "gicp")
+
+
+class _MethodDefault(int):
+    """verify_loops' default for normal_k.  It is the int 10 -- what method="plane" has used since it was added, and what the signature shows -- but its
+    identity tells "not given" from an explicit 10, so that method="gicp" can take GICP_NORMAL_K instead"""
+
+
+GICP_NORMAL_K = 20      # pcl::GeneralizedIterativeClosestPoint's k_correspondences_
+_NORMAL_K_OF_METHOD = _MethodDefault(10)
 
 
 # name -> (restype, argtypes); kept in one table so tests can check it against include/ltm.h
@@ -153,6 +162,7 @@ SIGNATURES = {
     "ltm_icp_align_scanset": (_i, [_vp, _sz, C.POINTER(_vp), _u64, _vp, _vp, C.POINTER(IcpParams), _vp, _vp]),
     "ltm_icp_align_plane": (_i, [_vp, _sz, C.POINTER(_vp), _pu64, _vp, C.POINTER(IcpParams), _vp, _vp]),
     "ltm_icp_align_plane_scanset": (_i, [_vp, _sz, C.POINTER(_vp), _u64, _vp, _vp, C.POINTER(IcpParams), _vp, _vp]),
+    "ltm_icp_align_gicp": (_i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(IcpParams), C.c_double, _vp, _vp]),
     "ltm_pose6d_to_affine3f": (_i, [_vp, _sz, _vp]),
     "ltm_submaps_assemble": (_i, [_vp, _u64, _vp, _vp, _sz, _i, _f, _i, _pu64]),
     "ltm_search_build_scanset": (_i, [_vp, _u64, _sz, _sz, C.POINTER(_vp)]),
@@ -631,17 +641,21 @@ class Context:
         return ScanSet(self, out.value)
 
     def verify_loops(self, target_scans, source_scans, pairs, target_affines=None, source_affines=None, search_num=25, leaf=0.3,
-                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, method="point", normal_k=10, **icp):
+                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, method="point", normal_k=_NORMAL_K_OF_METHOD, **icp):
         """The body of LTslam::addSCloops' loop (LTslam.cpp:370-416) for all `pairs` = (target key, source key): the target submap (+-search_num
         keyframes) and its search index are made ONCE per distinct target key, the source submap is the source keyframe alone (searchNum = 0), every
         source is aligned to its target by icp_align, and a pair is accepted iff converged and fitness <= fitness_threshold (loopFitnessScoreThreshold,
         0.5 by default: ltslam/src/RosParamServer.cpp:23).  The work is cut into batches of consecutive pairs whose submaps hold at most max_batch_points
         points before the grid (estimated from the scan sets' offsets).  method="plane" verifies with point-to-plane ICP: the normals of each batch of
         target indices are estimated in one call (normal_k neighbours), the viewpoint at the key keyframe's translation (the origin without affines).
+        method="gicp" verifies with generalized ICP (gicp_epsilon among **icp): the source keyframes'
+        indices are built with search_index_batch as well, and the normals of the batch's source and target indices are estimated in ONE call (targets
+        first; the viewpoint of a source at its keyframe's translation).
+        normal_k, when not given, is the method's own: 10 for "plane", 20 for "gicp" (PCL's k_correspondences_, DeviceICP's default too).
         Returns (ICP_RESULT records, accept mask), one entry per pair."""
         method = _icp_method(method)
-        if method == "plane":
-            normal_k = _normals_k(normal_k)
+        if method != "point":
+            normal_k = normals_k_of(method, normal_k)
         pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
         res = np.zeros(len(pairs), dtype=ICP_RESULT)
         t_off = target_scans.offsets().astype(np.int64)
@@ -669,7 +683,19 @@ class Context:
             tsub = self.loop_submaps(target_scans, tkeys, search_num, leaf, target_affines, order)
             ssub = self.loop_submaps(source_scans, [int(pairs[i, 1]) for i in b], 0, leaf, source_affines, order)
             idx = self.search_index_batch(tsub)
+            sidx = []
             try:
+                if method == "gicp":
+                    sidx = self.search_index_batch(ssub)
+                    vp = None
+                    if target_affines is not None or source_affines is not None:
+                        zero = np.zeros(3, np.float32)
+                        ta = None if target_affines is None else np.asarray(target_affines, dtype=np.float32).reshape(-1, 3, 4)
+                        sa = None if source_affines is None else np.asarray(source_affines, dtype=np.float32).reshape(-1, 3, 4)
+                        vp = np.stack([zero if ta is None else ta[k, :, 3] for k in tkeys] + [zero if sa is None else sa[int(pairs[i, 1]), :, 3] for i in b])
+                    self.estimate_normals(idx + sidx, normal_k, vp)
+                    res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], sidx[j]) for j, i in enumerate(b)], method=method, **icp)
+                    continue
                 if method == "plane":
                     vp = None
                     if target_affines is not None:
@@ -677,7 +703,7 @@ class Context:
                     self.estimate_normals(idx, normal_k, vp)
                 res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], (ssub, j)) for j, i in enumerate(b)], method=method, **icp)
             finally:
-                for x in idx:
+                for x in idx + sidx:
                     x.close()
                 tsub.free()
                 ssub.free()
@@ -702,15 +728,20 @@ class Context:
         return ScanContexts(self, h.value, p)
 
     # ---- icp
-    def icp_align(self, pairs, init=None, trace=False, method="point", **params):
+    def icp_align(self, pairs, init=None, trace=False, method="point", gicp_epsilon=1e-3, **params):
         """ltm_icp_align (method="point", the default) / ltm_icp_align_plane (method="plane": every target must carry normals, see estimate_normals;
         state 5 = degenerate system): ICP of every (target, source) of `pairs` in one batch -- target a SearchIndex of this context (one index
         may serve many pairs), source a Cloud of this context, an (n, 3) / (n, 4) array or (ScanSet, keyframe) -- when every source is a keyframe of one
         ScanSet they are read in place (ltm_icp_align_scanset).  init: (n, 4, 4) source->target start transforms
         (None: identity); params: the fields of ltm_icp_params, the reference's values by default.  Returns a record array of dtype ICP_RESULT
         (T, fitness, last_mse, converged, iterations, state, n_corr), one record per pair; with trace=True also the (n, max_iterations, 2)
-        array of (n_corr, mse) per iteration, NaN where no iteration ran."""
-        plane = _icp_method(method) == "plane"
+        array of (n_corr, mse) per iteration, NaN where no iteration ran.
+        method="gicp" is ltm_icp_align_gicp, generalized (plane-to-plane) ICP: the source of every pair is a SearchIndex too (anything else raises
+        TypeError, an empty batch ValueError: there is nothing to say which kind of source it would have had), both sides must carry normals, and
+        gicp_epsilon in (0, 1] (PCL's 0.001 by default) regularises the covariances the normals imply; the sources are read in place."""
+        if _icp_method(method) == "gicp":
+            return self._icp_align_gicp(list(pairs), init, trace, gicp_epsilon, params)
+        plane = method == "plane"
         align_clouds = self.lib.ltm_icp_align_plane if plane else self.lib.ltm_icp_align
         align_scanset = self.lib.ltm_icp_align_plane_scanset if plane else self.lib.ltm_icp_align_scanset
         p = icp_params(**params)
@@ -751,6 +782,26 @@ class Context:
             finally:
                 for s_ in made:
                     s_.free()
+        return (res, tr) if trace else res
+
+    def _icp_align_gicp(self, pairs, init, trace, gicp_epsilon, params):
+        n = len(pairs)
+        if not n:
+            raise ValueError("method='gicp' needs at least one (target SearchIndex, source SearchIndex) pair")
+        eps = float(gicp_epsilon)
+        if not (np.isfinite(eps) and 0.0 < eps <= 1.0):
+            raise ValueError("gicp_epsilon must be in (0, 1]")
+        for t, s_ in pairs:
+            if not isinstance(t, SearchIndex) or not isinstance(s_, SearchIndex):
+                raise TypeError("method='gicp' takes (SearchIndex, SearchIndex) pairs: the source needs an index and normals of its own")
+        p = icp_params(**params)
+        res = np.zeros(n, dtype=ICP_RESULT)
+        tr = np.full((n, max(p.max_iterations, 0), 2), np.nan) if trace else None
+        th = (_vp * n)(*[t.h for t, _ in pairs])
+        sh = (_vp * n)(*[s_.h for _, s_ in pairs])
+        i16 = None if init is None else np.ascontiguousarray(init, dtype=np.float64).reshape(n, 16)
+        self._ck(self.lib.ltm_icp_align_gicp(self.h, n, th, sh, None if i16 is None else i16.ctypes.data, C.byref(p), eps, res.ctypes.data,
+                                             tr.ctypes.data if trace and tr.size else None))
         return (res, tr) if trace else res
 
     # ---- debug / parity
@@ -968,6 +1019,11 @@ def _icp_method(method):
     if method not in ICP_METHODS:
         raise ValueError(f"method must be one of {ICP_METHODS}, not {method!r}")
     return method
+
+
+def normals_k_of(method, normal_k=_NORMAL_K_OF_METHOD):
+    """the neighbours verify_loops estimates normals with: normal_k where the caller gave one, else the method's own (10 for "plane", 20 for "gicp")"""
+    return _normals_k(GICP_NORMAL_K if normal_k is _NORMAL_K_OF_METHOD and _icp_method(method) == "gicp" else normal_k)
 
 
 def _normals_k(k):

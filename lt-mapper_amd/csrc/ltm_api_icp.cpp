@@ -1,6 +1,6 @@
-// ltm_api_icp.cpp -- C ABI: batched point-to-point and point-to-plane ICP of source clouds against search indices, the counterpart of the pcl::IterativeClosestPoint runs
+// ltm_api_icp.cpp -- C ABI: batched point-to-point, point-to-plane and generalized ICP of source clouds (generalized: source indices) against search indices, the counterpart of the pcl::IterativeClosestPoint runs
 // of LTslam::doICPVirtualRelative / doICPGlobalRelative (ltslam/src/LTslam.cpp:187-301) for all the pairs of addSCloops / addRSloops (:370-416, :508-560)
-// at once.  Kernels in ltm_k_icp.hip; the arithmetic is stated in include/ltm.h, "icp" and "icp, point-to-plane" (one driver, the method is a switch).
+// at once.  Kernels in ltm_k_icp.hip; the arithmetic is stated in include/ltm.h, "icp", "icp, point-to-plane" and "icp, generalized" (one driver, the method is a switch).
 #include "ltm_internal.h"
 
 namespace {
@@ -20,12 +20,15 @@ void check_params(const ltm_icp_params& p)
     LTM_REQUIRE(p.max_iterations <= (1 << 20), "max_iterations must be at most 2^20");
 }
 
-// the routine behind both entry points: source_of(i) names the points of pair i's source (a cloud, or a keyframe of a scan set read in place)
-struct IcpSource { const float4* d; size_t n; };
+// the routine behind all entry points: source_of(i) names the points of pair i's source (a cloud, a keyframe of a scan set read in place, or -- generalized
+// ICP -- the points and normals of a search index read in place, in the index's own order).  method: kIcpPoint, kIcpPlane or kIcpGicp
+struct IcpSource { const float4* d; size_t n; const float4* nrm; };
 template <class SourceOf>
-void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* targets, SourceOf&& source_of, const double* init16, const ltm_icp_params* params,
-                    ltm_icp_result* results, double* trace)
+void icp_align_impl(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* targets, SourceOf&& source_of, const double* init16, const ltm_icp_params* params,
+                    ltm_icp_result* results, double* trace, double gicp_epsilon = 0.0)
 {
+    const bool gicp = method == kIcpGicp, plane = method == kIcpPlane;
+    const bool wide = gicp || plane;      // records of kIcpPlanePartial doubles, the 6 x 6 solve
     ltm_icp_params prm;
     ltm_icp_default_params(&prm);
     if (params) prm = *params;
@@ -47,7 +50,7 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
         IcpPair& P = pairs[i];
         memset(&P, 0, sizeof P);
         search_view(c, targets[i], &P.t, &P.f);
-        if (plane) {
+        if (wide) {
             int nk = 0;
             P.nrm = search_normals(c, targets[i], &nk);
             LTM_REQUIRE(nk != 0, "a target has no normals (ltm_search_estimate_normals)");
@@ -56,6 +59,7 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
         LTM_REQUIRE(src.n < 0x80000000ull, "a source must have fewer than 2^31 points");
         const bool run = src.n && P.t.Mf && max_it >= 1;
         P.src = src.d;
+        P.snrm = src.nrm;
         P.o[0] = P.f.ox; P.o[1] = P.f.oy; P.o[2] = P.f.oz;
         P.first = off[i];
         P.n = run ? (uint32_t)src.n : 0u;
@@ -80,7 +84,9 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
 
     if (active) {
         DevBuf d_pairs(c, n_pairs * sizeof(IcpPair)), d_st(c, n_pairs * sizeof(IcpState)), d_off(c, (n_pairs + 1) * 8), d_bp(c, (size_t)n_blocks * 4);
-        DevBuf d_sorted(c, total * sizeof(float4)), d_part(c, (size_t)n_blocks * (plane ? kIcpPlanePartial : kIcpPartial) * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
+        std::unique_ptr<DevBuf> d_sorted;      // the sources in their target's code order; generalized ICP reads its source indices in place and has none
+        if (!gicp) d_sorted.reset(new DevBuf(c, total * sizeof(float4)));
+        DevBuf d_part(c, (size_t)n_blocks * (wide ? kIcpPlanePartial : kIcpPartial) * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
         h2d(c, d_pairs.p, pairs.data(), n_pairs * sizeof(IcpPair));
         h2d(c, d_st.p, st.data(), n_pairs * sizeof(IcpState));
         h2d(c, d_off.p, off.data(), (n_pairs + 1) * 8);
@@ -90,7 +96,8 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
         const IcpPair* dp = d_pairs.as<IcpPair>();
         IcpState* ds = d_st.as<IcpState>();
         const uint32_t* bp = d_bp.as<uint32_t>();
-        {
+        const float4* sorted = d_sorted ? d_sorted->as<float4>() : nullptr;
+        if (sorted) {
             // each source once into the code order of its target's frame: the lanes of a wavefront then walk the same part of the tree
             ProfScope ps(c, "icp_prepare", (double)total, 72.0 * (double)total);
             DevBuf keys(c, total * 8), keys_sorted(c, total * 8), idx(c, total * 4), order(c, total * 4);
@@ -98,7 +105,7 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
             DevBuf temp(c, tb);
             LTM_HIP(icp_source_keys(dp, bp, n_blocks, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
             LTM_HIP(icp_sort_sources(dp, bp, n_blocks, n_pairs, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), idx.as<uint32_t>(),
-                                     order.as<uint32_t>(), d_sorted.as<float4>(), temp.p, tb, c->stream));
+                                     order.as<uint32_t>(), d_sorted->as<float4>(), temp.p, tb, c->stream));
         }
         const double max2 = prm.max_corr_dist * prm.max_corr_dist;
         const int poll = poll_interval();
@@ -108,9 +115,9 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
                 ProfScope ps(c, "icp_iter", (double)total * chunk, 16.0 * (double)total * chunk, -1.0, false);
                 if (ps.cls >= 0) c->prof[ps.cls].launches += 2 * (uint64_t)chunk;
                 for (int k = 0; k < chunk; ++k) {
-                    LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), max2, plane ? kIcpPlane : kIcpPoint, d_part.as<double>(), c->stream));
+                    LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, sorted, max2, method, d_part.as<double>(), c->stream, 1.0 - gicp_epsilon));
                     LTM_HIP(icp_update(dp, ds, n_pairs, d_part.as<double>(), max_it, prm.transformation_epsilon, prm.euclidean_fitness_epsilon,
-                                       trace_n ? d_trace.as<double>() : nullptr, d_unf.as<uint32_t>(), c->stream, plane ? 1 : 0));
+                                       trace_n ? d_trace.as<double>() : nullptr, d_unf.as<uint32_t>(), c->stream, wide ? 1 : 0));
                 }
             }
             it += chunk;
@@ -122,7 +129,7 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
         {
             ProfScope ps(c, "icp_fitness", (double)total, 16.0 * (double)total, -1.0, false);
             if (ps.cls >= 0) c->prof[ps.cls].launches += 2;
-            LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, d_sorted.as<float4>(), 0.0, kIcpScore, d_part.as<double>(), c->stream));
+            LTM_HIP(icp_correspond(dp, ds, bp, n_blocks, sorted, 0.0, kIcpScore, d_part.as<double>(), c->stream));
             LTM_HIP(icp_fitness(dp, ds, n_pairs, d_part.as<double>(), c->stream));
         }
         d2h(c, st.data(), d_st.p, n_pairs * sizeof(IcpState));
@@ -142,24 +149,24 @@ void icp_align_impl(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* t
     }
 }
 
-// the two forms of the sources, shared by both methods
-int align_clouds(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16,
+// the two forms of the sources, shared by the point and plane methods
+int align_clouds(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16,
                  const ltm_icp_params* params, ltm_icp_result* results, double* trace)
 {
     return guarded(c, [&] {
         LTM_REQUIRE(!n_pairs || sources, "null argument");
-        icp_align_impl(c, plane, n_pairs, targets, [&](size_t i) { const Cloud& src = get_cloud(c, sources[i]); return IcpSource{src.d, src.n}; }, init16, params, results, trace);
+        icp_align_impl(c, method, n_pairs, targets, [&](size_t i) { const Cloud& src = get_cloud(c, sources[i]); return IcpSource{src.d, src.n, nullptr}; }, init16, params, results, trace);
     });
 }
-int align_scanset(ltm_ctx* c, bool plane, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
+int align_scanset(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
                   const ltm_icp_params* params, ltm_icp_result* results, double* trace)
 {
     return guarded(c, [&] {
         const ScanSet& ss = get_ss(c, sources);
         LTM_REQUIRE(!n_pairs || source_kf, "null argument");
-        icp_align_impl(c, plane, n_pairs, targets, [&](size_t i) {
+        icp_align_impl(c, method, n_pairs, targets, [&](size_t i) {
             LTM_REQUIRE(source_kf[i] < ss.nkf(), "source keyframe out of range");
-            return IcpSource{ss.d + ss.off[source_kf[i]], (size_t)(ss.off[source_kf[i] + 1] - ss.off[source_kf[i]])};
+            return IcpSource{ss.d + ss.off[source_kf[i]], (size_t)(ss.off[source_kf[i] + 1] - ss.off[source_kf[i]]), nullptr};
         }, init16, params, results, trace);
     });
 }
@@ -180,25 +187,42 @@ void ltm_icp_default_params(ltm_icp_params* p)
 int ltm_icp_align(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16, const ltm_icp_params* params,
                   ltm_icp_result* results, double* trace)
 {
-    return align_clouds(c, false, n_pairs, targets, sources, init16, params, results, trace);
+    return align_clouds(c, kIcpPoint, n_pairs, targets, sources, init16, params, results, trace);
 }
 
 int ltm_icp_align_scanset(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
                           const ltm_icp_params* params, ltm_icp_result* results, double* trace)
 {
-    return align_scanset(c, false, n_pairs, targets, sources, source_kf, init16, params, results, trace);
+    return align_scanset(c, kIcpPoint, n_pairs, targets, sources, source_kf, init16, params, results, trace);
 }
 
 int ltm_icp_align_plane(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, const ltm_cloud* sources, const double* init16, const ltm_icp_params* params,
                         ltm_icp_result* results, double* trace)
 {
-    return align_clouds(c, true, n_pairs, targets, sources, init16, params, results, trace);
+    return align_clouds(c, kIcpPlane, n_pairs, targets, sources, init16, params, results, trace);
 }
 
 int ltm_icp_align_plane_scanset(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, ltm_scanset sources, const uint32_t* source_kf, const double* init16,
                                 const ltm_icp_params* params, ltm_icp_result* results, double* trace)
 {
-    return align_scanset(c, true, n_pairs, targets, sources, source_kf, init16, params, results, trace);
+    return align_scanset(c, kIcpPlane, n_pairs, targets, sources, source_kf, init16, params, results, trace);
+}
+
+int ltm_icp_align_gicp(ltm_ctx* c, size_t n_pairs, ltm_search* const* targets, ltm_search* const* sources, const double* init16, const ltm_icp_params* params,
+                       double gicp_epsilon, ltm_icp_result* results, double* trace)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(std::isfinite(gicp_epsilon) && gicp_epsilon > 0.0 && gicp_epsilon <= 1.0, "gicp_epsilon must be in (0, 1]");
+        LTM_REQUIRE(!n_pairs || sources, "null argument");
+        icp_align_impl(c, kIcpGicp, n_pairs, targets, [&](size_t i) {
+            SearchTree st; SearchFrame sf;
+            search_view(c, sources[i], &st, &sf);
+            int nk = 0;
+            const float4* nrm = search_normals(c, sources[i], &nk);
+            LTM_REQUIRE(nk != 0, "a source has no normals (ltm_search_estimate_normals)");
+            return IcpSource{st.pts, (size_t)st.Mf, nrm};
+        }, init16, params, results, trace, gicp_epsilon);
+    });
 }
 
 } // extern "C"

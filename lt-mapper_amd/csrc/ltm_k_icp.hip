@@ -14,6 +14,9 @@
 // Point-to-plane (ltm_icp_align_plane; include/ltm.h "icp, point-to-plane") is a third mode of the same two kernels: the correspondence kernel reads the target
 // point's normal (ltm_k_normals.hip) and accumulates the 6 x 6 normal equations in a record of kIcpPlanePartial doubles, in the same fixed order; the update
 // kernel solves them by Cholesky (plane_step) where the point-to-point mode takes the SVD.  Everything else -- transform, 1-NN, stop tests, trace -- is shared.
+// Generalized ICP (ltm_icp_align_gicp; include/ltm.h "icp, generalized") is a fourth mode: both sides are search indices with normals, the source index's
+// points are read in place in its own order, and the record (same layout as the plane record) holds the normal equations weighted per correspondence by
+// the inverse of the two regularised covariances the normals imply; the update kernel's plane instantiation serves it unchanged.
 #include "ltm_kernels_common.h"
 #include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -205,13 +208,18 @@ hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, ui
 // ------------------------------------------------------------------------------------------------ correspondences
 // MODE (IcpMode): kIcpPoint the moments of the SVD estimate, kIcpScore the fitness pass, kIcpPlane the normal equations of the point-to-plane estimate
 // (include/ltm.h "icp, point-to-plane"): row [p x n, n], right side n . (q - p), with p, q about the pair's origin and n the target point's normal
+// kIcpGicp the weighted normal equations of generalized ICP (include/ltm.h "icp, generalized"): per correspondence M = (2I - w (n_b n_b^T + m m^T))^-1 with
+// n_b the target point's normal, m = R_T n_a the source point's normal turned by the current T and w = gicp_w = 1 - epsilon; the record is count,
+// sum A^T M A (21), sum A^T M d (6), sum d2 with A = [-[p]x, I], d = q - p -- the layout of the plane record, so k_icp_update<true> solves it.  The
+// sources of this mode are search indices read in place (P.src = the source index's points, P.snrm their normals): no sort, no copy; `sorted` is null
+// then, also in the score pass that follows
 template <int MODE>
 __global__ void __launch_bounds__(kIcpBlock)
 k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__ st, const uint32_t* __restrict__ block_pair, const float4* __restrict__ sorted,
-                 double max_corr2, double* __restrict__ partials)
+                 double max_corr2, double* __restrict__ partials, double gicp_w)
 {
     constexpr bool SCORE = MODE == kIcpScore;
-    constexpr int NP = MODE == kIcpPlane ? kIcpPlanePartial : kIcpPartial;      // doubles per record
+    constexpr int NP = (MODE == kIcpPlane || MODE == kIcpGicp) ? kIcpPlanePartial : kIcpPartial;      // doubles per record
     __shared__ double lds[kIcpBlock / 64][NP];
     const uint32_t pi = block_pair[blockIdx.x];
     const IcpState& S = st[pi];
@@ -223,7 +231,8 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
 #pragma unroll
     for (int c = 0; c < NP; ++c) v[c] = 0.0;
     if (local < P.n) {
-        const float4 p = sorted[P.first + local];
+        const float4* base = (MODE == kIcpGicp || (SCORE && !sorted)) ? P.src : sorted + P.first;      // uniform over the workgroup
+        const float4 p = base[local];
         if (finite3(p.x, p.y, p.z)) {
             const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
             const float qx = (float)(((S.T[0] * x + S.T[1] * y) + S.T[2] * z) + S.T[3]);
@@ -270,6 +279,52 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
                             v[NP - 1] = (double)bd;
                         }
                     }
+                } else if constexpr (MODE == kIcpGicp) {
+                    if (bi != INT_MAX && (double)bd <= max_corr2) {
+                        const float4 tp = t.pts[bj], tn = P.nrm[bj], sn = P.snrm[local];
+                        if (finite3(tn.x, tn.y, tn.z) && finite3(sn.x, sn.y, sn.z)) {      // a correspondence without both normals is dropped
+                            const double px = (double)qx - P.o[0], py = (double)qy - P.o[1], pz = (double)qz - P.o[2];
+                            const double dx = ((double)tp.x - P.o[0]) - px, dy = ((double)tp.y - P.o[1]) - py, dz = ((double)tp.z - P.o[2]) - pz;
+                            const double bx = (double)tn.x, by = (double)tn.y, bz = (double)tn.z;
+                            const double ax = (double)sn.x, ay = (double)sn.y, az = (double)sn.z;
+                            const double mx = (S.T[0] * ax + S.T[1] * ay) + S.T[2] * az;
+                            const double my = (S.T[4] * ax + S.T[5] * ay) + S.T[6] * az;
+                            const double mz = (S.T[8] * ax + S.T[9] * ay) + S.T[10] * az;
+                            const double s00 = 2.0 - gicp_w * (bx * bx + mx * mx), s01 = -gicp_w * (bx * by + mx * my), s02 = -gicp_w * (bx * bz + mx * mz);
+                            const double s11 = 2.0 - gicp_w * (by * by + my * my), s12 = -gicp_w * (by * bz + my * mz), s22 = 2.0 - gicp_w * (bz * bz + mz * mz);
+                            const double c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
+                            const double c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
+                            const double rdet = 1.0 / ((s00 * c00 + s01 * c01) + s02 * c02);
+                            const double M[3][3] = {{c00 * rdet, c01 * rdet, c02 * rdet}, {c01 * rdet, c11 * rdet, c12 * rdet}, {c02 * rdet, c12 * rdet, c22 * rdet}};
+                            // G = M W with W = -[p]x (column j of W is e_j x p); A^T M A = [[p x G_j, G^T], [G, M]], A^T M d = [p x g, g] with g = M d
+                            double G[3][3], g[3];
+#pragma unroll
+                            for (int r = 0; r < 3; ++r) {
+                                G[r][0] = M[r][2] * py - M[r][1] * pz;
+                                G[r][1] = M[r][0] * pz - M[r][2] * px;
+                                G[r][2] = M[r][1] * px - M[r][0] * py;
+                                g[r] = (M[r][0] * dx + M[r][1] * dy) + M[r][2] * dz;
+                            }
+                            v[0] = 1.0;
+                            int e = 1;
+#pragma unroll
+                            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                                for (int k = r; k < 3; ++k) {      // row r of p x (column k of G)
+                                    v[e++] = r == 0 ? py * G[2][k] - pz * G[1][k] : r == 1 ? pz * G[0][k] - px * G[2][k] : px * G[1][k] - py * G[0][k];
+                                }
+#pragma unroll
+                                for (int k = 0; k < 3; ++k) v[e++] = G[k][r];
+                            }
+#pragma unroll
+                            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                                for (int k = r; k < 3; ++k) v[e++] = M[r][k];
+                            v[22] = py * g[2] - pz * g[1]; v[23] = pz * g[0] - px * g[2]; v[24] = px * g[1] - py * g[0];
+                            v[25] = g[0]; v[26] = g[1]; v[27] = g[2];
+                            v[NP - 1] = (double)bd;
+                        }
+                    }
                 } else if (bi != INT_MAX && (double)bd <= max_corr2) {
                     const float4 tp = t.pts[bj];
                     const double px = (double)qx - P.o[0], py = (double)qy - P.o[1], pz = (double)qz - P.o[2];
@@ -296,12 +351,13 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
     }
 }
 hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32_t* block_pair, uint32_t n_blocks, const float4* sorted, double max_corr2,
-                          int mode, double* partials, hipStream_t s)
+                          int mode, double* partials, hipStream_t s, double gicp_w)
 {
     if (!n_blocks) return hipSuccess;
-    if (mode == kIcpScore) k_icp_correspond<kIcpScore><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
-    else if (mode == kIcpPlane) k_icp_correspond<kIcpPlane><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
-    else k_icp_correspond<kIcpPoint><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials);
+    if (mode == kIcpScore) k_icp_correspond<kIcpScore><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials, gicp_w);
+    else if (mode == kIcpPlane) k_icp_correspond<kIcpPlane><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials, gicp_w);
+    else if (mode == kIcpGicp) k_icp_correspond<kIcpGicp><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, nullptr, max_corr2, partials, gicp_w);
+    else k_icp_correspond<kIcpPoint><<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, st, block_pair, sorted, max_corr2, partials, gicp_w);
     return hipGetLastError();
 }
 

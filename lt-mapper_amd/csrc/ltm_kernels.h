@@ -301,11 +301,12 @@ hipError_t submap_gather(const float4* scans, const SubmapPiece* pieces, const u
 static constexpr int kIcpBlock = 256;           // source points per workgroup of the correspondence kernel = per partial record
 static constexpr int kIcpPartial = 17;          // doubles per partial record: count, sum p (3), sum q (3), sum p q^T (9, row-major), sum d2
 static constexpr int kIcpPlanePartial = 29;     // point-to-plane: count, A^T A (21, upper triangle row-major), A^T b (6), sum d2
-enum IcpMode { kIcpPoint = 0, kIcpScore = 1, kIcpPlane = 2 };
+enum IcpMode { kIcpPoint = 0, kIcpScore = 1, kIcpPlane = 2, kIcpGicp = 3 };      // kIcpGicp: records of kIcpPlanePartial doubles (sum A^T M A, sum A^T M d)
 // one pair of the batch: the target's tree and frame, the source as given (src, n points), its slice [first, first + n) of the batch's sorted sources and
 // its workgroups [block0, block0 + n_blocks) of the correspondence grid; o: the origin the moments are taken about (the corner of the target's frame);
-// nrm: the target's normals, aligned with t.pts (point-to-plane only)
-struct IcpPair { SearchTree t; SearchFrame f; const float4* src; double o[3]; uint64_t first; uint32_t n, block0, n_blocks, pad; const float4* nrm; };
+// nrm: the target's normals, aligned with t.pts (point-to-plane and generalized).  Generalized ICP reads its sources in place: src is then the source
+// index's own points (its finite points in its own code order, n = its Mf), snrm their normals, and `first` is not used
+struct IcpPair { SearchTree t; SearchFrame f; const float4* src; double o[3]; uint64_t first; uint32_t n, block0, n_blocks, pad; const float4* nrm; const float4* snrm; };
 // what k_icp_update keeps per pair between iterations (T: rows 0..2 of the accumulated transform, row-major)
 struct IcpState { double T[12]; double prev_mse, last_mse, fitness; int32_t iterations, state, converged, done; uint32_t n_corr, pad; };
 // codes of every source point under its target's frame (keys) and its position in its source (idx); grid over the blocks of block_pair
@@ -317,9 +318,10 @@ hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, ui
                             hipStream_t s);
 // one record per workgroup.  mode kIcpPoint: kIcpPartial doubles, correspondences within max_corr2 of the pairs not done yet; kIcpScore: count and sum d2
 // of every finite point of every pair, no limit (in a record of kIcpPartial); kIcpPlane: kIcpPlanePartial doubles, the normal equations of the
-// correspondences within max_corr2 whose target normal is finite
+// correspondences within max_corr2 whose target normal is finite; kIcpGicp: kIcpPlanePartial doubles, the weighted normal equations of the correspondences
+// within max_corr2 whose two normals are finite (gicp_w = 1 - gicp_epsilon).  sorted == nullptr (kIcpGicp, and kIcpScore after it): the points are pairs[].src
 hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32_t* block_pair, uint32_t n_blocks, const float4* sorted, double max_corr2,
-                          int mode, double* partials, hipStream_t s);
+                          int mode, double* partials, hipStream_t s, double gicp_w = 0.0);
 // per pair: partials added in block order, transform estimate (plane: the 6 x 6 solve of the kIcpPlane records), stop tests; trace (nullable):
 // n_pairs x max_iterations x 2; unfinished: one counter
 hipError_t icp_update(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, int max_iterations, double transformation_epsilon,

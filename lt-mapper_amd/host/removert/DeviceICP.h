@@ -7,6 +7,9 @@
 // Every member reports a failure by throwing (std::runtime_error with the context's message, std::logic_error for a call out of order).
 // setMethod(PointToPlane) switches to pcl::IterativeClosestPointWithNormals' error (include/ltm.h, "icp, point-to-plane"): the target's normals are then
 // estimated on the device (setKSearch / setViewPoint as on pcl::NormalEstimation) before the first alignment against a target.
+// setMethod(Generalized) switches to pcl::GeneralizedIterativeClosestPoint's plane-to-plane error (include/ltm.h, "icp, generalized"): every source gets a
+// search index of its own, and the normals of both sides -- which stand for GICP's covariances -- are estimated on the device with
+// setCorrespondenceRandomness(k) neighbours (20, PCL's k_correspondences_).  setRotationEpsilon is accepted and unused: the stop tests are those of "icp".
 // Not here: the Euler / gtsam::Pose3 conversions of the result stay on the host as they are (the submaps: DeviceLoopSubmaps.h).
 #pragma once
 #include <initializer_list>
@@ -34,12 +37,20 @@ public:
     void setEuclideanFitnessEpsilon(double e) { params_.euclidean_fitness_epsilon = e; }
     const ltm_icp_params& params() const { return params_; }
 
-    enum Method { PointToPoint, PointToPlane };
-    void setMethod(Method m) { method_ = m; }
+    enum Method { PointToPoint, PointToPlane, Generalized };
+    void setMethod(Method m) { method_ = m; have_normals_ = false; }
     Method method() const { return method_; }
     // the normals of the point-to-plane method: neighbours and viewpoint of pcl::NormalEstimation
     void setKSearch(int k) { normal_k_ = k; have_normals_ = false; }
     void setViewPoint(float vx, float vy, float vz) { viewpoint_[0] = vx; viewpoint_[1] = vy; viewpoint_[2] = vz; have_normals_ = false; }
+
+    // the generalized method, under pcl::GeneralizedIterativeClosestPoint's names: the neighbours of the covariances (here: of the normals of both sides),
+    // gicp_epsilon_ (no setter in PCL 1.10; the constant of the regularised covariance), and the rotation epsilon, which this library does not use
+    void setCorrespondenceRandomness(int k) { gicp_k_ = k; have_normals_ = false; }
+    int getCorrespondenceRandomness() const { return gicp_k_; }
+    void setGicpEpsilon(double e) { gicp_epsilon_ = e; }
+    void setRotationEpsilon(double e) { rotation_epsilon_ = e; }      // kept for the caller, unused (include/ltm.h, "icp, generalized", DEPARTURES)
+    double getRotationEpsilon() const { return rotation_epsilon_; }
 
     // pcl::Registration::setInputSource: the cloud is copied (the reference keeps a shared pointer)
     void setInputSource(const Cloud& source) { source_ = source; }
@@ -107,14 +118,25 @@ private:
         std::vector<ltm_search*> t(n, index_);
         int rc = LTM_OK;
         for (size_t i = 0; i < n && rc == LTM_OK; ++i) rc = ltm_cloud_upload(ctx_, sources[i]->data(), sources[i]->size(), sizeof(PointType), &h[i]);
-        if (rc == LTM_OK && method_ == PointToPlane && !have_normals_) {
-            rc = ltm_search_estimate_normals(ctx_, 1, &index_, normal_k_, viewpoint_);
+        if (rc == LTM_OK && method_ != PointToPoint && !have_normals_) {
+            rc = ltm_search_estimate_normals(ctx_, 1, &index_, method_ == Generalized ? gicp_k_ : normal_k_, viewpoint_);
             have_normals_ = rc == LTM_OK;
         }
-        if (rc == LTM_OK)
+        std::vector<ltm_search*> s(method_ == Generalized ? n : 0, nullptr);
+        if (method_ == Generalized) {
+            // the sources' own indices and normals (one launch for all of them), then the batch over (target index, source index) pairs
+            for (size_t i = 0; i < n && rc == LTM_OK; ++i) rc = ltm_search_build(ctx_, h[i], &s[i]);
+            std::vector<float> vp;
+            for (size_t i = 0; i < n; ++i) vp.insert(vp.end(), viewpoint_, viewpoint_ + 3);
+            if (rc == LTM_OK) rc = ltm_search_estimate_normals(ctx_, n, s.data(), gicp_k_, vp.data());
+            if (rc == LTM_OK)
+                rc = ltm_icp_align_gicp(ctx_, n, t.data(), s.data(), one_guess ? one_guess->data() : guesses, &params_, gicp_epsilon_, out.data(), nullptr);
+        } else if (rc == LTM_OK) {
             rc = (method_ == PointToPlane ? ltm_icp_align_plane : ltm_icp_align)(ctx_, n, t.data(), h.data(), one_guess ? one_guess->data() : guesses, &params_,
                                                                                  out.data(), nullptr);
+        }
         std::string msg = rc != LTM_OK ? ltm_last_error(ctx_) : "";
+        for (ltm_search* x : s) if (x) ltm_search_free(ctx_, x);
         for (ltm_cloud c : h) if (c) ltm_cloud_free(ctx_, c);
         if (rc != LTM_OK) throw std::runtime_error("DeviceICP: " + msg);
         return out;
@@ -147,6 +169,9 @@ private:
     ltm_icp_result result_;
     Method method_ = PointToPoint;
     int normal_k_ = 10;
+    int gicp_k_ = 20;                // k_correspondences_
+    double gicp_epsilon_ = 0.001;    // gicp_epsilon_
+    double rotation_epsilon_ = 2e-3; // rotation_epsilon_: PCL's default, not used here
     float viewpoint_[3] = {0.0f, 0.0f, 0.0f};
     bool have_normals_ = false;      // of index_, with the current k and viewpoint
 };
