@@ -247,6 +247,12 @@ int ltm_visibility_vote(ltm_ctx*, ltm_cloud map, ltm_scanset scans, ltm_poses po
  * kept for the votes that follow (selfRemovert projects every scan at res and 0.95 res for each entry of remove_resolution_list: six image shapes whose
  * spherical coordinates are the same).  ltm_visibility_vote computes what it does not find, one shape at a time; the images are identical either way. */
 int ltm_scanset_prepare_range_images(ltm_ctx*, ltm_scanset scans, size_t kf_begin, size_t kf_end, const float* res_alphas, size_t n_alphas);
+/* The same, plus the threshold the votes that follow will be called with (diff_thres of ltm_visibility_vote; < 0: none, which is the entry above).
+ * The images are built in the CU's LDS and written once (k_scan_rimg_lds: no fill, no global atomics), and with a threshold the bound images of the
+ * range-culled vote for it come out of the same pass instead of a pass of their own at the first vote.  A vote with another threshold rebuilds its bound
+ * image as before.  Context switch LTM_SCAN_IMG_LDS (read by ltm_create, default 1): 0 takes the fill / global-atomic / read-back kernels, which shape sets
+ * the LDS plan cannot serve (ltm_debug_scan_bands) take in any case.  Images, maxima and bound images are the same bits either way. */
+int ltm_scanset_prepare_vote_images(ltm_ctx*, ltm_scanset scans, size_t kf_begin, size_t kf_end, const float* res_alphas, size_t n_alphas, float diff_thres);
 /* partitionCurrentMap tail (Removerter.cpp:816-824, :675-687, :933-946): index-ascending split */
 int ltm_partition_by_labels(ltm_ctx*, ltm_cloud map, const uint8_t* labels_dev, ltm_cloud* kept, ltm_cloud* flagged);
 /* vote over all keyframes + partition (single-GPU convenience).  host_labels (M bytes) may be NULL. */
@@ -674,6 +680,18 @@ int ltm_debug_proj_launch(float vfov, float hfov, float res_alpha, const double*
  * behind the occlusion cull keeps one (tile, keyframe) pair per workgroup. */
 int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_run, uint32_t first_block, size_t n_blocks, uint32_t* out_run, uint32_t* out_kf,
                               uint32_t* out_run_len, uint32_t* out_grid);
+/* The band plan of k_scan_rimg_lds for a set of image shapes (rows[j] x cols[j], j < n_shapes): one workgroup keeps one band of one keyframe in LDS, a band
+ * being rows [out_row0[b * n_shapes + j], out_row0[(b + 1) * n_shapes + j]) of every shape j.  *out_n_bands = 0 (and LTM_OK) for a set the plan cannot serve:
+ * more than 8 shapes, a shape without pixels, one row of all shapes together wider than the budget.  out_row0 ((max_bands + 1) * n_shapes entries) and
+ * out_bytes (max_bands entries: LDS bytes of each band, at most *out_budget_bytes) are filled for the first min(n_bands, max_bands) bands; all outputs but
+ * out_n_bands may be NULL.  Needs no context and no device. */
+int ltm_debug_scan_bands(size_t n_shapes, const int32_t* rows, const int32_t* cols, uint32_t* out_n_bands, uint32_t* out_budget_bytes, size_t max_bands,
+                         uint32_t* out_row0, uint32_t* out_bytes);
+/* The scan range images of keyframes [kf_begin, kf_end) for one resolution as the votes see them, cached or built now: img_out ((kf_end - kf_begin) * rows * cols
+ * floats, 10000 = empty), smax_out (one float per keyframe: the largest non-empty range, 0 without one) and, for diff_thres >= 0, qbound_out (the bound image of the
+ * range-culled vote for that threshold).  Every output may be NULL. */
+int ltm_debug_scan_images(ltm_ctx*, ltm_scanset scans, size_t kf_begin, size_t kf_end, float res_alpha, float diff_thres, float* img_out, float* smax_out,
+                          float* qbound_out);
 /* The survivor queue word of k_vote_map_cull carries a pixel as a linear index in 18 bits (all ones: pixel not certain); row and column come back from it
  * as row = mulhi(px << 6, magic) >> shift, col = px - row * cols.  For the image shape a fresh context derives from (vfov, hfov, res_alpha):
  *   out_u32[8] = rows, cols, rows * cols, 1 if the shape may take the kernel's fast path (rows * cols <= out_u32[7]), magic, shift, pixel bits (18),

@@ -124,6 +124,7 @@ SIGNATURES = {
     "ltm_voxel_grid_scanset_begin": (_i, [_vp, _u64, _f, C.POINTER(_vp)]),
     "ltm_voxel_grid_scanset_end": (_i, [_vp, _vp, _pu64]),
     "ltm_scanset_prepare_range_images": (_i, [_vp, _u64, _sz, _sz, C.POINTER(_f), _sz]),
+    "ltm_scanset_prepare_vote_images": (_i, [_vp, _u64, _sz, _sz, C.POINTER(_f), _sz, _f]),
     "ltm_visibility_vote": (_i, [_vp, _u64, _u64, _u64, _sz, _sz, _f, _f, _i, _vp]),
     "ltm_partition_by_labels": (_i, [_vp, _u64, _vp, _pu64, _pu64]),
     "ltm_visibility_partition": (_i, [_vp, _u64, _u64, _u64, _f, _f, _i, _pu64, _pu64, _vp]),
@@ -179,6 +180,8 @@ SIGNATURES = {
     "ltm_debug_proj_launch": (_i, [_f, _f, _f, _vp, _sz, _sz, _i, _vp, _vp, C.c_uint32, _sz, _vp, _vp]),
     "ltm_debug_vote_run_launch": (_i, [_sz, _sz, _i, C.c_uint32, _sz, _vp, _vp, _vp, _vp]),
     "ltm_debug_vote_queue_word": (_i, [C.c_float, C.c_float, C.c_float, _vp, _sz, _vp, _vp, _vp]),
+    "ltm_debug_scan_bands": (_i, [_sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ltm_debug_scan_images": (_i, [_vp, _u64, _sz, _sz, _f, _f, _vp, _vp, _vp]),
     "ltm_debug_cull_validation": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_occlusion_stats": (_i, [_vp, _pu64, _pu64, _pu64, _i]),
     "ltm_debug_voxel_stats": (_i, [_vp, _pu64, _pu64, _i]),
@@ -262,6 +265,28 @@ def vote_run_launch(map_points, n_keyframes, tile_run, first_block=0, n_blocks=0
     if rc != 0:
         raise LtmError(rc, "ltm_debug_vote_run_launch")
     return run[:n_blocks], kf[:n_blocks], run_len.value, grid.value
+
+
+def scan_bands(rows, cols):
+    """ltm_debug_scan_bands: (n_bands, row0[n_bands + 1, n_shapes], bytes[n_bands], budget) -- the band plan of the LDS scan-image kernel for the image
+    shapes rows[j] x cols[j]: band b holds rows [row0[b, j], row0[b + 1, j]) of shape j.  n_bands == 0: the set is not served (the older kernels take it).
+    Needs no context and no device."""
+    r = np.ascontiguousarray(rows, dtype=np.int32)
+    c = np.ascontiguousarray(cols, dtype=np.int32)
+    assert r.shape == c.shape and r.ndim == 1
+    lib = load_library()
+    n_bands, budget = C.c_uint32(0), C.c_uint32(0)
+    rc = lib.ltm_debug_scan_bands(len(r), r.ctypes.data if len(r) else None, c.ctypes.data if len(r) else None, C.byref(n_bands), C.byref(budget), 0, None, None)
+    if rc != 0:
+        raise LtmError(rc, "ltm_debug_scan_bands")
+    nb = n_bands.value
+    row0 = np.zeros((nb + 1, max(len(r), 1)), dtype=np.uint32)
+    nbytes = np.zeros(max(nb, 1), dtype=np.uint32)
+    if nb:
+        rc = lib.ltm_debug_scan_bands(len(r), r.ctypes.data, c.ctypes.data, C.byref(n_bands), C.byref(budget), nb, row0.ctypes.data, nbytes.ctypes.data)
+        if rc != 0:
+            raise LtmError(rc, "ltm_debug_scan_bands")
+    return nb, row0[:, :len(r)], nbytes[:nb], budget.value
 
 
 VOTE_QUEUE_WORD_U32 = ("rows", "cols", "npx", "fast_path", "px_magic", "px_shift", "px_bits", "npx_limit")
@@ -552,6 +577,25 @@ class Context:
         """scan range images of all the listed resolutions in one pass over the scans (kept for the votes that follow)"""
         a = (_f * len(alphas))(*[float(x) for x in alphas])
         self._ck(self.lib.ltm_scanset_prepare_range_images(self.h, scans.h, kf_begin, scans.n_kf if kf_end is None else kf_end, a, len(alphas)))
+
+    def prepare_vote_images(self, scans, alphas, thr, kf_begin=0, kf_end=None):
+        """prepare_scan_images plus the threshold of the votes that follow: their bound images come out of the same pass (thr < 0: none)"""
+        a = (_f * len(alphas))(*[float(x) for x in alphas])
+        self._ck(self.lib.ltm_scanset_prepare_vote_images(self.h, scans.h, kf_begin, scans.n_kf if kf_end is None else kf_end, a, len(alphas), float(thr)))
+
+    def debug_scan_images(self, scans, alpha, thr=-1.0, kf_begin=0, kf_end=None, want_qbound=None):
+        """ltm_debug_scan_images: (img[n_kf, rows, cols] f32, smax[n_kf] f32, qbound[n_kf, rows, cols] f32 or None) -- the scan range images of one resolution
+        as the votes see them (cached or built now); the bound image for thr >= 0."""
+        ke = scans.n_kf if kf_end is None else kf_end
+        rows, cols = self.rimg_size(alpha)
+        n = ke - kf_begin
+        img = np.zeros((n, rows, cols), dtype=np.float32)
+        smax = np.zeros(n, dtype=np.float32)
+        want_q = (thr >= 0) if want_qbound is None else want_qbound
+        qb = np.zeros((n, rows, cols), dtype=np.float32) if want_q else None
+        self._ck(self.lib.ltm_debug_scan_images(self.h, scans.h, kf_begin, ke, float(alpha), float(thr), img.ctypes.data, smax.ctypes.data,
+                                                qb.ctypes.data if want_q else None))
+        return img, smax, qb
 
     def visibility_vote(self, cmap, scans, poses, kf_begin, kf_end, alpha, thr, mode, labels_dev_ptr):
         self._ck(self.lib.ltm_visibility_vote(self.h, cmap.h, scans.h, poses.h, kf_begin, kf_end, alpha, thr, mode, labels_dev_ptr))

@@ -264,6 +264,8 @@ int ltm_create(const ltm_config* cfg, ltm_ctx** out)
         if (const char* v = getenv("LTM_VOXEL_KEYBITS")) c->voxel_key_compress = atoi(v);
         if (const char* v = getenv("LTM_VOXEL_FUSED_TAIL")) c->voxel_fused_tail = atoi(v);
         if (const char* v = getenv("LTM_VOXEL_IDENTITY")) c->voxel_identity = atoi(v);
+        if (const char* v = getenv("LTM_SCAN_IMG_LDS")) c->scan_img_lds = atoi(v);
+        if (const char* v = getenv("LTM_SCAN_MULTI_MAX_DENSITY")) { const double d = atof(v); if (d > 0.0) c->scan_multi_max_density = d; }
         if (const char* v = getenv("LTM_OCCLUSION")) c->occlusion_cull = atoi(v);
         if (getenv("LTM_OCCLUSION_STATS")) c->occlusion_stats_on = 1;
         if (const char* v = getenv("LTM_OCCLUSION_MIN_PAIRS")) c->occlusion_min_pairs = (size_t)atoll(v);
@@ -1013,7 +1015,7 @@ int ltm_lane_create(ltm_ctx* parent, ltm_ctx** out)
         c->l2b_identity = parent->l2b_identity; c->b2l_identity = parent->b2l_identity; c->kf_batch = parent->kf_batch; c->kopts = parent->kopts;
         c->fast_math = parent->fast_math;      // the exhaustive create-time self-check is a property of (device, vfov, hfov): not repeated
         for (int i = 0; i < 3; ++i) c->selfcheck[i] = parent->selfcheck[i];
-        c->scan_cache_cap = parent->scan_cache_cap; c->occlusion_cull = parent->occlusion_cull;
+        c->scan_cache_cap = parent->scan_cache_cap; c->scan_img_lds = parent->scan_img_lds; c->scan_multi_max_density = parent->scan_multi_max_density; c->occlusion_cull = parent->occlusion_cull;
         c->occlusion_min_pairs = parent->occlusion_min_pairs; c->occlusion_r_near = parent->occlusion_r_near;
         c->occlusion_subtile = parent->occlusion_subtile; c->occlusion_stats_on = parent->occlusion_stats_on;
         c->voxel_key_compress = parent->voxel_key_compress; c->voxel_fused_tail = parent->voxel_fused_tail; c->voxel_identity = parent->voxel_identity;

@@ -60,6 +60,12 @@ void scan_cache_drop(ltm_ctx* c, uint64_t ss_handle)
     }
 }
 
+// the band plan of k_scan_rimg_lds for these shapes, or false: the switch is off, or the shapes / the scans are outside what the kernel serves
+static bool scan_lds_plan(const ltm_ctx* c, int n, const int* rows, const int* cols, uint64_t longest_kf, ScanBands* plan)
+{
+    return c->scan_img_lds != 0 && longest_kf < 0xffffffffull && make_scan_bands(n, rows, cols, kScanLdsBudget, plan);
+}
+
 // returns the finished scan range images of keyframes [kb, kb+nb) (cached or freshly computed and then cached)
 // qbound_thr >= 0 also returns (in *qbound_out) the squared-range bound image of the range-culled vote kernel for that threshold
 const uint32_t* scan_images(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size_t kb, size_t nb, const Geom& g, const uint32_t** smax_out,
@@ -93,22 +99,33 @@ const uint32_t* scan_images(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, s
     uint32_t* buf = reinterpret_cast<uint32_t*>(c->pool.alloc(bytes));
     uint32_t* smax = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * sizeof(uint32_t)));
     const uint64_t first = ss.off[kb], npts = ss.off[kb + nb] - first;
-    {
+    uint64_t longest = 0;
+    for (size_t k = kb; k < kb + nb; ++k) longest = std::max<uint64_t>(longest, ss.off[k + 1] - ss.off[k]);
+    ScanBands plan;
+    if (scan_lds_plan(c, 1, &g.rows, &g.cols, longest, &plan)) {
+        // built in LDS and written once (k_scan_rimg_lds): no fill, and the bound image of the vote that asks comes out of the same pass
+        const bool with_q = qbound_thr >= 0.0f && qbound_out;
+        float* qb = with_q ? reinterpret_cast<float*>(c->pool.alloc(bytes)) : nullptr;
+        // algorithmic bytes as before (the scan2RangeImg, and the bound image's read and write when it is made); compulsory: points in, image out, bound image out
+        ProfScope p(c, "vote_scan", (double)npts, (double)npts * 16 + (double)(nb * npx) * (with_q ? 12 : 4), (double)npts * 16 + (double)(nb * npx) * (with_q ? 8 : 4));
+        LTM_HIP(hipMemsetAsync(smax, 0, nb * sizeof(uint32_t), c->stream));
+        LTM_HIP(scan_range_images_lds(ss.d, ss.off_dev, kb, nb, g, plan, &buf, &smax, with_q ? &qb : nullptr, qbound_thr, c->stream));
+        c->scan_cache.push_back(ScanImgEntry{ss_handle, g.rows, g.cols, kb, nb, buf, smax, bytes * (with_q ? 2 : 1), ++c->scan_cache_stamp, qb, with_q ? qbound_thr : -1.0f});
+    } else {
         ProfScope p(c, "vote_scan", (double)npts, (double)npts * 16 + (double)(nb * npx) * 4);
         LTM_HIP(fill_u32(buf, kNoPointBits, nb * npx, c->stream));
         LTM_HIP(hipMemsetAsync(smax, 0, nb * sizeof(uint32_t), c->stream));
-        uint64_t longest = 0;
-        for (size_t k = kb; k < kb + nb; ++k) longest = std::max<uint64_t>(longest, ss.off[k + 1] - ss.off[k]);
         LTM_HIP(scan_range_images(ss.d, ss.off_dev, kb, nb, first, npts, longest, g, buf, smax, c->stream));
+        c->scan_cache.push_back(ScanImgEntry{ss_handle, g.rows, g.cols, kb, nb, buf, smax, bytes, ++c->scan_cache_stamp, nullptr, -1.0f});
     }
-    c->scan_cache.push_back(ScanImgEntry{ss_handle, g.rows, g.cols, kb, nb, buf, smax, bytes, ++c->scan_cache_stamp, nullptr, -1.0f});
     *smax_out = smax;
     with_qbound(c->scan_cache.back());
     return buf;
 }
 
 // the finished scan images of keyframes [kb, kb+nb) for SEVERAL shapes, the missing ones computed in one pass over the scans (k_scan_rimg_multi) and cached
-void scan_images_prepare(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size_t kb, size_t nb, const std::vector<Geom>& geoms)
+// thr >= 0: the threshold of the votes that will use them -- on the LDS path their bound images are made in the same pass (otherwise by the first vote, as before)
+void scan_images_prepare(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size_t kb, size_t nb, const std::vector<Geom>& geoms, float thr)
 {
     std::vector<Geom> todo;
     for (const Geom& g : geoms) {
@@ -122,24 +139,32 @@ void scan_images_prepare(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size
     const uint64_t first = ss.off[kb], npts = ss.off[kb + nb] - first;
     uint64_t longest = 0;
     for (size_t k = kb; k < kb + nb; ++k) longest = std::max<uint64_t>(longest, ss.off[k + 1] - ss.off[k]);
+    bool dense = false;
     {
         // The one-pass kernel pays while a scan has about as many points as the smallest shape has pixels (71 x 513 at the reference's 50 degree field of view:
         // 1.3 points per pixel for the lot's os1-64 scans; cascade vote_scan 71 -> 64 ms per step with every session on it).  With several points per pixel its six
         // atomics per point pile up on the same few lines while the point's neighbours do the same: hdl-64e on the street, 3.0 per pixel of the whole image and twice
         // that where the sensor's 27 degrees actually fall, 73 -> 113 ms per step (street 3-res 1057 -> 1100 ms); the re-gridded scans a cascade hands over (3.3) sit
         // on the same side of the line and give up 5 of their 790 ms.  Above `scan_multi_max_density` (2.5) the votes compute their images one shape at a time, as
-        // before round 6 (identical images either way).
+        // before round 6 (identical images either way).  That is the global-atomic kernel's limit: k_scan_rimg_lds takes its minima in LDS and is at least as fast in one
+        // pass on those scans (vote_scan of the street step 10.34 -> 10.30 ms, of the cascade step 33.5 -> 22.2 ms), so the gate stands in front of the older kernels only.
         size_t min_px = (size_t)todo[0].rows * todo[0].cols;
         for (const Geom& t : todo) min_px = std::min(min_px, (size_t)t.rows * t.cols);
         const double density = (double)(npts / std::max<size_t>(nb, 1)) / (double)std::max<size_t>(min_px, 1);
-        if (density > c->scan_multi_max_density) return;
+        dense = density > c->scan_multi_max_density;
     }
     for (size_t at = 0; at < todo.size(); at += kMaxScanShapes) {
         const int n = (int)std::min<size_t>(kMaxScanShapes, todo.size() - at);
         int rows[kMaxScanShapes], cols[kMaxScanShapes];
         uint32_t *imgs[kMaxScanShapes], *smax[kMaxScanShapes];
+        float* qb[kMaxScanShapes];
+        for (int j = 0; j < n; ++j) { rows[j] = todo[at + j].rows; cols[j] = todo[at + j].cols; }
+        ScanBands plan;
+        const bool lds = scan_lds_plan(c, n, rows, cols, longest, &plan);
+        if (dense && !lds) continue;      // left to the votes, one shape at a time
+        const bool with_q = lds && thr >= 0.0f;
         size_t need = 0;
-        for (int j = 0; j < n; ++j) { rows[j] = todo[at + j].rows; cols[j] = todo[at + j].cols; need += nb * (size_t)rows[j] * cols[j] * sizeof(uint32_t); }
+        for (int j = 0; j < n; ++j) need += nb * (size_t)rows[j] * cols[j] * sizeof(uint32_t) * (with_q ? 2 : 1);
         size_t held = 0;
         for (const ScanImgEntry& e : c->scan_cache) held += e.bytes;
         while (!c->scan_cache.empty() && held + need > c->scan_cache_cap) {      // evict least recently used (the shapes asked for were stamped above)
@@ -154,16 +179,19 @@ void scan_images_prepare(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size
             const size_t npx = (size_t)rows[j] * cols[j];
             imgs[j] = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * npx * sizeof(uint32_t)));
             smax[j] = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * sizeof(uint32_t)));
-            c->scan_cache.push_back(ScanImgEntry{ss_handle, rows[j], cols[j], kb, nb, imgs[j], smax[j], nb * npx * sizeof(uint32_t), ++c->scan_cache_stamp, nullptr, -1.0f});
+            qb[j] = with_q ? reinterpret_cast<float*>(c->pool.alloc(nb * npx * sizeof(float))) : nullptr;
+            c->scan_cache.push_back(ScanImgEntry{ss_handle, rows[j], cols[j], kb, nb, imgs[j], smax[j], nb * npx * sizeof(uint32_t) * (with_q ? 2 : 1), ++c->scan_cache_stamp, qb[j], with_q ? thr : -1.0f});
             px_all += (double)(nb * npx);
         }
-        // algorithmic bytes as SURVEY 8d counts them: every shape is one scan2RangeImg of every scan (16 B per point read, 4 B per pixel written)
-        ProfScope p(c, "vote_scan", (double)npts * n, (double)npts * 16 * n + px_all * 4, (double)npts * 16 + px_all * 4);
+        // algorithmic bytes as SURVEY 8d counts them: every shape is one scan2RangeImg of every scan (16 B per point read, 4 B per pixel written), and a bound image
+        // is its scan image read and itself written.  Compulsory: the points once, every image written, every bound image written.
+        ProfScope p(c, "vote_scan", (double)npts * n, (double)npts * 16 * n + px_all * (with_q ? 12 : 4), (double)npts * 16 + px_all * (with_q ? 8 : 4));
         for (int j = 0; j < n; ++j) {
-            LTM_HIP(fill_u32(imgs[j], kNoPointBits, nb * (size_t)rows[j] * cols[j], c->stream));
+            if (!lds) LTM_HIP(fill_u32(imgs[j], kNoPointBits, nb * (size_t)rows[j] * cols[j], c->stream));
             LTM_HIP(hipMemsetAsync(smax[j], 0, nb * sizeof(uint32_t), c->stream));
         }
-        LTM_HIP(scan_range_images_multi(ss.d, ss.off_dev, kb, nb, npts, longest, todo[at], n, rows, cols, imgs, smax, c->stream));
+        if (lds) LTM_HIP(scan_range_images_lds(ss.d, ss.off_dev, kb, nb, todo[at], plan, imgs, smax, with_q ? qb : nullptr, thr, c->stream));
+        else LTM_HIP(scan_range_images_multi(ss.d, ss.off_dev, kb, nb, npts, longest, todo[at], n, rows, cols, imgs, smax, c->stream));
     }
 }
 
@@ -361,7 +389,7 @@ void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud
 // =========================================================================================== C ABI
 extern "C" {
 
-int ltm_scanset_prepare_range_images(ltm_ctx* c, ltm_scanset hs, size_t kf_begin, size_t kf_end, const float* alphas, size_t n_alphas)
+int ltm_scanset_prepare_vote_images(ltm_ctx* c, ltm_scanset hs, size_t kf_begin, size_t kf_end, const float* alphas, size_t n_alphas, float thr)
 {
     return guarded(c, [&] {
         LTM_REQUIRE(alphas || n_alphas == 0, "null argument");
@@ -371,8 +399,13 @@ int ltm_scanset_prepare_range_images(ltm_ctx* c, ltm_scanset hs, size_t kf_begin
         std::vector<Geom> geoms;
         for (size_t i = 0; i < n_alphas; ++i) geoms.push_back(geom_for(c, alphas[i]));
         const size_t KB = std::min(c->kf_batch, kf_end - kf_begin);      // the batches ltm_visibility_vote will ask for
-        for (size_t kb = kf_begin; kb < kf_end; kb += KB) scan_images_prepare(c, hs, ss, kb, std::min(KB, kf_end - kb), geoms);
+        for (size_t kb = kf_begin; kb < kf_end; kb += KB) scan_images_prepare(c, hs, ss, kb, std::min(KB, kf_end - kb), geoms, thr);
     });
+}
+
+int ltm_scanset_prepare_range_images(ltm_ctx* c, ltm_scanset hs, size_t kf_begin, size_t kf_end, const float* alphas, size_t n_alphas)
+{
+    return ltm_scanset_prepare_vote_images(c, hs, kf_begin, kf_end, alphas, n_alphas, -1.0f);
 }
 
 int ltm_visibility_vote(ltm_ctx* c, ltm_cloud hmap, ltm_scanset hs, ltm_poses hp, size_t kf_begin, size_t kf_end, float alpha,
@@ -622,6 +655,50 @@ int ltm_debug_vote_run_launch(size_t map_points, size_t n_keyframes, int tile_ru
     if (out_run_len) *out_run_len = len;
     if (out_grid) *out_grid = grid;
     return LTM_OK;
+}
+
+int ltm_debug_scan_bands(size_t n_shapes, const int32_t* rows, const int32_t* cols, uint32_t* out_n_bands, uint32_t* out_budget_bytes, size_t max_bands,
+                         uint32_t* out_row0, uint32_t* out_bytes)
+{
+    if (!out_n_bands || (n_shapes && (!rows || !cols))) return LTM_E_INVALID;
+    *out_n_bands = 0;
+    if (out_budget_bytes) *out_budget_bytes = (uint32_t)kScanLdsBudget;
+    ScanBands plan;
+    if (n_shapes < 1 || n_shapes > (size_t)kMaxScanShapes || !make_scan_bands((int)n_shapes, rows, cols, kScanLdsBudget, &plan)) return LTM_OK;      // not served: 0 bands
+    *out_n_bands = (uint32_t)plan.n_bands;
+    const size_t nb = std::min<size_t>((size_t)plan.n_bands, max_bands);
+    for (size_t b = 0; b < nb; ++b) {
+        if (out_bytes) out_bytes[b] = (uint32_t)scan_band_bytes(plan, (int)b);
+        if (out_row0)
+            for (size_t j = 0; j < n_shapes; ++j) {
+                out_row0[b * n_shapes + j] = (uint32_t)scan_band_row0(plan.rows[j], plan.n_bands, (int)b);
+                out_row0[(b + 1) * n_shapes + j] = (uint32_t)scan_band_row0(plan.rows[j], plan.n_bands, (int)b + 1);
+            }
+    }
+    return LTM_OK;
+}
+
+int ltm_debug_scan_images(ltm_ctx* c, ltm_scanset hs, size_t kf_begin, size_t kf_end, float alpha, float thr, float* img_out, float* smax_out, float* qbound_out)
+{
+    return guarded(c, [&] {
+        const ScanSet& ss = get_ss(c, hs);
+        LTM_REQUIRE(kf_begin <= kf_end && kf_end <= ss.nkf(), "keyframe range out of bounds");
+        LTM_REQUIRE(!qbound_out || thr >= 0.0f, "a bound image needs a threshold");
+        if (kf_begin == kf_end) return;
+        const Geom g = geom_for(c, alpha);
+        LTM_REQUIRE(g.rows > 0 && g.cols > 0, "empty range image");
+        const size_t npx = (size_t)g.rows * g.cols;
+        const size_t KB = std::min(c->kf_batch, kf_end - kf_begin);      // the batches ltm_visibility_vote asks for
+        for (size_t kb = kf_begin; kb < kf_end; kb += KB) {
+            const size_t nb = std::min(KB, kf_end - kb);
+            const uint32_t* smax = nullptr;
+            const float* qbound = nullptr;
+            const uint32_t* img = scan_images(c, hs, ss, kb, nb, g, &smax, thr, &qbound);
+            if (img_out) d2h(c, img_out + (kb - kf_begin) * npx, img, nb * npx * 4);
+            if (smax_out) d2h(c, smax_out + (kb - kf_begin), smax, nb * 4);
+            if (qbound_out) d2h(c, qbound_out + (kb - kf_begin) * npx, qbound, nb * npx * 4);
+        }
+    });
 }
 
 int ltm_debug_vote_queue_word(float vfov, float hfov, float alpha, uint32_t* out_u32, size_t n_px, const uint32_t* px, uint32_t* out_row, uint32_t* out_col)

@@ -289,7 +289,8 @@ struct ltm_ctx {
     std::vector<PendingLive> pending_live;
     unsigned long long* live_counts = nullptr;   // device, kLiveSlots entries
     std::vector<hipEvent_t> event_pool;
-    double scan_multi_max_density = 2.5;        // mean scan points per pixel of the smallest shape up to which ltm_scanset_prepare_range_images uses the one-pass kernel (scan_images_prepare)
+    double scan_multi_max_density = 2.5;        // mean scan points per pixel of the smallest shape up to which ltm_scanset_prepare_*_images uses the one-pass GLOBAL-ATOMIC kernel (scan_images_prepare; k_scan_rimg_lds is not gated); LTM_SCAN_MULTI_MAX_DENSITY
+    int scan_img_lds = 1;                       // LTM_SCAN_IMG_LDS=0: scan images by fill + global atomics + k_image_max + k_scan_qbound (the form before k_scan_rimg_lds; A/B switch and the path of shapes make_scan_bands cannot serve)
     std::vector<ScanImgEntry> scan_cache;
     uint64_t scan_cache_stamp = 0;
     size_t scan_cache_cap = (size_t)3 << 30;   // bytes

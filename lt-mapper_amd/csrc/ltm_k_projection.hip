@@ -54,6 +54,23 @@ k_scan_rimg(const float4* __restrict__ scans, const uint64_t* __restrict__ offse
 // (2.5, 2.375, 2.0, 1.9, 1.5, 1.425 pixels per degree).  The point is read once, the exact atan2f / sqrtf chain and the two divisions by the field of
 // view (shape-independent) run once, and each shape costs a multiply, a round, a clamp and its atomic -- bit for bit pixel_row_col's arithmetic.
 struct ScanShapes { int n; int rows[kMaxScanShapes], cols[kMaxScanShapes]; uint32_t* img[kMaxScanShapes]; };
+// pixel_row_col's arithmetic in its shape-independent and per-shape parts: the row and column fractions of a direction, and the clamped pixel of a fraction
+__device__ __forceinline__ float scan_row_frac(const RimgGeom& g, float el)
+{
+    const float el_deg = g.fast ? rad2deg_fast(el) : rad2deg_exact(el);
+    return 1.0f - div_by_const(el_deg + g.half_v, g.vfov, g.inv_v, g.fast);
+}
+__device__ __forceinline__ float scan_col_frac(const RimgGeom& g, float az)
+{
+    const float az_deg = g.fast ? rad2deg_fast(az) : rad2deg_exact(az);
+    return div_by_const(az_deg + g.half_h, g.hfov, g.inv_h, g.fast);
+}
+__device__ __forceinline__ int scan_clamped_px(float fn, float frac)      // fn = (float)rows or (float)cols
+{
+    float f = roundf(fn * frac);
+    f = (f < 0.0f) ? 0.0f : f;  f = (fn - 1.0f < f) ? fn - 1.0f : f;
+    return (int)f;
+}
 __global__ void __launch_bounds__(kBlock)
 k_scan_rimg_multi(const float4* __restrict__ scans, const uint64_t* __restrict__ offsets, size_t kb, Geom gg, ScanShapes sh)
 {
@@ -63,20 +80,15 @@ k_scan_rimg_multi(const float4* __restrict__ scans, const uint64_t* __restrict__
     const RimgGeom g = make_geom(gg);      // rows / cols of gg are not used: only the field of view and the fast-form switch
     const float4 p = scans[a + local];
     const Sph s = cart2sph(p.x, p.y, p.z);
-    const float el_deg = g.fast ? rad2deg_fast(s.el) : rad2deg_exact(s.el);
-    const float az_deg = g.fast ? rad2deg_fast(s.az) : rad2deg_exact(s.az);
-    const float u = 1.0f - div_by_const(el_deg + g.half_v, g.vfov, g.inv_v, g.fast);
-    const float w = div_by_const(az_deg + g.half_h, g.hfov, g.inv_h, g.fast);
+    const float u = scan_row_frac(g, s.el);
+    const float w = scan_col_frac(g, s.az);
     const uint32_t rbits = f2u(s.r);
 #pragma unroll
     for (int j = 0; j < kMaxScanShapes; ++j) {
         if (j >= sh.n) break;
-        const float frows = (float)sh.rows[j], fcols = (float)sh.cols[j];
-        float fr = roundf(frows * u), fc = roundf(fcols * w);
-        fr = (fr < 0.0f) ? 0.0f : fr;  fr = (frows - 1.0f < fr) ? frows - 1.0f : fr;
-        fc = (fc < 0.0f) ? 0.0f : fc;  fc = (fcols - 1.0f < fc) ? fcols - 1.0f : fc;
+        const int row = scan_clamped_px((float)sh.rows[j], u), col = scan_clamped_px((float)sh.cols[j], w);
         const size_t npx = (size_t)sh.rows[j] * (size_t)sh.cols[j];
-        img_min_u32(sh.img[j] + (size_t)blockIdx.y * npx + (size_t)((int)fr * sh.cols[j] + (int)fc), rbits);
+        img_min_u32(sh.img[j] + (size_t)blockIdx.y * npx + (size_t)(row * sh.cols[j] + col), rbits);
     }
 }
 
@@ -108,12 +120,8 @@ k_image_max(const uint32_t* __restrict__ img, uint32_t npx, uint32_t* __restrict
 // r2 of its approximate projection, r_e^2 >= r2 (1 - 3e-6) (validated bound), so it may drop the point iff
 // r2 >= ((s - thr + 1e-3) (1 + 1e-5))^2, rounded up.  Empty pixels (10000) never flag below 9800 m (and farther points take the
 // exact path): 0.  Evaluated in double, rounded up to float.
-__global__ void __launch_bounds__(kBlock)
-k_scan_qbound(const uint32_t* __restrict__ scan_img, size_t n, float thr, float* __restrict__ qbound)
+__device__ __forceinline__ float scan_qbound_of(uint32_t sb, float thr)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t sb = scan_img[i];
     float q = 0.0f;
     if (sb < kNoPointBits) {
         const double lim = ((double)u2f(sb) - (double)thr + 1.0e-3) * (1.0 + 1.0e-5);
@@ -123,7 +131,14 @@ k_scan_qbound(const uint32_t* __restrict__ scan_img, size_t n, float thr, float*
             if ((double)q < q2) q = u2f(f2u(q) + 1u);      // round up (q > 0)
         }
     }
-    qbound[i] = q;
+    return q;
+}
+__global__ void __launch_bounds__(kBlock)
+k_scan_qbound(const uint32_t* __restrict__ scan_img, size_t n, float thr, float* __restrict__ qbound)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    qbound[i] = scan_qbound_of(scan_img[i], thr);
 }
 hipError_t scan_qbound(const uint32_t* scan_img, size_t n, float thr, float* qbound, hipStream_t s)
 {
@@ -168,6 +183,252 @@ hipError_t scan_range_images_multi(const float4* scans, const uint64_t* offsets_
             const uint32_t npx = (uint32_t)(rows[j] * cols[j]);
             k_image_max<<<dim3(std::min<unsigned>(grid_for(npx, kBlock * 8), 64), (unsigned)nb), dim3(kBlock), 0, s>>>(imgs[j], npx, smax_bits[j]);
         }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------ scan images built in LDS
+// The same images without a fill, without global atomics and without the two read-back passes (k_image_max, k_scan_qbound): one workgroup owns one band of
+// one keyframe (ltm_kernels.h: ScanBands), keeps the band's rows of every shape in LDS, streams ALL points of the keyframe over it and writes every pixel of
+// the band out exactly once, with the per-shape maximum and (when a threshold is given) the bound image in the same loop.
+//   * Per point and band only a first reject runs: z against tan(elevation) * sqrt(x^2 + y^2) for the two elevations that bound the band's rows over all
+//     shapes, widened by kScanBandMarginDeg (0.01 degrees, four orders of magnitude above the float error of either side).  It only ever lets too many
+//     points through: what passes is projected with today's arithmetic (cart2sph, the row / column fractions, multiply / round / clamp per shape) and
+//     enters a shape only when its exact row lies in the band, so the images do not depend on the reject, only the time.  The bands cut all shapes at
+//     the same elevations, so a point passes in one band, seldom two.  (The exact elevation half in every band, the first form, was VALU-bound at four
+//     times the time: NOTEBOOK 4.1.)
+//   * The points that pass are queued per wave in LDS and projected 64 at a time: the exact arithmetic runs with full waves whatever the order of the
+//     scan (ring-major scans pass whole waves, voxel-ordered ones a few lanes of each).
+//   * Workgroups b, b + 8, b + 16, ... run on the same XCD (see tile_kf_of_block): the bands of a keyframe follow each other there, so its points come from
+//     HBM once and from that XCD's L2 for the other bands.
+// The minimum of positive float bit patterns does not depend on the order, so the images are those of k_scan_rimg / k_scan_rimg_multi bit for bit.
+struct ScanLdsArgs {
+    int n, n_bands;
+    int rows[kMaxScanShapes], cols[kMaxScanShapes];
+    uint32_t* img[kMaxScanShapes]; uint32_t* smax[kMaxScanShapes]; float* qbound[kMaxScanShapes];
+    float thr;
+};
+__global__ void __launch_bounds__(kScanLdsThreads)
+k_scan_rimg_lds(const float4* __restrict__ scans, const uint64_t* __restrict__ offsets, size_t kb, uint32_t nk, Geom gg, ScanLdsArgs sh)
+{
+    constexpr int kWaves = kScanLdsThreads / 64;
+    __shared__ uint4 s_img4[kScanLdsBudget / 16];
+    __shared__ uint32_t s_queue[kWaves][128];
+    __shared__ uint32_t s_max[kMaxScanShapes][kWaves];
+    static_assert(sizeof(s_img4) + sizeof(s_queue) + sizeof(s_max) == (size_t)160 * 1024, "the workgroup declares the CU's whole LDS");
+    uint32_t* const s_img = reinterpret_cast<uint32_t*>(s_img4);
+
+    const uint32_t b = blockIdx.x, q8 = b >> 3;
+    const uint32_t band = q8 % (uint32_t)sh.n_bands, kfl = (q8 / (uint32_t)sh.n_bands) * 8u + (b & 7u);
+    if (kfl >= nk) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const RimgGeom g = make_geom(gg);      // rows / cols of gg are not used: only the field of view and the fast-form switch
+
+    // the band: per shape its rows [row0, row1), the LDS word its first pixel sits at, the global pixel that is
+    int row0[kMaxScanShapes], row1[kMaxScanShapes];
+    uint32_t lbase[kMaxScanShapes];
+    uint32_t band_words = 0;
+#pragma unroll
+    for (int j = 0; j < kMaxScanShapes; ++j) {
+        row0[j] = row1[j] = 0; lbase[j] = 0;
+        if (j >= sh.n) continue;
+        row0[j] = scan_band_row0(sh.rows[j], sh.n_bands, (int)band);
+        row1[j] = scan_band_row0(sh.rows[j], sh.n_bands, (int)band + 1);
+        lbase[j] = band_words;
+        band_words += (uint32_t)scan_band_shape_words(row1[j] - row0[j], sh.cols[j]);
+    }
+    for (uint32_t i = tid; i < band_words / 4u; i += kScanLdsThreads) s_img4[i] = make_uint4(kNoPointBits, kNoPointBits, kNoPointBits, kNoPointBits);
+    // (shape j's pixels start `pad` words into its range, pad = the global pixel offset mod 4: an aligned group of four in LDS is an aligned group in HBM)
+    uint32_t pad[kMaxScanShapes];
+#pragma unroll
+    for (int j = 0; j < kMaxScanShapes; ++j) {
+        pad[j] = 0;
+        if (j >= sh.n) continue;
+        const size_t gofs = (size_t)kfl * ((size_t)sh.rows[j] * (size_t)sh.cols[j]) + (size_t)row0[j] * (size_t)sh.cols[j];
+        pad[j] = (uint32_t)(gofs & 3u);
+    }
+    __syncthreads();
+
+    const size_t lo = kb + kfl;
+    const uint64_t a = offsets[lo];
+    const uint32_t n = (uint32_t)(offsets[lo + 1] - a);
+    const float4* __restrict__ pts = scans + a;
+    uint32_t qn = 0;      // entries in this wave's queue (wave-uniform, < 64 between points)
+
+    // the first reject: tangents of the elevations that bound the band (see above); a side that reaches the image's first / last row, where everything
+    // beyond is clamped into the band, or comes within a degree of the pole, is not tested
+    float t_lo = 0.0f, t_hi = 0.0f;
+    bool has_lo = false, has_hi = false;
+    {
+        double el_lo = 1.0e9, el_hi = -1.0e9;      // degrees
+        bool open_lo = false, open_hi = false;
+#pragma unroll
+        for (int j = 0; j < kMaxScanShapes; ++j) {
+            if (j >= sh.n || row1[j] <= row0[j]) continue;
+            // row = round(rows * u), u = 1 - (el_deg + vfov / 2) / vfov: row >= row0 <=> rows * u >= row0 - 0.5, row < row1 <=> rows * u < row1 - 0.5
+            if (row0[j] == 0) open_hi = true;
+            else el_hi = fmax(el_hi, (1.0 - ((double)row0[j] - 0.5) / (double)sh.rows[j]) * (double)gg.vfov - 0.5 * (double)gg.vfov);
+            if (row1[j] == sh.rows[j]) open_lo = true;
+            else el_lo = fmin(el_lo, (1.0 - ((double)row1[j] - 0.5) / (double)sh.rows[j]) * (double)gg.vfov - 0.5 * (double)gg.vfov);
+        }
+        el_lo -= kScanBandMarginDeg; el_hi += kScanBandMarginDeg;
+        has_lo = !open_lo && el_lo > -89.0 && el_lo < 89.0;
+        has_hi = !open_hi && el_hi > -89.0 && el_hi < 89.0;
+        if (el_lo >= 89.0 && !open_lo) { has_lo = true; el_lo = 89.0; }          // (a band wholly above 89 degrees: still a lower bound)
+        if (el_hi <= -89.0 && !open_hi) { has_hi = true; el_hi = -89.0; }
+        if (has_lo) t_lo = (float)tan(el_lo * (3.14159265358979323846 / 180.0));
+        if (has_hi) t_hi = (float)tan(el_hi * (3.14159265358979323846 / 180.0));
+    }
+
+    auto drain = [&](uint32_t from, uint32_t cnt) {      // project queue entries [from, from + cnt), cnt <= 64
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // the entries were written by other lanes of this wave
+        if (lane < cnt) {
+            const float4 p = pts[s_queue[wave][from + lane]];
+            const Sph sp = cart2sph(p.x, p.y, p.z);
+            const float u = scan_row_frac(g, sp.el), w = scan_col_frac(g, sp.az);
+            const uint32_t rbits = f2u(sp.r);
+#pragma unroll
+            for (int j = 0; j < kMaxScanShapes; ++j) {
+                if (j >= sh.n) break;
+                const int row = scan_clamped_px((float)sh.rows[j], u);
+                if (row >= row0[j] && row < row1[j]) {
+                    const int col = scan_clamped_px((float)sh.cols[j], w);
+                    atomicMin(&s_img[lbase[j] + pad[j] + (uint32_t)((row - row0[j]) * sh.cols[j] + col)], rbits);
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");      // read before the next points overwrite them
+    };
+
+    constexpr uint32_t kAhead = 4;      // loads in flight per lane
+    for (uint32_t i0 = 0; i0 < n; i0 += kScanLdsThreads * kAhead) {      // (block-uniform trip count)
+        float4 p[kAhead];
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; ++k) {
+            const uint32_t i = i0 + k * kScanLdsThreads + tid;
+            p[k] = pts[i < n ? i : 0u];      // (n > 0 inside the loop)
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kAhead; ++k) {
+            const uint32_t i = i0 + k * kScanLdsThreads + tid;
+            const float xx = p[k].x * p[k].x, yy = p[k].y * p[k].y;
+            const float xy = xx + yy;
+            const float rho = __builtin_amdgcn_sqrtf(xy);
+            // written as rejects, so that a NaN anywhere passes; so does a point on the axis (xy tiny: elevation +-90 degrees or, at the origin, 0)
+            const bool out = (xy > 1.0e-30f) && ((has_lo && p[k].z < t_lo * rho) || (has_hi && p[k].z > t_hi * rho));
+            const bool hit = !out && i < n;
+            const uint64_t m = __ballot(hit);
+            if (m) {
+                if (hit) s_queue[wave][qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = i;
+                qn += (uint32_t)__popcll(m);
+                if (qn >= 64u) { qn -= 64u; drain(qn, 64u); }
+            }
+        }
+    }
+    if (qn) drain(0u, qn);
+    __syncthreads();
+
+    // write-out: every pixel of the band once, in aligned groups of four; the first and last group of a range may be shared with the neighbouring band or
+    // keyframe and go out pixel by pixel
+#pragma unroll
+    for (int j = 0; j < kMaxScanShapes; ++j) {
+        if (j >= sh.n) break;
+        const uint32_t nw = (uint32_t)((row1[j] - row0[j]) * sh.cols[j]);
+        uint32_t mx = 0;
+        if (nw) {
+            const size_t gofs = (size_t)kfl * ((size_t)sh.rows[j] * (size_t)sh.cols[j]) + (size_t)row0[j] * (size_t)sh.cols[j] - pad[j];      // multiple of 4
+            uint32_t* __restrict__ gimg = sh.img[j] + gofs;
+            float* __restrict__ gq = sh.qbound[j] ? sh.qbound[j] + gofs : nullptr;
+            const uint32_t end = pad[j] + nw, ngroups = (end + 3u) >> 2;
+            for (uint32_t k = tid; k < ngroups; k += kScanLdsThreads) {
+                const uint4 v = s_img4[(lbase[j] >> 2) + k];
+                const uint32_t w0 = k * 4u;
+                if (w0 >= pad[j] && w0 + 4u <= end) {
+                    reinterpret_cast<uint4*>(gimg)[k] = v;
+                    mx = max(mx, v.x < kNoPointBits ? v.x : 0u); mx = max(mx, v.y < kNoPointBits ? v.y : 0u);
+                    mx = max(mx, v.z < kNoPointBits ? v.z : 0u); mx = max(mx, v.w < kNoPointBits ? v.w : 0u);
+                    if (gq) reinterpret_cast<float4*>(gq)[k] = make_float4(scan_qbound_of(v.x, sh.thr), scan_qbound_of(v.y, sh.thr), scan_qbound_of(v.z, sh.thr), scan_qbound_of(v.w, sh.thr));
+                } else {
+                    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (uint32_t t = 0; t < 4u; ++t) {
+                        if (w0 + t < pad[j] || w0 + t >= end) continue;
+                        gimg[w0 + t] = e[t];
+                        mx = max(mx, e[t] < kNoPointBits ? e[t] : 0u);
+                        if (gq) gq[w0 + t] = scan_qbound_of(e[t], sh.thr);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, off, 64));
+        if (lane == 0) s_max[j][wave] = mx;
+    }
+    __syncthreads();
+    if (tid < (uint32_t)sh.n) {
+        uint32_t mx = 0;
+        for (int w = 0; w < kWaves; ++w) mx = max(mx, s_max[tid][w]);
+        // (dynamic index into the argument arrays would put them into scratch: select)
+        uint32_t* smax = nullptr;
+#pragma unroll
+        for (int j = 0; j < kMaxScanShapes; ++j) smax = ((int)tid == j) ? sh.smax[j] : smax;
+        if (mx && smax) atomicMax(smax + kfl, mx);
+    }
+}
+
+size_t scan_band_bytes(const ScanBands& p, int b)
+{
+    size_t words = 0;
+    for (int j = 0; j < p.n_shapes; ++j) words += scan_band_shape_words(scan_band_row0(p.rows[j], p.n_bands, b + 1) - scan_band_row0(p.rows[j], p.n_bands, b), p.cols[j]);
+    return words * 4;
+}
+bool make_scan_bands(int n_shapes, const int* rows, const int* cols, size_t budget, ScanBands* out)
+{
+    if (n_shapes < 1 || n_shapes > kMaxScanShapes || !rows || !cols || !out) return false;
+    ScanBands p{};
+    p.n_shapes = n_shapes;
+    int max_rows = 0;
+    size_t all = 0;
+    for (int j = 0; j < n_shapes; ++j) {
+        if (rows[j] < 1 || cols[j] < 1 || (size_t)rows[j] * (size_t)cols[j] > 0x7fffffffull) return false;
+        p.rows[j] = rows[j]; p.cols[j] = cols[j];
+        max_rows = std::max(max_rows, rows[j]);
+        all += scan_band_shape_words(rows[j], cols[j]) * 4;
+    }
+    // more bands than the tallest shape has rows cut nothing smaller: band 0 then still holds one row of every shape
+    const int last = std::min(max_rows, kMaxScanBands);
+    for (int nb = (int)std::min<size_t>((all + budget - 1) / std::max<size_t>(budget, 1), (size_t)last); nb <= last; ++nb) {
+        if (nb < 1) continue;
+        p.n_bands = nb;
+        size_t worst = 0;
+        for (int b = 0; b < nb && worst <= budget; ++b) worst = std::max(worst, scan_band_bytes(p, b));
+        if (worst <= budget) { p.max_band_bytes = worst; *out = p; return true; }
+    }
+    return false;
+}
+
+hipError_t scan_range_images_lds(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, Geom g, const ScanBands& plan,
+                                 uint32_t* const* imgs, uint32_t* const* smax_bits, float* const* qbounds, float thr, hipStream_t s)
+{
+    if (plan.n_shapes < 1 || plan.n_shapes > kMaxScanShapes || plan.n_bands < 1 || plan.max_band_bytes > kScanLdsBudget) return hipErrorInvalidValue;
+    for (int b = 0; b < plan.n_bands; ++b)
+        if (scan_band_bytes(plan, b) > kScanLdsBudget) return hipErrorInvalidValue;      // the kernel lays its LDS out by the same formula
+    ScanLdsArgs sh{};
+    sh.n = plan.n_shapes; sh.n_bands = plan.n_bands; sh.thr = thr;
+    for (int j = 0; j < plan.n_shapes; ++j) {
+        if ((reinterpret_cast<uintptr_t>(imgs[j]) & 15u) || (qbounds && (reinterpret_cast<uintptr_t>(qbounds[j]) & 15u))) return hipErrorInvalidValue;
+        sh.rows[j] = plan.rows[j]; sh.cols[j] = plan.cols[j];
+    }
+    const size_t per_launch = std::max<size_t>(8, (((size_t)1 << 30) / (size_t)plan.n_bands) & ~(size_t)7);      // keyframes of one grid, a multiple of 8
+    for (size_t k0 = 0; k0 < nb; k0 += per_launch) {
+        const size_t nk = std::min(per_launch, nb - k0);
+        for (int j = 0; j < plan.n_shapes; ++j) {
+            const size_t npx = (size_t)plan.rows[j] * (size_t)plan.cols[j];      // (k0 is a multiple of 8: the alignment holds)
+            sh.img[j] = imgs[j] + k0 * npx;
+            sh.smax[j] = (smax_bits && smax_bits[j]) ? smax_bits[j] + k0 : nullptr;
+            sh.qbound[j] = (qbounds && qbounds[j]) ? qbounds[j] + k0 * npx : nullptr;
+        }
+        k_scan_rimg_lds<<<dim3((unsigned)(((nk + 7) / 8) * 8 * (size_t)plan.n_bands)), dim3(kScanLdsThreads), 0, s>>>(scans, offsets_dev, kb + k0, (uint32_t)nk, g, sh);
+    }
     return hipGetLastError();
 }
 

@@ -43,6 +43,32 @@ static constexpr int kMaxScanShapes = 8;
 hipError_t scan_range_images_multi(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t n_pts, uint64_t max_kf_pts, Geom g,
                                    int n_shapes, const int* rows, const int* cols, uint32_t* const* imgs, uint32_t* const* smax_bits, hipStream_t s);
 hipError_t scan_qbound(const uint32_t* scan_img, size_t n, float thr, float* qbound, hipStream_t s);
+// The same images built in LDS and written once (k_scan_rimg_lds): one workgroup per (keyframe, band).  A band is, for every shape, a contiguous range of
+// its rows -- band b of B holds rows [b rows / B, (b + 1) rows / B) -- so the bands cut every shape at (nearly) the same elevations and a point lands in
+// one band, or two next to each other, for all shapes at once.  All row ranges of a band lie one behind the other in the workgroup's LDS, each rounded up to
+// whole 16-byte words plus one (the kernel shifts a range by up to 3 pixels so that LDS and global addresses are aligned alike).
+static constexpr int kScanLdsThreads = 1024;                                                            // 16 waves: the only workgroup of its CU
+static constexpr size_t kScanLdsQueueBytes = (size_t)(kScanLdsThreads / 64) * 128 * 4;                  // per wave 128 queued points
+static constexpr size_t kScanLdsReduceBytes = (size_t)kMaxScanShapes * (kScanLdsThreads / 64) * 4;      // per shape and wave one partial maximum
+static constexpr size_t kScanLdsBudget = (size_t)160 * 1024 - kScanLdsQueueBytes - kScanLdsReduceBytes; // image bytes of a band: 155136
+static constexpr int kMaxScanBands = 4096;
+static constexpr double kScanBandMarginDeg = 0.01;      // how far the kernel's first reject stays outside a band's elevations
+struct ScanBands { int n_shapes; int rows[kMaxScanShapes], cols[kMaxScanShapes]; int n_bands; size_t max_band_bytes; };
+#ifdef __HIPCC__
+#define LTM_HOST_DEVICE __host__ __device__
+#else
+#define LTM_HOST_DEVICE
+#endif
+LTM_HOST_DEVICE inline int scan_band_row0(int rows, int n_bands, int b) { return (int)(((long long)b * rows) / n_bands); }      // first row of band b (b = n_bands: rows)
+LTM_HOST_DEVICE inline size_t scan_band_shape_words(int band_rows, int cols) { return (((size_t)band_rows * (size_t)cols + 3u) + 3u) & ~(size_t)3u; }
+size_t scan_band_bytes(const ScanBands& p, int b);
+// the plan with the fewest bands whose bytes fit `budget`; false when there is none (a single row of all shapes together is wider than the budget, more than
+// kMaxScanShapes shapes, a shape without pixels, more than kMaxScanBands bands): those take scan_range_images / scan_range_images_multi
+bool make_scan_bands(int n_shapes, const int* rows, const int* cols, size_t budget, ScanBands* out);
+// imgs[j] need no fill: every pixel is written exactly once.  smax_bits[j] zeroed by the caller.  qbounds (nullable, and each entry nullable): the bound image of
+// scan_qbound for `thr`, written in the same pass.  Every image pointer 16-byte aligned; no keyframe longer than 2^32 - 1 points.
+hipError_t scan_range_images_lds(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, Geom g, const ScanBands& plan,
+                                 uint32_t* const* imgs, uint32_t* const* smax_bits, float* const* qbounds, float thr, hipStream_t s);
 // bounds[6*t..] = {min xyz, max xyz} of map points [4096 t, 4096 (t+1))
 hipError_t tile_bounds(const float4* map, size_t M, float* bounds, hipStream_t s);
 hipError_t subtile_bounds(const float4* map, size_t M, float* bounds, hipStream_t s);   // 4 x 6 floats per 4096-point tile: its 1024-point quarters

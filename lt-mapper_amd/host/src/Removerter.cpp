@@ -311,7 +311,8 @@ void Removerter::selfRemovert(const Session& _sess, int _repeat = 1)            
         ltm_poses ph = 0; size_t kb = 0, ke = 0;
         _sess.stageArgs(_sess.keyframe_scans_, &ph, &kb, &ke);
         ltm_ctx* ctx = _sess.dev_->ctx;
-        ltmCheck(ctx, ltm_scanset_prepare_range_images(ctx, _sess.keyframe_scans_->h, kb, ke, alphas.data(), alphas.size()), "ltm_scanset_prepare_range_images");
+        // (0.1f: the threshold partitionCurrentMap votes with -- the bound images of those votes come out of the same pass)
+        ltmCheck(ctx, ltm_scanset_prepare_vote_images(ctx, _sess.keyframe_scans_->h, kb, ke, alphas.data(), alphas.size(), 0.1f), "ltm_scanset_prepare_vote_images");
     }
     for (float _res : remove_resolution_list_) {
         for (int i = 0; i < _repeat; i++) {

@@ -65,7 +65,7 @@ class HipOps:
     def voxel_grid_scanset_end(self, ticket): return self.ctx.voxel_grid_scanset_end(ticket)
     def preclean(self, s, radius): return self.ctx.preclean(s, radius)                      # Session.cpp:506-533
     def vote_partition(self, cmap, scans, poses, alpha, thr, mode): return self.ctx.visibility_partition(cmap, scans, poses, alpha, thr, mode)
-    def prepare_scan_images(self, scans, alphas): self.ctx.prepare_scan_images(scans, alphas)
+    def prepare_scan_images(self, scans, alphas, thr=-1.0): self.ctx.prepare_vote_images(scans, alphas, thr)
     def reproject(self, cmap, poses, alpha): return self.ctx.reproject(cmap, poses, alpha)
     def knn_partition(self, target, scans, poses, k, thr): return self.ctx.knn_partition(target, scans, poses, k, thr)
     def knn_split(self, target, query, k, thr): return self.ctx.knn_split_cloud(target, query, k, thr)
@@ -243,7 +243,7 @@ class Removerter:
         prepare = getattr(ops or self.ops, "prepare_scan_images", None)
         if prepare is not None and repeat > 0:      # every scan image the passes below will ask for, in one pass over the scans
             rs = [float(np.float32(r)) for r in self.P.remove_resolution_list]
-            prepare(sess.keyframe_scans_, rs + [float(np.float32(0.95 * r)) for r in rs])
+            prepare(sess.keyframe_scans_, rs + [float(np.float32(0.95 * r)) for r in rs], 0.1)      # 0.1: removeOnce's / revertOnce's threshold
         for res in self.P.remove_resolution_list:
             res = float(np.float32(res))
             for _ in range(repeat):                                            # `i < _repeat`, Removerter.cpp:1381: repeat 0 runs nothing
