@@ -250,8 +250,8 @@ int ltm_scanset_prepare_range_images(ltm_ctx*, ltm_scanset scans, size_t kf_begi
 /* The same, plus the threshold the votes that follow will be called with (diff_thres of ltm_visibility_vote; < 0: none, which is the entry above).
  * The images are built in the CU's LDS and written once (k_scan_rimg_lds: no fill, no global atomics), and with a threshold the bound images of the
  * range-culled vote for it come out of the same pass instead of a pass of their own at the first vote.  A vote with another threshold rebuilds its bound
- * image as before.  Context switch LTM_SCAN_IMG_LDS (read by ltm_create, default 1): 0 takes the fill / global-atomic / read-back kernels, which shape sets
- * the LDS plan cannot serve (ltm_debug_scan_bands) take in any case.  Images, maxima and bound images are the same bits either way. */
+ * image as before.  Context switch LTM_SCAN_IMG_LDS (read by ltm_create, default 1): 0 takes the fill / global-atomic / read-back kernels (k_scan_rimg_multi for one
+ * shape or several, k_image_max, k_scan_qbound), which shape sets the LDS plan cannot serve (ltm_debug_scan_bands) take in any case.  Images, maxima and bound images are the same bits either way. */
 int ltm_scanset_prepare_vote_images(ltm_ctx*, ltm_scanset scans, size_t kf_begin, size_t kf_end, const float* res_alphas, size_t n_alphas, float diff_thres);
 /* partitionCurrentMap tail (Removerter.cpp:816-824, :675-687, :933-946): index-ascending split */
 int ltm_partition_by_labels(ltm_ctx*, ltm_cloud map, const uint8_t* labels_dev, ltm_cloud* kept, ltm_cloud* flagged);

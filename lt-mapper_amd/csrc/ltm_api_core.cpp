@@ -323,7 +323,7 @@ const char* ltm_last_error(const ltm_ctx* c) { return c ? c->err.c_str() : "null
 
 int ltm_synchronize(ltm_ctx* c) { return guarded(c, [&] { sync(c); }); }
 
-int ltm_clear_caches(ltm_ctx* c) { return guarded(c, [&] { sync(c); scan_cache_drop(c, 0); }); }
+int ltm_clear_caches(ltm_ctx* c) { return guarded(c, [&] { sync(c); c->scan_cache.drop(0); }); }
 
 void* ltm_stream(ltm_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
@@ -629,7 +629,7 @@ int ltm_scanset_alloc(ltm_ctx* c, const uint64_t* off, size_t n_kf, ltm_scanset*
 
 int ltm_scanset_free(ltm_ctx* c, ltm_scanset h)
 {
-    return guarded(c, [&] { ScanSet& s = get_ss(c, h); scan_cache_drop(c, h); if (!s.borrowed) { c->pool.free(s.d); c->pool.free(s.off_dev); } c->scansets.erase(h); });
+    return guarded(c, [&] { ScanSet& s = get_ss(c, h); c->scan_cache.drop(h); if (!s.borrowed) { c->pool.free(s.d); c->pool.free(s.off_dev); } c->scansets.erase(h); });
 }
 
 // ------------------------------------------------------------------ pipelined upload / async fetch
@@ -1015,7 +1015,7 @@ int ltm_lane_create(ltm_ctx* parent, ltm_ctx** out)
         c->l2b_identity = parent->l2b_identity; c->b2l_identity = parent->b2l_identity; c->kf_batch = parent->kf_batch; c->kopts = parent->kopts;
         c->fast_math = parent->fast_math;      // the exhaustive create-time self-check is a property of (device, vfov, hfov): not repeated
         for (int i = 0; i < 3; ++i) c->selfcheck[i] = parent->selfcheck[i];
-        c->scan_cache_cap = parent->scan_cache_cap; c->scan_img_lds = parent->scan_img_lds; c->scan_multi_max_density = parent->scan_multi_max_density; c->occlusion_cull = parent->occlusion_cull;
+        c->scan_cache.cap = parent->scan_cache.cap; c->scan_img_lds = parent->scan_img_lds; c->scan_multi_max_density = parent->scan_multi_max_density; c->occlusion_cull = parent->occlusion_cull;
         c->occlusion_min_pairs = parent->occlusion_min_pairs; c->occlusion_r_near = parent->occlusion_r_near;
         c->occlusion_subtile = parent->occlusion_subtile; c->occlusion_stats_on = parent->occlusion_stats_on;
         c->voxel_key_compress = parent->voxel_key_compress; c->voxel_fused_tail = parent->voxel_fused_tail; c->voxel_identity = parent->voxel_identity;
@@ -1106,7 +1106,7 @@ static int scanset_pass(ltm_ctx* from, ltm_scanset h, ltm_ctx* to, ltm_scanset* 
         dst.d = src.d; dst.n_pts = src.n_pts; dst.off = src.off; dst.off_dev = src.off_dev; dst.borrowed = !give;
         if (give) {
             LTM_REQUIRE(from->pool.owns(src.d) && from->pool.owns(src.off_dev), "scan set memory is not owned by this context's pool");
-            scan_cache_drop(from, h);
+            from->scan_cache.drop(h);
             from->pool.move_to(src.d, to->pool); from->pool.move_to(src.off_dev, to->pool);
             from->scansets.erase(h);
         }

@@ -52,18 +52,48 @@ size_t scan_total_u8(ltm_ctx* c, const uint8_t* labels, const uint32_t* pos, siz
 }
 
 // --------------------------------------------------------------------------------- vote
-void scan_cache_drop(ltm_ctx* c, uint64_t ss_handle)
+// Builds the scan range images of keyframes [kb, kb+nb) for the n <= kMaxScanShapes shapes of geoms[0 .. n) (one field of view, none of them cached) in one pass
+// over the scans and caches them: in LDS, written once (k_scan_rimg_lds), where the band plan serves the shapes, else by fill + k_scan_rimg_multi + k_image_max.
+// thr >= 0: the threshold of the votes that will use them -- the LDS pass writes their bound images as well (otherwise the first vote makes them, scan_images).
+// lds_only: without a band plan nothing is built (the density gate of scan_images_prepare).
+// The buffers belong to the stage until every launch has been issued: whatever throws before that, they go back to the pool and the cache holds no entry of this build.
+static void build_scan_images(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size_t kb, size_t nb, const Geom* geoms, int n, float thr, bool lds_only)
 {
-    for (size_t i = 0; i < c->scan_cache.size();) {
-        if (ss_handle == 0 || c->scan_cache[i].ss == ss_handle) { c->pool.free(c->scan_cache[i].buf); c->pool.free(c->scan_cache[i].smax); c->pool.free(c->scan_cache[i].qbound); c->scan_cache.erase(c->scan_cache.begin() + i); }
-        else ++i;
+    const uint64_t npts = ss.off[kb + nb] - ss.off[kb];
+    uint64_t longest = 0;
+    for (size_t k = kb; k < kb + nb; ++k) longest = std::max<uint64_t>(longest, ss.off[k + 1] - ss.off[k]);
+    int rows[kMaxScanShapes], cols[kMaxScanShapes];
+    for (int j = 0; j < n; ++j) { rows[j] = geoms[j].rows; cols[j] = geoms[j].cols; }
+    // the band plan of k_scan_rimg_lds, unless the switch is off or the shapes / the scans are outside what that kernel serves
+    ScanBands plan;
+    const bool lds = c->scan_img_lds != 0 && longest < 0xffffffffull && make_scan_bands(n, rows, cols, kScanLdsBudget, &plan);
+    if (lds_only && !lds) return;
+    const bool with_q = lds && thr >= 0.0f;
+    size_t px_all = 0;
+    for (int j = 0; j < n; ++j) px_all += nb * (size_t)rows[j] * cols[j];
+    c->scan_cache.make_room(px_all * sizeof(uint32_t) * (with_q ? 2 : 1));      // exactly what is allocated below (the nb maxima per shape are not counted)
+    ScanCacheStage stage(c->scan_cache, (size_t)n);
+    uint32_t *imgs[kMaxScanShapes], *smax[kMaxScanShapes];
+    float* qb[kMaxScanShapes];
+    for (int j = 0; j < n; ++j) {
+        const size_t bytes = nb * (size_t)rows[j] * cols[j] * sizeof(uint32_t);
+        ScanImgEntry& e = stage.add(ss_handle, rows[j], cols[j], kb, nb, bytes * (with_q ? 2 : 1), with_q ? thr : -1.0f);
+        imgs[j] = e.buf = reinterpret_cast<uint32_t*>(c->pool.alloc(bytes));
+        smax[j] = e.smax = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * sizeof(uint32_t)));
+        qb[j] = e.qbound = with_q ? reinterpret_cast<float*>(c->pool.alloc(bytes)) : nullptr;
     }
-}
-
-// the band plan of k_scan_rimg_lds for these shapes, or false: the switch is off, or the shapes / the scans are outside what the kernel serves
-static bool scan_lds_plan(const ltm_ctx* c, int n, const int* rows, const int* cols, uint64_t longest_kf, ScanBands* plan)
-{
-    return c->scan_img_lds != 0 && longest_kf < 0xffffffffull && make_scan_bands(n, rows, cols, kScanLdsBudget, plan);
+    {
+        // algorithmic bytes as SURVEY 8d counts them: every shape is one scan2RangeImg of every scan (16 B per point read, 4 B per pixel written), and a bound image
+        // is its scan image read and itself written.  Compulsory: the points once, every image written, every bound image written.
+        ProfScope p(c, "vote_scan", (double)npts * n, (double)npts * 16 * n + (double)px_all * (with_q ? 12 : 4), (double)npts * 16 + (double)px_all * (with_q ? 8 : 4));
+        for (int j = 0; j < n; ++j) {
+            if (!lds) LTM_HIP(fill_u32(imgs[j], kNoPointBits, nb * (size_t)rows[j] * cols[j], c->stream));
+            LTM_HIP(hipMemsetAsync(smax[j], 0, nb * sizeof(uint32_t), c->stream));
+        }
+        if (lds) LTM_HIP(scan_range_images_lds(ss.d, ss.off_dev, kb, nb, geoms[0], plan, imgs, smax, with_q ? qb : nullptr, thr, c->stream));
+        else LTM_HIP(scan_range_images_multi(ss.d, ss.off_dev, kb, nb, npts, longest, geoms[0], n, rows, cols, imgs, smax, c->stream));
+    }
+    stage.hand_over();
 }
 
 // returns the finished scan range images of keyframes [kb, kb+nb) (cached or freshly computed and then cached)
@@ -71,128 +101,50 @@ static bool scan_lds_plan(const ltm_ctx* c, int n, const int* rows, const int* c
 const uint32_t* scan_images(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size_t kb, size_t nb, const Geom& g, const uint32_t** smax_out,
                             float qbound_thr = -1.0f, const float** qbound_out = nullptr)
 {
-    const size_t npx = (size_t)g.rows * g.cols;
-    auto with_qbound = [&](ScanImgEntry& e) {
-        if (qbound_thr < 0.0f || !qbound_out) return;
-        if (!e.qbound || e.q_thr != qbound_thr) {
-            if (!e.qbound) { e.qbound = reinterpret_cast<float*>(c->pool.alloc(nb * npx * sizeof(float))); e.bytes += nb * npx * sizeof(float); }
-            ProfScope p(c, "vote_scan", 0.0, (double)(nb * npx) * 8);
-            LTM_HIP(scan_qbound(e.buf, nb * npx, qbound_thr, e.qbound, c->stream));
-            e.q_thr = qbound_thr;
+    const bool want_q = qbound_thr >= 0.0f && qbound_out;
+    ScanImgEntry* e = c->scan_cache.find(ss_handle, g.rows, g.cols, kb, nb);
+    if (!e) {
+        build_scan_images(c, ss_handle, ss, kb, nb, &g, 1, want_q ? qbound_thr : -1.0f, false);
+        e = c->scan_cache.find(ss_handle, g.rows, g.cols, kb, nb);
+    }
+    if (want_q) {
+        if (!e->qbound || e->q_thr != qbound_thr) {      // none yet (the older kernels, or a build without a threshold), or one for another threshold
+            const size_t n = nb * (size_t)g.rows * g.cols;
+            if (!e->qbound) c->scan_cache.bound_image(*e, reinterpret_cast<float*>(c->pool.alloc(n * sizeof(float))), n * sizeof(float));      // the entry's from here on
+            ProfScope p(c, "vote_scan", 0.0, (double)n * 8);
+            LTM_HIP(scan_qbound(e->buf, n, qbound_thr, e->qbound, c->stream));
+            e->q_thr = qbound_thr;
         }
-        *qbound_out = e.qbound;
-    };
-    for (ScanImgEntry& e : c->scan_cache)
-        if (e.ss == ss_handle && e.rows == g.rows && e.cols == g.cols && e.kb == kb && e.nb == nb) { e.stamp = ++c->scan_cache_stamp; *smax_out = e.smax; with_qbound(e); return e.buf; }
-    const size_t bytes = nb * npx * sizeof(uint32_t);
-    size_t held = 0;
-    for (const ScanImgEntry& e : c->scan_cache) held += e.bytes;
-    while (!c->scan_cache.empty() && held + bytes > c->scan_cache_cap) {      // evict least recently used
-        size_t lru = 0;
-        for (size_t i = 1; i < c->scan_cache.size(); ++i) if (c->scan_cache[i].stamp < c->scan_cache[lru].stamp) lru = i;
-        held -= c->scan_cache[lru].bytes;
-        c->pool.free(c->scan_cache[lru].buf);
-        c->pool.free(c->scan_cache[lru].smax);
-        c->pool.free(c->scan_cache[lru].qbound);
-        c->scan_cache.erase(c->scan_cache.begin() + lru);
+        *qbound_out = e->qbound;
     }
-    uint32_t* buf = reinterpret_cast<uint32_t*>(c->pool.alloc(bytes));
-    uint32_t* smax = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * sizeof(uint32_t)));
-    const uint64_t first = ss.off[kb], npts = ss.off[kb + nb] - first;
-    uint64_t longest = 0;
-    for (size_t k = kb; k < kb + nb; ++k) longest = std::max<uint64_t>(longest, ss.off[k + 1] - ss.off[k]);
-    ScanBands plan;
-    if (scan_lds_plan(c, 1, &g.rows, &g.cols, longest, &plan)) {
-        // built in LDS and written once (k_scan_rimg_lds): no fill, and the bound image of the vote that asks comes out of the same pass
-        const bool with_q = qbound_thr >= 0.0f && qbound_out;
-        float* qb = with_q ? reinterpret_cast<float*>(c->pool.alloc(bytes)) : nullptr;
-        // algorithmic bytes as before (the scan2RangeImg, and the bound image's read and write when it is made); compulsory: points in, image out, bound image out
-        ProfScope p(c, "vote_scan", (double)npts, (double)npts * 16 + (double)(nb * npx) * (with_q ? 12 : 4), (double)npts * 16 + (double)(nb * npx) * (with_q ? 8 : 4));
-        LTM_HIP(hipMemsetAsync(smax, 0, nb * sizeof(uint32_t), c->stream));
-        LTM_HIP(scan_range_images_lds(ss.d, ss.off_dev, kb, nb, g, plan, &buf, &smax, with_q ? &qb : nullptr, qbound_thr, c->stream));
-        c->scan_cache.push_back(ScanImgEntry{ss_handle, g.rows, g.cols, kb, nb, buf, smax, bytes * (with_q ? 2 : 1), ++c->scan_cache_stamp, qb, with_q ? qbound_thr : -1.0f});
-    } else {
-        ProfScope p(c, "vote_scan", (double)npts, (double)npts * 16 + (double)(nb * npx) * 4);
-        LTM_HIP(fill_u32(buf, kNoPointBits, nb * npx, c->stream));
-        LTM_HIP(hipMemsetAsync(smax, 0, nb * sizeof(uint32_t), c->stream));
-        LTM_HIP(scan_range_images(ss.d, ss.off_dev, kb, nb, first, npts, longest, g, buf, smax, c->stream));
-        c->scan_cache.push_back(ScanImgEntry{ss_handle, g.rows, g.cols, kb, nb, buf, smax, bytes, ++c->scan_cache_stamp, nullptr, -1.0f});
-    }
-    *smax_out = smax;
-    with_qbound(c->scan_cache.back());
-    return buf;
+    *smax_out = e->smax;
+    return e->buf;
 }
 
-// the finished scan images of keyframes [kb, kb+nb) for SEVERAL shapes, the missing ones computed in one pass over the scans (k_scan_rimg_multi) and cached
+// the finished scan images of keyframes [kb, kb+nb) for SEVERAL shapes, the missing ones computed in one pass over the scans per group of kMaxScanShapes and cached
 // thr >= 0: the threshold of the votes that will use them -- on the LDS path their bound images are made in the same pass (otherwise by the first vote, as before)
 void scan_images_prepare(ltm_ctx* c, uint64_t ss_handle, const ScanSet& ss, size_t kb, size_t nb, const std::vector<Geom>& geoms, float thr)
 {
     std::vector<Geom> todo;
     for (const Geom& g : geoms) {
-        bool have = false;
-        for (ScanImgEntry& e : c->scan_cache)
-            if (e.ss == ss_handle && e.rows == g.rows && e.cols == g.cols && e.kb == kb && e.nb == nb) { e.stamp = ++c->scan_cache_stamp; have = true; }
+        bool have = c->scan_cache.find(ss_handle, g.rows, g.cols, kb, nb) != nullptr;      // (stamped: what this call asks for is the last to be evicted by it)
         for (const Geom& t : todo) have = have || (t.rows == g.rows && t.cols == g.cols);
         if (!have && g.rows > 0 && g.cols > 0) todo.push_back(g);
     }
     if (todo.empty() || !nb) return;
-    const uint64_t first = ss.off[kb], npts = ss.off[kb + nb] - first;
-    uint64_t longest = 0;
-    for (size_t k = kb; k < kb + nb; ++k) longest = std::max<uint64_t>(longest, ss.off[k + 1] - ss.off[k]);
-    bool dense = false;
-    {
-        // The one-pass kernel pays while a scan has about as many points as the smallest shape has pixels (71 x 513 at the reference's 50 degree field of view:
-        // 1.3 points per pixel for the lot's os1-64 scans; cascade vote_scan 71 -> 64 ms per step with every session on it).  With several points per pixel its six
-        // atomics per point pile up on the same few lines while the point's neighbours do the same: hdl-64e on the street, 3.0 per pixel of the whole image and twice
-        // that where the sensor's 27 degrees actually fall, 73 -> 113 ms per step (street 3-res 1057 -> 1100 ms); the re-gridded scans a cascade hands over (3.3) sit
-        // on the same side of the line and give up 5 of their 790 ms.  Above `scan_multi_max_density` (2.5) the votes compute their images one shape at a time, as
-        // before round 6 (identical images either way).  That is the global-atomic kernel's limit: k_scan_rimg_lds takes its minima in LDS and is at least as fast in one
-        // pass on those scans (vote_scan of the street step 10.34 -> 10.30 ms, of the cascade step 33.5 -> 22.2 ms), so the gate stands in front of the older kernels only.
-        size_t min_px = (size_t)todo[0].rows * todo[0].cols;
-        for (const Geom& t : todo) min_px = std::min(min_px, (size_t)t.rows * t.cols);
-        const double density = (double)(npts / std::max<size_t>(nb, 1)) / (double)std::max<size_t>(min_px, 1);
-        dense = density > c->scan_multi_max_density;
-    }
-    for (size_t at = 0; at < todo.size(); at += kMaxScanShapes) {
-        const int n = (int)std::min<size_t>(kMaxScanShapes, todo.size() - at);
-        int rows[kMaxScanShapes], cols[kMaxScanShapes];
-        uint32_t *imgs[kMaxScanShapes], *smax[kMaxScanShapes];
-        float* qb[kMaxScanShapes];
-        for (int j = 0; j < n; ++j) { rows[j] = todo[at + j].rows; cols[j] = todo[at + j].cols; }
-        ScanBands plan;
-        const bool lds = scan_lds_plan(c, n, rows, cols, longest, &plan);
-        if (dense && !lds) continue;      // left to the votes, one shape at a time
-        const bool with_q = lds && thr >= 0.0f;
-        size_t need = 0;
-        for (int j = 0; j < n; ++j) need += nb * (size_t)rows[j] * cols[j] * sizeof(uint32_t) * (with_q ? 2 : 1);
-        size_t held = 0;
-        for (const ScanImgEntry& e : c->scan_cache) held += e.bytes;
-        while (!c->scan_cache.empty() && held + need > c->scan_cache_cap) {      // evict least recently used (the shapes asked for were stamped above)
-            size_t lru = 0;
-            for (size_t i = 1; i < c->scan_cache.size(); ++i) if (c->scan_cache[i].stamp < c->scan_cache[lru].stamp) lru = i;
-            held -= c->scan_cache[lru].bytes;
-            c->pool.free(c->scan_cache[lru].buf); c->pool.free(c->scan_cache[lru].smax); c->pool.free(c->scan_cache[lru].qbound);
-            c->scan_cache.erase(c->scan_cache.begin() + lru);
-        }
-        double px_all = 0;
-        for (int j = 0; j < n; ++j) {
-            const size_t npx = (size_t)rows[j] * cols[j];
-            imgs[j] = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * npx * sizeof(uint32_t)));
-            smax[j] = reinterpret_cast<uint32_t*>(c->pool.alloc(nb * sizeof(uint32_t)));
-            qb[j] = with_q ? reinterpret_cast<float*>(c->pool.alloc(nb * npx * sizeof(float))) : nullptr;
-            c->scan_cache.push_back(ScanImgEntry{ss_handle, rows[j], cols[j], kb, nb, imgs[j], smax[j], nb * npx * sizeof(uint32_t) * (with_q ? 2 : 1), ++c->scan_cache_stamp, qb[j], with_q ? thr : -1.0f});
-            px_all += (double)(nb * npx);
-        }
-        // algorithmic bytes as SURVEY 8d counts them: every shape is one scan2RangeImg of every scan (16 B per point read, 4 B per pixel written), and a bound image
-        // is its scan image read and itself written.  Compulsory: the points once, every image written, every bound image written.
-        ProfScope p(c, "vote_scan", (double)npts * n, (double)npts * 16 * n + px_all * (with_q ? 12 : 4), (double)npts * 16 + px_all * (with_q ? 8 : 4));
-        for (int j = 0; j < n; ++j) {
-            if (!lds) LTM_HIP(fill_u32(imgs[j], kNoPointBits, nb * (size_t)rows[j] * cols[j], c->stream));
-            LTM_HIP(hipMemsetAsync(smax[j], 0, nb * sizeof(uint32_t), c->stream));
-        }
-        if (lds) LTM_HIP(scan_range_images_lds(ss.d, ss.off_dev, kb, nb, todo[at], plan, imgs, smax, with_q ? qb : nullptr, thr, c->stream));
-        else LTM_HIP(scan_range_images_multi(ss.d, ss.off_dev, kb, nb, npts, longest, todo[at], n, rows, cols, imgs, smax, c->stream));
-    }
+    // The one-pass kernel pays while a scan has about as many points as the smallest shape has pixels (71 x 513 at the reference's 50 degree field of view:
+    // 1.3 points per pixel for the lot's os1-64 scans; cascade vote_scan 71 -> 64 ms per step with every session on it).  With several points per pixel its six
+    // atomics per point pile up on the same few lines while the point's neighbours do the same: hdl-64e on the street, 3.0 per pixel of the whole image and twice
+    // that where the sensor's 27 degrees actually fall, 73 -> 113 ms per step (street 3-res 1057 -> 1100 ms); the re-gridded scans a cascade hands over (3.3) sit
+    // on the same side of the line and give up 5 of their 790 ms.  Above `scan_multi_max_density` (2.5) the votes compute their images one shape at a time, as
+    // before round 6 (identical images either way).  That is the global-atomic kernel's limit: k_scan_rimg_lds takes its minima in LDS and is at least as fast in one
+    // pass on those scans (vote_scan of the street step 10.34 -> 10.30 ms, of the cascade step 33.5 -> 22.2 ms), so the gate stands in front of the older kernels only.
+    size_t min_px = (size_t)todo[0].rows * todo[0].cols;
+    for (const Geom& t : todo) min_px = std::min(min_px, (size_t)t.rows * t.cols);
+    const uint64_t npts = ss.off[kb + nb] - ss.off[kb];
+    const bool dense = (double)(npts / std::max<size_t>(nb, 1)) / (double)std::max<size_t>(min_px, 1) > c->scan_multi_max_density;
+    for (size_t at = 0; at < todo.size(); at += kMaxScanShapes)
+        build_scan_images(c, ss_handle, ss, kb, nb, &todo[at], (int)std::min<size_t>(kMaxScanShapes, todo.size() - at), thr, dense);      // dense and no band plan: left to the votes
 }
 
 // first use of an image shape by this context: is the bounded-error projection inside its bounds for it?  (see ltm_ctx::cull_geom_ok)

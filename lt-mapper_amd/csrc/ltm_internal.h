@@ -7,6 +7,7 @@
 #include "ltm.h"
 #include "ltm_pclsort.h"
 #include "ltm_kernels.h"
+#include "ltm_scan_cache.h"
 #include "ltm_device_prims.h"      // ordered_unkey: the host reads boxes with the function the kernels wrote them with
 
 #include <hip/hip_runtime_api.h>
@@ -192,9 +193,6 @@ struct Poses { size_t n = 0; std::vector<double> pose, inv; double* pose_dev = n
 // bytes = SURVEY 8(d)'s algorithmic bytes (one map read per keyframe); bytes_c = the compulsory bytes of the launch as this design issues it (a projection
 // launch reads its map ONCE for all the keyframes of the batch): equal to `bytes` for every class but the projection kernels
 struct ProfClass { double ms = 0; uint64_t launches = 0; double units = 0, bytes = 0, bytes_c = 0; };
-// scan2RangeImg depends only on (scan set, image shape, keyframe range): the remove / revert / remove passes of one
-// resolution and the three ND / PD filter passes project the same scans again, so finished scan images are kept.
-struct ScanImgEntry { uint64_t ss; int rows, cols; size_t kb, nb; uint32_t* buf; uint32_t* smax; size_t bytes; uint64_t stamp; float* qbound; float q_thr; };
 struct Pending { int cls; hipEvent_t a, b; };
 // a vote launch whose algorithmic bytes depend on the number of (tile, keyframe) workgroups that survive the whole-tile cull:
 // counted on the device into slot `slot` of ctx->live_counts, folded into the class totals when the profile is collected
@@ -289,11 +287,9 @@ struct ltm_ctx {
     std::vector<PendingLive> pending_live;
     unsigned long long* live_counts = nullptr;   // device, kLiveSlots entries
     std::vector<hipEvent_t> event_pool;
-    double scan_multi_max_density = 2.5;        // mean scan points per pixel of the smallest shape up to which ltm_scanset_prepare_*_images uses the one-pass GLOBAL-ATOMIC kernel (scan_images_prepare; k_scan_rimg_lds is not gated); LTM_SCAN_MULTI_MAX_DENSITY
-    int scan_img_lds = 1;                       // LTM_SCAN_IMG_LDS=0: scan images by fill + global atomics + k_image_max + k_scan_qbound (the form before k_scan_rimg_lds; A/B switch and the path of shapes make_scan_bands cannot serve)
-    std::vector<ScanImgEntry> scan_cache;
-    uint64_t scan_cache_stamp = 0;
-    size_t scan_cache_cap = (size_t)3 << 30;   // bytes
+    double scan_multi_max_density = 2.5;        // mean scan points per pixel of the smallest shape up to which ltm_scanset_prepare_*_images uses the one-pass GLOBAL-ATOMIC kernel k_scan_rimg_multi (scan_images_prepare; k_scan_rimg_lds is not gated); LTM_SCAN_MULTI_MAX_DENSITY
+    int scan_img_lds = 1;                       // LTM_SCAN_IMG_LDS=0: scan images by fill + k_scan_rimg_multi (global atomics) + k_image_max + k_scan_qbound (the form before k_scan_rimg_lds; A/B switch and the path of shapes make_scan_bands cannot serve)
+    ScanCache scan_cache{[this](void* p) { pool.free(p); }};      // ltm_scan_cache.h
     int occlusion_cull = 1;                     // LTM_OCCLUSION=0: the exact-image kernel runs every (tile, keyframe) pair (A/B switch)
     size_t occlusion_min_pairs = (size_t)1 << 21;   // LTM_OCCLUSION_MIN_PAIRS: smaller launches are not worth the two extra passes (2 M pairs = 4096 tiles x 512 keyframes)
     float occlusion_r_near = 60.0f;             // LTM_OCCLUSION_RNEAR [m]: tiles nearer than this are projected first and serve as occluders
@@ -666,7 +662,6 @@ inline size_t count_flags(ltm_ctx* c, const uint8_t* flags, size_t n, DevBuf& po
     scan_flags(c, flags, n, pos);
     return scan_total_u8(c, flags, pos.as<uint32_t>(), n);
 }
-void scan_cache_drop(ltm_ctx* c, uint64_t ss_handle);                             // ltm_api_vote.cpp
 void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud* kept, ltm_cloud* flagged);   // ltm_api_vote.cpp
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
 void vgs_release_all(ltm_ctx* c);                                                 // ltm_api_voxel.cpp: open ltm_voxel_grid_scanset tickets, at ltm_destroy

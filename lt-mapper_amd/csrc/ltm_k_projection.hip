@@ -32,27 +32,10 @@ hipError_t fill_u64(uint64_t* p, uint64_t v, size_t n, hipStream_t s)
     return hipGetLastError();
 }
 
-// Removerter.cpp:109-156 scan2RangeImg, all keyframes of a batch in one launch.
-__global__ void __launch_bounds__(kBlock)
-k_scan_rimg(const float4* __restrict__ scans, const uint64_t* __restrict__ offsets, size_t kb, size_t nb,
-            uint64_t first_pt, uint64_t n_pts, Geom gg, uint32_t* __restrict__ img)
-{
-    // grid = (chunks of the longest keyframe, keyframes): the keyframe comes from blockIdx.y instead of a binary search over
-    // the offsets (nine dependent loads per point)
-    const size_t lo = kb + blockIdx.y;
-    const uint64_t a = offsets[lo], local = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (local >= offsets[lo + 1] - a) return;
-    const uint64_t gi = a + local;
-    const RimgGeom g = make_geom(gg);
-    const float4 p = scans[gi];
-    const Sph s = cart2sph(p.x, p.y, p.z);
-    const int px = pixel_index(g, s.az, s.el);
-    img_min_u32(img + (lo - kb) * (size_t)(g.rows * g.cols) + px, f2u(s.r));
-}
-
-// The same for up to kMaxScanShapes image shapes at once (round 6): the remove / revert passes of selfRemovert project every scan into six shapes
-// (2.5, 2.375, 2.0, 1.9, 1.5, 1.425 pixels per degree).  The point is read once, the exact atan2f / sqrtf chain and the two divisions by the field of
-// view (shape-independent) run once, and each shape costs a multiply, a round, a clamp and its atomic -- bit for bit pixel_row_col's arithmetic.
+// Removerter.cpp:109-156 scan2RangeImg, all keyframes of a batch and up to kMaxScanShapes image shapes in one launch: the remove / revert passes of selfRemovert
+// project every scan into six shapes (2.5, 2.375, 2.0, 1.9, 1.5, 1.425 pixels per degree).  The point is read once, the exact atan2f / sqrtf chain and the two
+// divisions by the field of view (shape-independent) run once, and each shape costs a multiply, a round, a clamp and its atomic -- bit for bit pixel_row_col's
+// arithmetic.  grid = (chunks of the longest keyframe, keyframes): the keyframe comes from blockIdx.y instead of a binary search over the offsets.
 struct ScanShapes { int n; int rows[kMaxScanShapes], cols[kMaxScanShapes]; uint32_t* img[kMaxScanShapes]; };
 // pixel_row_col's arithmetic in its shape-independent and per-shape parts: the row and column fractions of a direction, and the clamped pixel of a fraction
 __device__ __forceinline__ float scan_row_frac(const RimgGeom& g, float el)
@@ -147,22 +130,6 @@ hipError_t scan_qbound(const uint32_t* scan_img, size_t n, float thr, float* qbo
     return hipGetLastError();
 }
 
-hipError_t scan_range_images(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t first_pt,
-                             uint64_t n_pts, uint64_t max_kf_pts, Geom g, uint32_t* scan_img, uint32_t* smax_bits, hipStream_t s)
-{
-    if (n_pts && max_kf_pts)
-        for (size_t k0 = 0; k0 < nb; k0 += 65535) {       // gridDim.y limit
-            const size_t nk = std::min<size_t>(65535, nb - k0);
-            k_scan_rimg<<<dim3(grid_for(max_kf_pts), (unsigned)nk), dim3(kBlock), 0, s>>>(scans, offsets_dev, kb + k0, nk, first_pt, n_pts, g,
-                                                                                        scan_img + k0 * (size_t)(g.rows * g.cols));
-        }
-    if (smax_bits && nb) {
-        const uint32_t npx = (uint32_t)(g.rows * g.cols);
-        k_image_max<<<dim3(std::min<unsigned>(grid_for(npx, kBlock * 8), 64), (unsigned)nb), dim3(kBlock), 0, s>>>(scan_img, npx, smax_bits);
-    }
-    return hipGetLastError();
-}
-
 hipError_t scan_range_images_multi(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t n_pts, uint64_t max_kf_pts, Geom g,
                                    int n_shapes, const int* rows, const int* cols, uint32_t* const* imgs, uint32_t* const* smax_bits, hipStream_t s)
 {
@@ -200,7 +167,7 @@ hipError_t scan_range_images_multi(const float4* scans, const uint64_t* offsets_
 //     scan (ring-major scans pass whole waves, voxel-ordered ones a few lanes of each).
 //   * Workgroups b, b + 8, b + 16, ... run on the same XCD (see tile_kf_of_block): the bands of a keyframe follow each other there, so its points come from
 //     HBM once and from that XCD's L2 for the other bands.
-// The minimum of positive float bit patterns does not depend on the order, so the images are those of k_scan_rimg / k_scan_rimg_multi bit for bit.
+// The minimum of positive float bit patterns does not depend on the order, so the images are those of k_scan_rimg_multi bit for bit.
 struct ScanLdsArgs {
     int n, n_bands;
     int rows[kMaxScanShapes], cols[kMaxScanShapes];

@@ -32,16 +32,13 @@ hipError_t fill_u32(uint32_t* p, uint32_t v, size_t n, hipStream_t s);
 hipError_t fill_u64(uint64_t* p, uint64_t v, size_t n, hipStream_t s);
 
 // ---- projection / vote ----
-// scan2RangeImg for keyframes [kb, kb+nb): scan_img[(kf-kb)*npx + px] = min range bits
-// smax_bits (nb entries, zero-initialised by the caller, may be null): per keyframe the float bits of the largest scan range
-hipError_t scan_range_images(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb,
-                             uint64_t first_pt, uint64_t n_pts, uint64_t max_kf_pts, Geom g, uint32_t* scan_img, uint32_t* smax_bits, hipStream_t s);
-// squared-range bound image of the range-culled vote kernel from finished scan images (see k_scan_qbound)
-// scan2RangeImg of keyframes [kb, kb+nb) into n_shapes (<= kMaxScanShapes) image shapes of one field of view in ONE pass over the points; imgs[j] pre-filled
-// with the empty range, smax_bits[j] (nullable) zeroed.  Bit-identical to n_shapes calls of scan_range_images.
+// scan2RangeImg of keyframes [kb, kb+nb) into n_shapes (1 .. kMaxScanShapes) image shapes of one field of view in ONE pass over the points (k_scan_rimg_multi, one global
+// atomic per point and shape, then k_image_max per shape): imgs[j][(kf-kb)*npx_j + px] = min range bits, imgs[j] pre-filled with the empty range by the caller.
+// smax_bits[j] (nb entries, zeroed by the caller, nullable): per keyframe the float bits of the largest scan range.
 static constexpr int kMaxScanShapes = 8;
 hipError_t scan_range_images_multi(const float4* scans, const uint64_t* offsets_dev, size_t kb, size_t nb, uint64_t n_pts, uint64_t max_kf_pts, Geom g,
                                    int n_shapes, const int* rows, const int* cols, uint32_t* const* imgs, uint32_t* const* smax_bits, hipStream_t s);
+// squared-range bound image of the range-culled vote kernel from finished scan images (see k_scan_qbound)
 hipError_t scan_qbound(const uint32_t* scan_img, size_t n, float thr, float* qbound, hipStream_t s);
 // The same images built in LDS and written once (k_scan_rimg_lds): one workgroup per (keyframe, band).  A band is, for every shape, a contiguous range of
 // its rows -- band b of B holds rows [b rows / B, (b + 1) rows / B) -- so the bands cut every shape at (nearly) the same elevations and a point lands in
@@ -63,7 +60,7 @@ LTM_HOST_DEVICE inline int scan_band_row0(int rows, int n_bands, int b) { return
 LTM_HOST_DEVICE inline size_t scan_band_shape_words(int band_rows, int cols) { return (((size_t)band_rows * (size_t)cols + 3u) + 3u) & ~(size_t)3u; }
 size_t scan_band_bytes(const ScanBands& p, int b);
 // the plan with the fewest bands whose bytes fit `budget`; false when there is none (a single row of all shapes together is wider than the budget, more than
-// kMaxScanShapes shapes, a shape without pixels, more than kMaxScanBands bands): those take scan_range_images / scan_range_images_multi
+// kMaxScanShapes shapes, a shape without pixels, more than kMaxScanBands bands): those take scan_range_images_multi
 bool make_scan_bands(int n_shapes, const int* rows, const int* cols, size_t budget, ScanBands* out);
 // imgs[j] need no fill: every pixel is written exactly once.  smax_bits[j] zeroed by the caller.  qbounds (nullable, and each entry nullable): the bound image of
 // scan_qbound for `thr`, written in the same pass.  Every image pointer 16-byte aligned; no keyframe longer than 2^32 - 1 points.

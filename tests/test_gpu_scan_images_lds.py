@@ -170,3 +170,54 @@ def test_shape_the_plan_rejects_takes_the_older_kernels(ltm, orc):
     finally:
         for c in ctxs:
             c.close()
+
+
+def _same(got, want, what):
+    for x, y, name in zip(got, want, ("image", "maximum", "bound image")):
+        assert (x is None) == (y is None), f"{what}: {name}"
+        if x is not None:
+            assert x.shape == y.shape and (_bits(x) == _bits(y)).all(), f"{what}: {name}"
+
+
+TEN_ALPHAS = [float(np.float32(0.1 * i)) for i in range(2, 12)]      # 0.2 .. 1.1
+
+
+@pytest.mark.parametrize("thr", [0.1, -1.0])
+def test_ten_shapes_are_two_groups_of_one_prepare_call(ltm, orc, ctx_pair, scans, thr):
+    """more shapes than one pass takes (kMaxScanShapes = 8): 10 x 72 up to 55 x 396, all different, built as a group of eight and a group of two"""
+    pts, off = scans
+    shapes = [orc.rimg_size(VFOV, HFOV, a) for a in TEN_ALPHAS]
+    assert shapes == [(5 * i, 36 * i) for i in range(2, 12)]
+    assert ltm.scan_bands([s[0] for s in shapes[:9]], [s[1] for s in shapes[:9]])[0] == 0, "nine shapes are not one pass"
+    assert ltm.scan_bands([s[0] for s in shapes[:8]], [s[1] for s in shapes[:8]])[0] >= 1 and ltm.scan_bands([s[0] for s in shapes[8:]], [s[1] for s in shapes[8:]])[0] >= 1
+    _compare(orc, ctx_pair, pts, off, TEN_ALPHAS, thr)
+
+
+def test_repeated_alpha_and_two_orders_of_arrival(orc, ctx_pair, scans):
+    """what a scan set already holds is not built again and not disturbed, whichever way it got there: a prepare call for one of two shapes or a vote's lazy build
+    (without a threshold: its bound image is made at the read-back), and an alpha named twice in one list"""
+    pts, off = scans
+    fresh = _compare(orc, ctx_pair, pts, off, [2.5, 2.0], 0.1)
+    for ctx, (_, want) in zip(ctx_pair, fresh):
+        a = ctx.upload_scans(pts, off)
+        ctx.prepare_vote_images(a, [2.5], 0.1)
+        first = ctx.debug_scan_images(a, 2.5, 0.1)
+        ctx.prepare_vote_images(a, [2.5, 2.0, 2.5], 0.1)
+        b = ctx.upload_scans(pts, off)
+        lazy = ctx.debug_scan_images(b, 2.0)
+        ctx.prepare_vote_images(b, [2.5, 2.0], 0.1)
+        _same(first, want[0], "prepared alone")
+        _same(lazy, (want[1][0], want[1][1], None), "lazy, no threshold")
+        for ss, what in ((a, "prepare, then prepare"), (b, "lazy, then prepare")):
+            for i, alpha in enumerate((2.5, 2.0)):
+                _same(ctx.debug_scan_images(ss, alpha, 0.1), want[i], f"{what}: alpha {alpha}")
+
+
+def test_clear_caches_between_two_read_backs(orc, ctx_pair, scans):
+    pts, off = scans
+    fresh = _compare(orc, ctx_pair, pts, off, [2.0], 0.1, kb=1, ke=6)
+    for ctx, (ss, want) in zip(ctx_pair, fresh):
+        ctx.clear_caches()
+        _same(ctx.debug_scan_images(ss, 2.0, 0.1, 1, 6), want[0], "rebuilt after clear_caches")
+        ctx.clear_caches()
+        _same(ctx.debug_scan_images(ss, 2.0, -1.0, 1, 6), (want[0][0], want[0][1], None), "rebuilt without a threshold")
