@@ -46,11 +46,9 @@ struct KnnIndex {
             LTM_HIP(sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), Mt, bits, stemp.p, stb, c->stream));
         }
         LTM_HIP(gather_points(target.d, idx2.as<uint32_t>(), Mt, sorted, c->stream));
-        DevBuf heads(c, Mt), pos(c, Mt * 4);
-        LTM_HIP(head_flags(keys2.as<uint64_t>(), Mt, heads.as<uint8_t>(), c->stream));
-        const size_t ncell = count_flags(c, heads.as<uint8_t>(), Mt, pos);
-        DevBuf starts(c, ncell * 4);
-        LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), Mt, starts.as<uint32_t>(), c->stream));
+        const Segments cells = sorted_segments(c, keys2.as<uint64_t>(), Mt);
+        const size_t ncell = cells.count;
+        const DevBuf& starts = cells.starts;
         size_t tsize = 1024;
         while (tsize < 2 * ncell) tsize <<= 1;
         mask = (uint32_t)(tsize - 1);

@@ -1,4 +1,6 @@
 // ltm_api_voxel.cpp -- C ABI: octreeDownsampling (utility.cpp:204-219), its batch / shard / key-range forms, and the loader's pcl::VoxelGrid (Session.cpp:284-289)
+// The centroid grids are ONE pipeline: a VoxelJob per cloud, voxel_plan (frame, identity, sort layout), voxel_keys, voxel_select_shard, voxel_sort_segments,
+// voxel_centroids_of, driven by voxel_centroid_jobs for one job or many.  The two scan-set grids share their tail (scanset_centroids).
 #include "ltm_internal.h"
 
 namespace ltm_detail {
@@ -95,200 +97,202 @@ void voxel_segments(ltm_ctx* c, const uint64_t* keys2, size_t n, unsigned kshift
     LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), n, starts, c->stream));
 }
 
-// voxel centroids of pts[0..n) into a freshly pooled array; returns count
-// With n_shards > 1 only the voxels of shard `shard` are produced: the Morton key space is cut into n_shards contiguous
-// ranges holding about n/n_shards points each (cut points on a 4096-bin histogram of the key prefix, so they are a pure
-// function of the input), and the outputs of shards 0..n_shards-1 concatenated are exactly the unsharded output.
-//
-// Sort layout: when Morton bits + index bits fit one 64-bit word (always, for clouds the 32-bit index allows and octrees up
-// to depth 10-13) the pair travels packed and the radix sort is keys-only over the Morton bits; otherwise key/index pairs.
-size_t voxel_centroid_raw(ltm_ctx* c, const float4* pts, size_t n_in, float leaf, float4** out, uint32_t shard = 0, uint32_t n_shards = 1,
-                          const OctreeFrame* cached = nullptr, OctreeFrame* frame_out = nullptr, const float* box_mn = nullptr, const float* box_mx = nullptr)
+// One voxel grid: the voxel centroids of pts[0..n) into a freshly pooled array.  Every centroid entry point (single, batch, shard, box) fills in
+// the first two lines and hands its jobs to voxel_centroid_jobs; the rest is what the stages below decide and own on the way.
+struct VoxelJob {
+    VoxelJob() = default;
+    VoxelJob(const Cloud& in, float leaf_) : pts(in.d), n(in.n), leaf(leaf_) {}
+    const float4* pts = nullptr; size_t n = 0; float leaf = 0.0f;
+    bool has_cached = false; OctreeFrame cached{};        // the frame the input was gridded under, if it still carries one
+    const float* box_mn = nullptr; const float* box_mx = nullptr;      // the bounding box of a LARGER cloud this one is a part of (key-range exchange, ltm_voxel_centroid_box)
+    uint32_t shard = 0, n_shards = 1;                     // n_shards > 1: only the voxels of one key range (voxel_select_shard)
+    // the plan (voxel_plan)
+    OctreeFrame f{}; bool identity = false;
+    unsigned ib = 1, kshift = 0, mbits = 0; bool packed = false; KeyCompress kc{};
+    // on the way: keys (and point indices, unless packed) before and after the sort, the first sorted position of every voxel
+    size_t nkeys = 0;                                     // n, or what the shard selection left of it
+    std::unique_ptr<DevBuf> keys, idx, keys2, idx2, starts;
+    float4* out = nullptr; size_t nvox = 0;
+};
+
+// What a job's bounding box decides, in this order: the frame, whether the grid is the identity (`check` is word 6 of the box), and the sort layout:
+// when Morton bits + index bits fit one 64-bit word (always, for clouds the 32-bit index allows and octrees up to depth 10-13) the pair travels
+// packed and the radix sort is keys-only over the Morton bits; otherwise key/index pairs.
+void voxel_plan(ltm_ctx* c, VoxelJob& j, const float mn[3], const float mx[3], uint32_t check)
 {
-    *out = nullptr;
-    if (n_in == 0) return 0;
-    LTM_REQUIRE(leaf > 0.0f, "leaf size must be positive");
-    LTM_REQUIRE(n_in < 0xffffffffull, "cloud too large for 32-bit point indices");
-    ProfScope p(c, "voxel", (double)n_in, 64.0 * n_in);
-    ++c->voxel_calls;
-    float mn[3], mx[3];
-    bool untouched = false;
-    if (cached && c->voxel_identity && n_shards == 1) {
-        untouched = read_box(c, mn, mx, [&](uint32_t* bb) { return bbox_reduce_check(pts, n_in, *cached, bb, c->stream); }) == 0;
-    } else if (box_mn && box_mx) {      // the bounding box of a LARGER cloud this one is a part of (key-range exchange, ltm_voxel_centroid_box)
-        for (int d = 0; d < 3; ++d) { mn[d] = box_mn[d]; mx[d] = box_mx[d]; }
-    } else bbox_of(c, pts, n_in, mn, mx);
-    OctreeFrame f;
-    if (!octree_frame_from_bbox(mn, mx, leaf, &f)) throw Err{LTM_E_UNSUPPORTED, "octree depth > 21 (extent / leaf too large)"};
-    if (frame_out) *frame_out = f;
-    if (untouched && same_frame(f, *cached)) {
-        // every point alone in its voxel and already in octree order under the frame this very call would use: the grid is the identity
-        float4* o = reinterpret_cast<float4*>(c->pool.alloc(n_in * sizeof(float4)));
-        d2d(c, o, pts, n_in * sizeof(float4));
-        ++c->voxel_identity_hits;
-        *out = o;
-        return n_in;
-    }
-    unsigned ib = 1;
-    while (ib < 32 && ((size_t)1 << ib) < n_in) ++ib;
+    if (!octree_frame_from_bbox(mn, mx, j.leaf, &j.f)) throw Err{LTM_E_UNSUPPORTED, "octree depth > 21 (extent / leaf too large)"};
+    // every point alone in its voxel and already in octree order under the frame this very call would use: the grid is the identity
+    j.identity = j.has_cached && c->voxel_identity && check == 0 && same_frame(j.f, j.cached);
+    if (j.identity) return;
+    while (j.ib < 32 && ((size_t)1 << j.ib) < j.n) ++j.ib;
     // packed (code << index bits | index in one word, keys-only sort) whenever the COMPRESSED code fits beside the index: a 45 M-point
     // street map (depth 13, 26 index bits) misses 64 bits by one with the full code and fits easily without the undecidable bits
-    const KeyCompress kc = key_compress_for(mn, mx, f, c->voxel_key_compress != 0);
-    const bool packed = kc.bits + ib <= 64;
-    const unsigned mbits = packed ? kc.bits : 3 * f.depth;        // code bits the sort has to look at
-    const unsigned kshift = packed ? ib : 0;                       // Morton code = key >> kshift
-    size_t n = n_in;
-    DevBuf keys(c, n * 8), idx(c, packed ? 8 : n * 4);
-    if (packed) LTM_HIP(morton_keys_packed(pts, n, f, kc, ib, keys.as<uint64_t>(), c->stream));
-    else LTM_HIP(morton_keys(pts, n, f, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
-    if (n_shards > 1) {
-        const unsigned shift = mbits > 12 ? mbits - 12 : 0;
-        std::vector<uint32_t> hist(kVoxelKeyBins);
-        {
-            DevBuf hd(c, kVoxelKeyBins * sizeof(uint32_t));
-            LTM_HIP(key_histogram(keys.as<uint64_t>(), n, shift + kshift, hd.as<uint32_t>(), c->stream));
-            d2h(c, hist.data(), hd.p, kVoxelKeyBins * sizeof(uint32_t));
-        }
-        // cut b (1..n_shards-1) = first bin whose preceding count reaches b*n/n_shards
-        auto cut = [&](uint32_t b) -> uint64_t {
-            if (b == 0) return 0;
-            if (b >= n_shards) return kVoxelKeyBins;
-            const uint64_t want = (uint64_t)n * b / n_shards;
-            uint64_t cum = 0;
-            for (uint64_t s = 0; s < (uint64_t)kVoxelKeyBins; ++s) {
-                if (cum >= want) return s;
-                cum += hist[s];
-            }
-            return kVoxelKeyBins;
-        };
-        auto bound = [&](uint64_t bin) { return bin >= (uint64_t)kVoxelKeyBins ? ~0ull : bin << (shift + kshift); };
-        const uint64_t lo = bound(cut(shard));
-        const uint64_t hi = (shard + 1 >= n_shards) ? ~0ull : bound(cut(shard + 1));
-        DevBuf flags(c, n), pos(c, n * 4);
-        LTM_HIP(key_range_flags(keys.as<uint64_t>(), n, lo, hi, flags.as<uint8_t>(), c->stream));
-        const size_t nsel = count_flags(c, flags.as<uint8_t>(), n, pos);
-        if (nsel == 0) return 0;
-        DevBuf ck(c, nsel * 8), ci(c, packed ? 8 : nsel * 4);
-        if (packed) LTM_HIP(compact_keys(keys.as<uint64_t>(), flags.as<uint8_t>(), pos.as<uint32_t>(), n, ck.as<uint64_t>(), c->stream));
-        else LTM_HIP(compact_pairs(keys.as<uint64_t>(), idx.as<uint32_t>(), flags.as<uint8_t>(), pos.as<uint32_t>(), n,
-                                   ck.as<uint64_t>(), ci.as<uint32_t>(), c->stream));
-        std::swap(keys.p, ck.p); std::swap(idx.p, ci.p);
-        n = nsel;
+    j.kc = key_compress_for(mn, mx, j.f, c->voxel_key_compress != 0);
+    j.packed = j.kc.bits + j.ib <= 64;
+    j.mbits = j.packed ? j.kc.bits : 3 * j.f.depth;        // code bits the sort has to look at
+    j.kshift = j.packed ? j.ib : 0;                         // Morton code = key >> kshift
+}
+
+void voxel_keys(ltm_ctx* c, VoxelJob& j)
+{
+    j.nkeys = j.n;
+    j.keys.reset(new DevBuf(c, j.n * 8)); j.idx.reset(new DevBuf(c, j.packed ? 8 : j.n * 4));
+    if (j.packed) LTM_HIP(morton_keys_packed(j.pts, j.n, j.f, j.kc, j.ib, j.keys->as<uint64_t>(), c->stream));
+    else LTM_HIP(morton_keys(j.pts, j.n, j.f, j.keys->as<uint64_t>(), j.idx->as<uint32_t>(), c->stream));
+}
+
+// Keeps only the keys of shard j.shard: the Morton key space is cut into n_shards contiguous ranges holding about n/n_shards points each (cut points
+// on a 4096-bin histogram of the key prefix, so they are a pure function of the input), and the outputs of shards 0..n_shards-1 concatenated are
+// exactly the unsharded output.  Two host round trips (histogram, selected count); only the ABI's one-job ltm_voxel_centroid_shard ever asks for it.
+void voxel_select_shard(ltm_ctx* c, VoxelJob& j)
+{
+    const size_t n = j.n;
+    const uint32_t shard = j.shard, n_shards = j.n_shards;
+    const unsigned shift = (j.mbits > 12 ? j.mbits - 12 : 0) + j.kshift;
+    std::vector<uint32_t> hist(kVoxelKeyBins);
+    {
+        DevBuf hd(c, kVoxelKeyBins * sizeof(uint32_t));
+        LTM_HIP(key_histogram(j.keys->as<uint64_t>(), n, shift, hd.as<uint32_t>(), c->stream));
+        d2h(c, hist.data(), hd.p, kVoxelKeyBins * sizeof(uint32_t));
     }
-    DevBuf keys2(c, n * 8), idx2(c, packed ? 8 : n * 4);
-    if (packed) {
+    // cut b (1..n_shards-1) = first bin whose preceding count reaches b*n/n_shards
+    auto cut = [&](uint32_t b) -> uint64_t {
+        if (b == 0) return 0;
+        if (b >= n_shards) return kVoxelKeyBins;
+        const uint64_t want = (uint64_t)n * b / n_shards;
+        uint64_t cum = 0;
+        for (uint64_t s = 0; s < (uint64_t)kVoxelKeyBins; ++s) {
+            if (cum >= want) return s;
+            cum += hist[s];
+        }
+        return kVoxelKeyBins;
+    };
+    auto bound = [&](uint64_t bin) { return bin >= (uint64_t)kVoxelKeyBins ? ~0ull : bin << shift; };
+    const uint64_t lo = bound(cut(shard));
+    const uint64_t hi = (shard + 1 >= n_shards) ? ~0ull : bound(cut(shard + 1));
+    DevBuf flags(c, n), pos(c, n * 4);
+    LTM_HIP(key_range_flags(j.keys->as<uint64_t>(), n, lo, hi, flags.as<uint8_t>(), c->stream));
+    j.nkeys = count_flags(c, flags.as<uint8_t>(), n, pos);
+    if (j.nkeys == 0) return;
+    std::unique_ptr<DevBuf> ck(new DevBuf(c, j.nkeys * 8)), ci(new DevBuf(c, j.packed ? 8 : j.nkeys * 4));
+    if (j.packed) LTM_HIP(compact_keys(j.keys->as<uint64_t>(), flags.as<uint8_t>(), pos.as<uint32_t>(), n, ck->as<uint64_t>(), c->stream));
+    else LTM_HIP(compact_pairs(j.keys->as<uint64_t>(), j.idx->as<uint32_t>(), flags.as<uint8_t>(), pos.as<uint32_t>(), n,
+                               ck->as<uint64_t>(), ci->as<uint32_t>(), c->stream));
+    j.keys = std::move(ck); j.idx = std::move(ci);
+}
+
+// sort, then head flags + scan + segment starts; the voxel count goes to *count_dev
+void voxel_sort_segments(ltm_ctx* c, VoxelJob& j, uint32_t* count_dev)
+{
+    const size_t n = j.nkeys;
+    j.keys2.reset(new DevBuf(c, n * 8)); j.idx2.reset(new DevBuf(c, j.packed ? 8 : n * 4));
+    if (j.packed) {
         const size_t stb = sort_keys_temp_bytes(n);
         DevBuf stemp(c, stb);
-        LTM_HIP(sort_keys_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), n, ib, ib + mbits, stemp.p, stb, c->stream));
+        LTM_HIP(sort_keys_u64(j.keys->as<uint64_t>(), j.keys2->as<uint64_t>(), n, j.ib, j.ib + j.mbits, stemp.p, stb, c->stream));
     } else {
         const size_t stb = sort_temp_bytes(n);
         DevBuf stemp(c, stb);
-        LTM_HIP(sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), n, mbits, stemp.p, stb, c->stream));
+        LTM_HIP(sort_pairs_u64(j.keys->as<uint64_t>(), j.keys2->as<uint64_t>(), j.idx->as<uint32_t>(), j.idx2->as<uint32_t>(), n, j.mbits, stemp.p, stb, c->stream));
     }
-    DevBuf starts(c, n * 4), cnt(c, 4);
-    voxel_segments(c, keys2.as<uint64_t>(), n, kshift, starts.as<uint32_t>(), cnt.as<uint32_t>());
-    uint32_t nvox32 = 0;
-    d2h(c, &nvox32, cnt.p, 4);
-    const size_t nvox = nvox32;
-    float4* o = reinterpret_cast<float4*>(c->pool.alloc(nvox * sizeof(float4)));
-    if (packed) LTM_HIP(voxel_centroids_packed(pts, keys2.as<uint64_t>(), ((uint64_t)1 << ib) - 1, starts.as<uint32_t>(), nvox, n, o, c->stream));
-    else LTM_HIP(voxel_centroids(pts, idx2.as<uint32_t>(), starts.as<uint32_t>(), nvox, n, o, c->stream));
-    *out = o;
-    return nvox;
+    j.keys.reset(); j.idx.reset();      // stream-ordered pool: reusable by the next job's buffers
+    j.starts.reset(new DevBuf(c, n * 4));
+    voxel_segments(c, j.keys2->as<uint64_t>(), n, j.kshift, j.starts->as<uint32_t>(), count_dev);
 }
 
-// Several independent voxel grids as one batch: the stages of every cloud are enqueued phase by phase and the host reads all bounding
-// boxes in ONE copy and all voxel counts in ONE copy -- two host round trips (~70 us of idle GPU each) for the whole batch instead
-// of two per cloud.  Results are exactly those of voxel_centroid_raw (same kernels, same order inside each cloud).
-struct VoxelJob {
-    const float4* pts; size_t n; float leaf;
-    OctreeFrame f; unsigned ib = 1, kshift = 0, mbits = 0; bool packed = false;
-    std::unique_ptr<DevBuf> keys, idx, keys2, idx2, starts;
-    float4* out = nullptr; size_t nvox = 0;
-    bool has_cached = false; OctreeFrame cached{};        // the frame the input was gridded under, if it still carries one
-    bool identity = false;                                 // decided after the bounding-box round trip: output = copy of the input
-};
-void voxel_centroid_batch_impl(ltm_ctx* c, std::vector<VoxelJob>& jobs);
-void voxel_centroid_batch(ltm_ctx* c, std::vector<VoxelJob>& jobs)
+void voxel_centroids_of(ltm_ctx* c, VoxelJob& j)      // j.nvox is known
 {
-    try { voxel_centroid_batch_impl(c, jobs); }
-    catch (...) {      // outputs already allocated for earlier jobs go back to the pool (the scratch buffers are RAII)
-        for (VoxelJob& j : jobs) { if (j.out) c->pool.free(j.out); j.out = nullptr; j.nvox = 0; }
+    j.out = reinterpret_cast<float4*>(c->pool.alloc(j.nvox * sizeof(float4)));
+    if (j.packed) LTM_HIP(voxel_centroids_packed(j.pts, j.keys2->as<uint64_t>(), ((uint64_t)1 << j.ib) - 1, j.starts->as<uint32_t>(), j.nvox, j.nkeys, j.out, c->stream));
+    else LTM_HIP(voxel_centroids(j.pts, j.idx2->as<uint32_t>(), j.starts->as<uint32_t>(), j.nvox, j.nkeys, j.out, c->stream));
+    j.keys2.reset(); j.idx2.reset(); j.starts.reset();
+}
+
+// The one driver of every centroid entry point.  The stages of every job are enqueued phase by phase and the host reads all bounding boxes in ONE
+// copy and all voxel counts in ONE copy -- two host round trips (~70 us of idle GPU each) for the whole batch instead of two per cloud.  A copy
+// nobody needs is not made: no box copy when every box was given, no counts copy when no job was sorted (identity hits, empty clouds and shards).
+void voxel_centroid_jobs(ltm_ctx* c, VoxelJob* jobs, size_t nj)
+{
+    if (nj == 0) return;
+    double tot_pts = 0;
+    for (size_t k = 0; k < nj; ++k) {
+        LTM_REQUIRE(jobs[k].leaf > 0.0f || jobs[k].n == 0, "leaf size must be positive");
+        LTM_REQUIRE(jobs[k].n < 0xffffffffull, "cloud too large for 32-bit point indices");
+        tot_pts += (double)jobs[k].n;
+    }
+    ProfScope p(c, "voxel", tot_pts, 64.0 * tot_pts);
+    try {
+        // bounding boxes, one round trip
+        DevBuf bb(c, nj * 8 * sizeof(uint32_t));
+        std::vector<uint32_t> enc(nj * 8);
+        bool reduced = false;
+        for (size_t k = 0; k < nj; ++k) {
+            const VoxelJob& j = jobs[k];
+            if (j.box_mn) continue;
+            reduced = true;
+            LTM_HIP(bbox_init(bb.as<uint32_t>() + 8 * k, c->stream));
+            if (j.has_cached && c->voxel_identity) LTM_HIP(bbox_reduce_check(j.pts, j.n, j.cached, bb.as<uint32_t>() + 8 * k, c->stream));
+            else LTM_HIP(bbox_reduce(j.pts, j.n, bb.as<uint32_t>() + 8 * k, c->stream));
+        }
+        if (reduced) d2h(c, enc.data(), bb.p, enc.size() * 4);
+        // plan, keys, sort, segments; the counts go to one small device array
+        DevBuf counts(c, nj * 4);
+        std::vector<uint32_t> nv(nj);
+        bool sorted = false;
+        for (size_t k = 0; k < nj; ++k) {
+            VoxelJob& j = jobs[k];
+            if (j.n == 0) continue;
+            ++c->voxel_calls;
+            float mn[3], mx[3];
+            if (!j.box_mn) decode_box(&enc[8 * k], mn, mx);
+            voxel_plan(c, j, j.box_mn ? j.box_mn : mn, j.box_mn ? j.box_mx : mx, enc[8 * k + 6]);
+            if (j.identity) {
+                j.out = reinterpret_cast<float4*>(c->pool.alloc(j.n * sizeof(float4)));
+                d2d(c, j.out, j.pts, j.n * sizeof(float4));
+                j.nvox = j.n;
+                ++c->voxel_identity_hits;
+                continue;
+            }
+            voxel_keys(c, j);
+            if (j.n_shards > 1) voxel_select_shard(c, j);
+            if (j.nkeys == 0) continue;      // an empty shard
+            voxel_sort_segments(c, j, counts.as<uint32_t>() + k);
+            sorted = true;
+        }
+        if (sorted) d2h(c, nv.data(), counts.p, nj * 4);
+        // centroids
+        for (size_t k = 0; k < nj; ++k) if (jobs[k].starts) { jobs[k].nvox = nv[k]; voxel_centroids_of(c, jobs[k]); }
+    } catch (...) {      // outputs already allocated for earlier jobs go back to the pool (the scratch buffers are RAII)
+        for (size_t k = 0; k < nj; ++k) { if (jobs[k].out) c->pool.free(jobs[k].out); jobs[k].out = nullptr; jobs[k].nvox = 0; }
         throw;
     }
 }
-void voxel_centroid_batch_impl(ltm_ctx* c, std::vector<VoxelJob>& jobs)
+
+// The output handle of a job the driver is done with (an empty result still owns one point); with_frame: the cloud remembers the frame it was gridded under
+ltm_cloud voxel_output(ltm_ctx* c, VoxelJob& j, bool with_frame)
 {
-    const size_t nj = jobs.size();
-    if (nj == 0) return;
-    double tot_pts = 0;
-    for (VoxelJob& j : jobs) {
-        LTM_REQUIRE(j.leaf > 0.0f || j.n == 0, "leaf size must be positive");
-        LTM_REQUIRE(j.n < 0xffffffffull, "cloud too large for 32-bit point indices");
-        tot_pts += (double)j.n;
-    }
-    ProfScope p(c, "voxel", tot_pts, 64.0 * tot_pts);
-    // phase A: bounding boxes, one round trip
-    DevBuf bb(c, nj * 8 * sizeof(uint32_t));
-    for (size_t k = 0; k < nj; ++k) {
-        LTM_HIP(bbox_init(bb.as<uint32_t>() + 8 * k, c->stream));
-        if (jobs[k].has_cached && c->voxel_identity) LTM_HIP(bbox_reduce_check(jobs[k].pts, jobs[k].n, jobs[k].cached, bb.as<uint32_t>() + 8 * k, c->stream));
-        else LTM_HIP(bbox_reduce(jobs[k].pts, jobs[k].n, bb.as<uint32_t>() + 8 * k, c->stream));
-    }
-    std::vector<uint32_t> enc(nj * 8);
-    d2h(c, enc.data(), bb.p, enc.size() * 4);
-    // phase B: keys, sort, head flags, scan; the counts go to one small device array
-    DevBuf counts(c, nj * 4);
-    for (size_t k = 0; k < nj; ++k) {
-        VoxelJob& j = jobs[k];
-        if (j.n == 0) { LTM_HIP(hipMemsetAsync(counts.as<uint32_t>() + k, 0, 4, c->stream)); continue; }
-        ++c->voxel_calls;
-        float mn[3], mx[3];
-        decode_box(&enc[8 * k], mn, mx);
-        if (!octree_frame_from_bbox(mn, mx, j.leaf, &j.f)) throw Err{LTM_E_UNSUPPORTED, "octree depth > 21 (extent / leaf too large)"};
-        if (j.has_cached && c->voxel_identity && enc[8 * k + 6] == 0 && same_frame(j.f, j.cached)) {      // see voxel_centroid_raw
-            j.identity = true;
-            j.out = reinterpret_cast<float4*>(c->pool.alloc(j.n * sizeof(float4)));
-            d2d(c, j.out, j.pts, j.n * sizeof(float4));
-            LTM_HIP(fill_u32(counts.as<uint32_t>() + k, (uint32_t)j.n, 1, c->stream));
-            ++c->voxel_identity_hits;
-            continue;
-        }
-        while (j.ib < 32 && ((size_t)1 << j.ib) < j.n) ++j.ib;
-        const KeyCompress kc = key_compress_for(mn, mx, j.f, c->voxel_key_compress != 0);
-        j.packed = kc.bits + j.ib <= 64;
-        j.mbits = j.packed ? kc.bits : 3 * j.f.depth;
-        j.kshift = j.packed ? j.ib : 0;
-        const size_t n = j.n;
-        j.keys.reset(new DevBuf(c, n * 8)); j.idx.reset(new DevBuf(c, j.packed ? 8 : n * 4));
-        j.keys2.reset(new DevBuf(c, n * 8)); j.idx2.reset(new DevBuf(c, j.packed ? 8 : n * 4));
-        if (j.packed) {
-            LTM_HIP(morton_keys_packed(j.pts, n, j.f, kc, j.ib, j.keys->as<uint64_t>(), c->stream));
-            const size_t stb = sort_keys_temp_bytes(n);
-            DevBuf stemp(c, stb);
-            LTM_HIP(sort_keys_u64(j.keys->as<uint64_t>(), j.keys2->as<uint64_t>(), n, j.ib, j.ib + j.mbits, stemp.p, stb, c->stream));
-        } else {
-            LTM_HIP(morton_keys(j.pts, n, j.f, j.keys->as<uint64_t>(), j.idx->as<uint32_t>(), c->stream));
-            const size_t stb = sort_temp_bytes(n);
-            DevBuf stemp(c, stb);
-            LTM_HIP(sort_pairs_u64(j.keys->as<uint64_t>(), j.keys2->as<uint64_t>(), j.idx->as<uint32_t>(), j.idx2->as<uint32_t>(), n, j.mbits, stemp.p, stb, c->stream));
-        }
-        j.keys.reset(); j.idx.reset();      // stream-ordered pool: reusable by the next job's buffers
-        j.starts.reset(new DevBuf(c, n * 4));
-        voxel_segments(c, j.keys2->as<uint64_t>(), n, j.kshift, j.starts->as<uint32_t>(), counts.as<uint32_t>() + k);
-    }
-    std::vector<uint32_t> nv(nj);
-    d2h(c, nv.data(), counts.p, nj * 4);
-    // phase C: centroids
-    for (size_t k = 0; k < nj; ++k) {
-        VoxelJob& j = jobs[k];
-        j.nvox = nv[k];
-        if (j.n == 0 || j.identity) continue;
-        j.out = reinterpret_cast<float4*>(c->pool.alloc(j.nvox * sizeof(float4)));
-        if (j.packed) LTM_HIP(voxel_centroids_packed(j.pts, j.keys2->as<uint64_t>(), ((uint64_t)1 << j.ib) - 1, j.starts->as<uint32_t>(), j.nvox, j.n, j.out, c->stream));
-        else LTM_HIP(voxel_centroids(j.pts, j.idx2->as<uint32_t>(), j.starts->as<uint32_t>(), j.nvox, j.n, j.out, c->stream));
-        j.keys2.reset(); j.idx2.reset(); j.starts.reset();
-    }
+    float4* d = j.out ? j.out : reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
+    const ltm_cloud h = new_cloud(c, d, j.nvox);
+    j.out = nullptr;
+    if (with_frame && j.n) set_frame(c, h, j.f, j.leaf, true);
+    return h;
+}
+
+// The tail of both scan-set grids, from the sorted keys (n > 0) to the output scan set: segments, the per-keyframe bounds in one copy down, centroids.
+// The keys lead with the keyframe id (and the host order works keyframe by keyframe), so keyframe k still occupies sorted positions [off[k], off[k+1]).
+// grid: the frames of ltm_voxel_grid_scanset (voxelgrid_centroids); null: the octree grid (voxel_centroids)
+ltm_scanset scanset_centroids(ltm_ctx* c, const ScanSet& s, const uint64_t* keys2, const uint32_t* idx2, const VoxelGridFrame* grid)
+{
+    const size_t nk = s.nkf(), n = s.n_pts;
+    const Segments seg = sorted_segments(c, keys2, n);
+    DevBuf bout(c, (nk + 1) * 4);
+    LTM_HIP(gather_u32(seg.pos.as<uint32_t>(), s.off_dev, nk + 1, n, (uint32_t)seg.count, bout.as<uint32_t>(), c->stream));
+    std::vector<uint32_t> b(nk + 1);
+    d2h(c, b.data(), bout.p, (nk + 1) * 4);
+    float4* o = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(seg.count, 1) * sizeof(float4)));
+    if (grid) LTM_HIP(voxelgrid_centroids(s.d, keys2, idx2, seg.starts.as<uint32_t>(), grid, seg.count, n, o, c->stream));
+    else LTM_HIP(voxel_centroids(s.d, idx2, seg.starts.as<uint32_t>(), seg.count, n, o, c->stream));
+    return new_scanset(c, o, std::vector<uint64_t>(b.begin(), b.end()));
 }
 
 
@@ -302,13 +306,10 @@ int ltm_voxel_centroid(ltm_ctx* c, ltm_cloud hin, float leaf, ltm_cloud* out)
     return guarded(c, [&] {
         LTM_REQUIRE(out, "null argument");
         const Cloud in = get_cloud(c, hin);
-        float4* d = nullptr;
-        OctreeFrame f{};
-        const bool have = in.vf_ok && in.vleaf == leaf;
-        const size_t nv = voxel_centroid_raw(c, in.d, in.n, leaf, &d, 0, 1, have ? &in.vf : nullptr, &f);
-        if (!d) d = reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
-        *out = new_cloud(c, d, nv);
-        if (in.n) set_frame(c, *out, f, leaf, true);
+        VoxelJob j(in, leaf);
+        j.has_cached = in.vf_ok && in.vleaf == leaf; j.cached = in.vf;
+        if (in.n) voxel_centroid_jobs(c, &j, 1);
+        *out = voxel_output(c, j, true);
     });
 }
 
@@ -318,20 +319,14 @@ int ltm_voxel_centroid_batch(ltm_ctx* c, size_t n, const ltm_cloud* in, const fl
         LTM_REQUIRE((in && leaf && out) || n == 0, "null argument");
         std::vector<VoxelJob> jobs(n);
         for (size_t k = 0; k < n; ++k) {
-            const Cloud cl = get_cloud(c, in[k]);
-            jobs[k].pts = cl.d; jobs[k].n = cl.n; jobs[k].leaf = leaf[k];
-            jobs[k].has_cached = cl.vf_ok && cl.vleaf == leaf[k] && cl.n > 0;
-            jobs[k].cached = cl.vf;
+            const Cloud& cl = get_cloud(c, in[k]);
+            jobs[k] = VoxelJob(cl, leaf[k]);
+            jobs[k].has_cached = cl.vf_ok && cl.vleaf == leaf[k] && cl.n > 0; jobs[k].cached = cl.vf;
         }
-        voxel_centroid_batch(c, jobs);
+        voxel_centroid_jobs(c, jobs.data(), n);
         size_t done = 0;
         try {
-            for (; done < n; ++done) {
-                float4* d = jobs[done].out ? jobs[done].out : reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
-                jobs[done].out = nullptr;
-                out[done] = new_cloud(c, d, jobs[done].nvox);
-                if (jobs[done].n) set_frame(c, out[done], jobs[done].f, jobs[done].leaf, true);
-            }
+            for (; done < n; ++done) out[done] = voxel_output(c, jobs[done], true);
         } catch (...) {      // handles made so far stay valid for the caller to free; the rest of the outputs go back to the pool
             for (size_t k = done; k < n; ++k) if (jobs[k].out) c->pool.free(jobs[k].out);
             throw;
@@ -345,10 +340,10 @@ int ltm_voxel_centroid_shard(ltm_ctx* c, ltm_cloud hin, float leaf, uint32_t sha
         LTM_REQUIRE(out, "null argument");
         LTM_REQUIRE(n_shards >= 1 && n_shards <= 4096 && shard < n_shards, "shard index out of range");
         const Cloud in = get_cloud(c, hin);
-        float4* d = nullptr;
-        const size_t nv = voxel_centroid_raw(c, in.d, in.n, leaf, &d, shard, n_shards);
-        if (!d) d = reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
-        *out = new_cloud(c, d, nv);
+        VoxelJob j(in, leaf);
+        j.shard = shard; j.n_shards = n_shards;
+        if (in.n) voxel_centroid_jobs(c, &j, 1);
+        *out = voxel_output(c, j, false);
     });
 }
 
@@ -448,8 +443,6 @@ int ltm_voxel_key_split(ltm_ctx* c, ltm_cloud hin, const float* mn, const float*
             const uint64_t hi = cut_bins[r + 1] >= (uint32_t)kVoxelKeyBins ? ~0ull : (uint64_t)cut_bins[r + 1] << shift;
             if (cut_bins[r] == cut_bins[r + 1]) { float4* d; parts[r] = alloc_cloud(c, 0, &d); continue; }
             LTM_HIP(key_range_flags(keys.as<uint64_t>(), in.n, lo, hi, flags.as<uint8_t>(), c->stream));
-            ltm_cloud rest_unused = 0;
-            (void)rest_unused;
             do_partition(c, in, flags.as<uint8_t>(), nullptr, &parts[r]);
             c->clouds[parts[r]].vf_ok = false;         // a part of a merged cloud was never gridded
         }
@@ -461,14 +454,13 @@ int ltm_voxel_centroid_box(ltm_ctx* c, ltm_cloud hin, const float* mn, const flo
     return guarded(c, [&] {
         LTM_REQUIRE(out, "null argument");
         const Cloud in = get_cloud(c, hin);
-        float4* d = nullptr;
-        size_t nv = 0;
+        VoxelJob j(in, leaf);
+        j.box_mn = mn; j.box_mx = mx;
         if (in.n) {
             box_check(mn, mx);
-            nv = voxel_centroid_raw(c, in.d, in.n, leaf, &d, 0, 1, nullptr, nullptr, mn, mx);
+            voxel_centroid_jobs(c, &j, 1);
         }
-        if (!d) d = reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
-        *out = new_cloud(c, d, nv);
+        *out = voxel_output(c, j, false);
     });
 }
 
@@ -481,9 +473,8 @@ int ltm_voxel_centroid_scanset(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_scan
         const size_t nk = s.nkf();
         const size_t n = s.n_pts;
         LTM_REQUIRE(n < 0xffffffffull, "scan set too large for 32-bit point indices");
-        std::vector<uint64_t> off(nk + 1, 0);
         if (n == 0 || nk == 0) {
-            *out = new_scanset(c, reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4))), std::move(off));
+            *out = new_scanset(c, reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4))), std::vector<uint64_t>(nk + 1, 0));
             return;
         }
         ProfScope ps(c, "voxel_scanset", (double)n, 64.0 * n);
@@ -515,20 +506,7 @@ int ltm_voxel_centroid_scanset(ltm_ctx* c, ltm_scanset hin, float leaf, ltm_scan
             DevBuf stemp(c, stb);
             LTM_HIP(sort_pairs_u64(keys.as<uint64_t>(), keys2.as<uint64_t>(), idx.as<uint32_t>(), idx2.as<uint32_t>(), n, shift + kf_bits, stemp.p, stb, c->stream));
         }
-        DevBuf heads(c, n), pos(c, n * 4);
-        LTM_HIP(head_flags(keys2.as<uint64_t>(), n, heads.as<uint8_t>(), c->stream));
-        const size_t nvox = count_flags(c, heads.as<uint8_t>(), n, pos);
-        // the sort key leads with the keyframe id, so keyframe k still occupies sorted positions [off[k], off[k+1])
-        DevBuf bout(c, (nk + 1) * 4);
-        LTM_HIP(gather_u32(pos.as<uint32_t>(), s.off_dev, nk + 1, n, (uint32_t)nvox, bout.as<uint32_t>(), c->stream));
-        std::vector<uint32_t> b(nk + 1);
-        d2h(c, b.data(), bout.p, (nk + 1) * 4);
-        for (size_t k = 0; k <= nk; ++k) off[k] = b[k];
-        DevBuf starts(c, nvox * 4);
-        LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), n, starts.as<uint32_t>(), c->stream));
-        float4* o = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(nvox, 1) * sizeof(float4)));
-        LTM_HIP(voxel_centroids(s.d, idx2.as<uint32_t>(), starts.as<uint32_t>(), nvox, n, o, c->stream));
-        *out = new_scanset(c, o, std::move(off));
+        *out = scanset_centroids(c, s, keys2.as<uint64_t>(), idx2.as<uint32_t>(), nullptr);
     });
 }
 
@@ -686,8 +664,7 @@ void vgs_end(ltm_ctx* c, ltm_vgs* v, ltm_scanset* out)
 {
     LTM_REQUIRE(out, "null argument");
     const size_t nk = v->nk, n = v->n;
-    std::vector<uint64_t> off(nk + 1, 0);
-    if (v->trivial) { *out = new_scanset(c, reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4))), std::move(off)); return; }
+    if (v->trivial) { *out = new_scanset(c, reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4))), std::vector<uint64_t>(nk + 1, 0)); return; }
     const ScanSet& s = get_ss(c, v->in);
     LTM_REQUIRE(s.nkf() == nk && s.n_pts == n, "the scan set changed between begin and end");
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -710,20 +687,7 @@ void vgs_end(ltm_ctx* c, ltm_vgs* v, ltm_scanset* out)
         DevBuf stemp(c, stb);
         LTM_HIP(sort_pairs_u64(v->keys->as<uint64_t>(), keys2.as<uint64_t>(), v->idx->as<uint32_t>(), idx2.as<uint32_t>(), n, 32 + v->kf_bits, stemp.p, stb, c->stream));
     }
-    DevBuf heads(c, n), pos(c, n * 4);
-    LTM_HIP(head_flags(keys2.as<uint64_t>(), n, heads.as<uint8_t>(), c->stream));
-    const size_t nvox = count_flags(c, heads.as<uint8_t>(), n, pos);
-    // the keys lead with the keyframe id (and the host order works keyframe by keyframe), so keyframe k still occupies positions [off[k], off[k+1])
-    DevBuf bout(c, (nk + 1) * 4);
-    LTM_HIP(gather_u32(pos.as<uint32_t>(), s.off_dev, nk + 1, n, (uint32_t)nvox, bout.as<uint32_t>(), c->stream));
-    std::vector<uint32_t> b(nk + 1);
-    d2h(c, b.data(), bout.p, (nk + 1) * 4);
-    for (size_t k = 0; k <= nk; ++k) off[k] = b[k];
-    DevBuf starts(c, nvox * 4);
-    LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), n, starts.as<uint32_t>(), c->stream));
-    float4* o = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(nvox, 1) * sizeof(float4)));
-    LTM_HIP(voxelgrid_centroids(s.d, keys2.as<uint64_t>(), idx2.as<uint32_t>(), starts.as<uint32_t>(), v->fdev->as<VoxelGridFrame>(), nvox, n, o, c->stream));
-    *out = new_scanset(c, o, std::move(off));
+    *out = scanset_centroids(c, s, keys2.as<uint64_t>(), idx2.as<uint32_t>(), v->fdev->as<VoxelGridFrame>());
 }
 } // namespace
 

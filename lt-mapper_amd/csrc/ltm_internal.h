@@ -335,6 +335,7 @@ struct DevBuf {   // RAII pooled scratch
     ltm_ctx* c; void* p;
     DevBuf(ltm_ctx* c_, size_t bytes) : c(c_), p(c_->pool.alloc(bytes)) {}
     ~DevBuf() { c->pool.free(p); }
+    DevBuf(DevBuf&& o) : c(o.c), p(o.p) { o.p = nullptr; }
     DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
@@ -661,6 +662,18 @@ inline size_t count_flags(ltm_ctx* c, const uint8_t* flags, size_t n, DevBuf& po
 {
     scan_flags(c, flags, n, pos);
     return scan_total_u8(c, flags, pos.as<uint32_t>(), n);
+}
+// The segments (runs of equal keys) of a sorted key array, n > 0: head flags, scan, the count read by the host (one round trip), segment starts.
+// pos[i] = number of segments that begin before i; starts has one entry per segment.
+struct Segments { DevBuf pos, starts; size_t count; };
+inline Segments sorted_segments(ltm_ctx* c, const uint64_t* keys, size_t n)
+{
+    DevBuf heads(c, n), pos(c, n * 4);
+    LTM_HIP(head_flags(keys, n, heads.as<uint8_t>(), c->stream));
+    const size_t count = count_flags(c, heads.as<uint8_t>(), n, pos);
+    DevBuf starts(c, count * 4);
+    LTM_HIP(segment_starts(heads.as<uint8_t>(), pos.as<uint32_t>(), n, starts.as<uint32_t>(), c->stream));
+    return Segments{std::move(pos), std::move(starts), count};
 }
 void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud* kept, ltm_cloud* flagged);   // ltm_api_vote.cpp
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
