@@ -589,6 +589,58 @@ int ltm_submaps_assemble(ltm_ctx*, ltm_scanset scans, const float* affine12_host
  * of 2^31 points or more LTM_E_UNSUPPORTED.  On an error no handle is returned and nothing stays allocated. */
 int ltm_search_build_scanset(ltm_ctx*, ltm_scanset, size_t kf_begin, size_t kf_end, ltm_search** out /* kf_end - kf_begin handles */);
 
+/* ---------------------------------------------------------------- clusters ---- */
+/* Euclidean cluster extraction over the target of a search index: pcl::EuclideanClusterExtraction (setClusterTolerance, setMinClusterSize,
+ * setMaxClusterSize, extract), the step that turns a map of changed points (nd_map, pd_map, scans_pd...) into objects, and the usual pre-filter before ICP,
+ * normals or one Scan Context per object.  The reference does not call it and PCL is not available to compare against; this is what this library takes PCL
+ * 1.10's extractEuclideanClusters / EuclideanClusterExtraction::extract to do, as understood.  tools/cluster_numpy.py restates it with scipy and the tests
+ * compare against that, for equality.
+ *  Graph: the vertices are the finite target points of the index; i and j are adjacent iff d2(i, j) < r2, with d2 the index's own distance (FLANN's
+ *   L2_Simple in float, ((dx*dx)+dy*dy)+dz*dz, no fused multiply-add) and r2 = (float)((double)tolerance * tolerance), strict <: exactly the relation of
+ *   ltm_radius_search.  The float expression is symmetric in its two points, so the relation is.  A cluster is a connected component; coincident points are
+ *   adjacent (0 < r2).
+ *  Filter: a component is kept iff min_size <= size <= max_size (max_size = 0: no upper limit).  The points of dropped components and the points with a
+ *   non-finite coordinate have label -1.
+ *  Order: clusters are numbered 0 .. n_clusters - 1 by size descending; TIES GO TO THE CLUSTER WHOSE LOWEST ORIGINAL POINT INDEX IS SMALLER (PCL's extract
+ *   sorts by size with an unstable sort).  Inside a cluster the point indices are listed in ascending original index.
+ *  Per cluster: size; lowest original index; bounding box, float min / max per axis, exact (-0.0 orders below +0.0); centroid, the mean of x, y, z in double.
+ *   The centroid's sum runs over the cluster's points in ascending original index in a fixed shape: chunks of 256 consecutive points, the last one padded
+ *   with zeros, each summed by a binary tree (entries 128 apart first, then 64, ... 1); the chunk sums 64 at a time, the last group padded with zeros, each
+ *   group by a binary tree (entries 32 apart first, then 16, ... 1), the group sums added in order; then divided by the size.  There are no floating-point
+ *   atomics: two runs give the same bytes, and the result is a function of the cluster's point set alone.
+ *  The partition, the numbering and every per-cluster value depend neither on the order of the input cloud (up to the renaming of the indices) nor on the
+ *   rest of the batch nor on the schedule.
+ *  Domain: tolerance finite and > 0; 1 <= min_size <= max_size or max_size = 0; a NULL handle, a handle of another context (a lane included): anything else
+ *   is LTM_E_INVALID, detected before the device is touched.  An empty index, or one without a finite point, is valid and gives zero clusters.  The same
+ *   index may be listed more than once.  All indices of a call together: fewer than 2^31 target points (LTM_E_UNSUPPORTED beyond).
+ *  DEPARTURES from PCL: PCL lists the points of a cluster in the breadth-first order of its region growing and leaves the order of clusters of equal size to
+ *   std::sort; here both are canonical.  PCL's max_size default is INT_MAX; here 0 says "no limit".  PCL grows one cluster after the other on one thread
+ *   with a radius search per point; here all points of all listed indices hook into a lock-free union-find at once (ltm_k_cluster.hip), which gives the
+ *   same partition.
+ * ltm_search_cluster clusters ALL listed indices in ONE fixed sequence of launches with ONE read-back by the host (the cluster and point counts of every
+ * index, which size the handles); out receives n_idx handles.  Memory comes from the context's pool; the handles of one call share their blocks, which
+ * return to the pool when the last of them is freed (ltm_destroy releases what is left); all scratch is back when the call returns, on every error path
+ * too, and then no handle is returned.  A cluster set keeps no reference to its index: either may be freed first. */
+typedef struct ltm_clusters ltm_clusters;
+typedef struct {
+    double   tolerance;   /* 0 (must be set)  setClusterTolerance [m] */
+    uint32_t min_size;    /* 1                setMinClusterSize */
+    uint32_t max_size;    /* 0 = no limit     setMaxClusterSize */
+} ltm_cluster_params;
+void ltm_cluster_default_params(ltm_cluster_params*);      /* host only, needs no device */
+int  ltm_search_cluster(ltm_ctx*, size_t n_idx, ltm_search* const* idx, const ltm_cluster_params*, ltm_clusters** out /* n_idx handles */);
+int  ltm_clusters_info(ltm_ctx*, ltm_clusters*, size_t* n_target, size_t* n_clusters, size_t* n_clustered_points);
+/* the set's device arrays, borrowed until ltm_clusters_free: labels (int32, n_target, the target's ORIGINAL order, -1 = in no cluster), CSR offsets
+ * (n_clusters + 1, uint64) and point indices (int32, n_clustered_points; row c = the points of cluster c in ascending original index) */
+int  ltm_clusters_device(ltm_ctx*, ltm_clusters*, const int32_t** labels_dev, const uint64_t** offsets_dev, const int32_t** idx_dev);
+/* host copies, any pointer may be NULL: labels n_target, sizes n_clusters, first_idx n_clusters (lowest original index), box6 n_clusters x 6 floats (min xyz, max
+ * xyz), centroid3 n_clusters x 3 doubles */
+int  ltm_clusters_download(ltm_ctx*, ltm_clusters*, int32_t* labels, uint32_t* sizes, int32_t* first_idx, float* box6, double* centroid3);
+/* the clustered points of `cloud` -- the cloud the index was built over: n_target points, else LTM_E_INVALID -- as an ordinary scan set, keyframe c = cluster c in
+ * the order of its CSR row: one PCD per object, gridding, Scan Context and ltm_search_build_scanset over the objects work on it unchanged */
+int  ltm_clusters_extract(ltm_ctx*, ltm_clusters*, ltm_cloud cloud, ltm_scanset* out);
+int  ltm_clusters_free(ltm_ctx*, ltm_clusters*);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections
@@ -720,6 +772,11 @@ int ltm_debug_voxel_stats(ltm_ctx*, uint64_t* grids, uint64_t* identity_hits, in
  * cell id + query index did not fit 64 bits so that phase 2 walked its queue in scan order.  All four are counted only in a context created
  * with LTM_KNN_STATS=1 (lanes inherit the switch) and stay 0 otherwise; any pointer may be NULL. */
 int ltm_debug_knn_stats(ltm_ctx*, uint64_t* queries, uint64_t* undecided, uint64_t* two_phase_calls, uint64_t* unsorted_queue_calls, int reset);
+/* counters of ltm_search_cluster since the last reset, stats[6]: point pairs whose distance was evaluated, pairs found adjacent (edges, each from its higher end;
+ * at most one per visited clique leaf), leaves visited by the walks, clique leaves among them (leaves whose box diagonal is below the tolerance: united
+ * beforehand), walks that left a clique leaf at its first hit, compare-and-swaps of the union-find that failed and were retried.  Always counted; context
+ * switch LTM_CLUSTER_CLIQUE=0 (read by ltm_create) turns the clique leaves off -- same results, the counters show which form ran. */
+int ltm_debug_cluster_stats(ltm_ctx*, uint64_t* stats /* 6 */, int reset);
 /* which kernel forms a Scan Context shape gets (host arithmetic only, needs no device; the launch wrappers' own expressions): *scatter_in_lds = 1 if
  * ltm_sc_from_scanset pre-reduces a block's points in LDS (up to 4096 bins), 0 if it goes straight to device memory; *pair_in_lds = 1 if the pair
  * distance of ltm_sc_distance / ltm_sc_detect stages both descriptors in LDS (up to 60 KB with the keys and norms), 0 if it reads them from device

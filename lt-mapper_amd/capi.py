@@ -34,6 +34,11 @@ class ScParams(C.Structure):
                 ("num_candidates", C.c_int), ("search_ratio", C.c_double), ("dist_thres", C.c_double)]
 
 
+class ClusterParams(C.Structure):
+    """ltm_cluster_params"""
+    _fields_ = [("tolerance", C.c_double), ("min_size", C.c_uint32), ("max_size", C.c_uint32)]
+
+
 class IcpParams(C.Structure):
     """ltm_icp_params (LTslam.cpp:207-210)"""
     _fields_ = [("max_corr_dist", C.c_double), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
@@ -167,6 +172,14 @@ SIGNATURES = {
     "ltm_pose6d_to_affine3f": (_i, [_vp, _sz, _vp]),
     "ltm_submaps_assemble": (_i, [_vp, _u64, _vp, _vp, _sz, _i, _f, _i, _pu64]),
     "ltm_search_build_scanset": (_i, [_vp, _u64, _sz, _sz, C.POINTER(_vp)]),
+    "ltm_cluster_default_params": (None, [C.POINTER(ClusterParams)]),
+    "ltm_search_cluster": (_i, [_vp, _sz, C.POINTER(_vp), C.POINTER(ClusterParams), C.POINTER(_vp)]),
+    "ltm_clusters_info": (_i, [_vp, _vp, _psz, _psz, _psz]),
+    "ltm_clusters_device": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_clusters_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltm_clusters_extract": (_i, [_vp, _vp, _u64, _pu64]),
+    "ltm_clusters_free": (_i, [_vp, _vp]),
+    "ltm_debug_cluster_stats": (_i, [_vp, _pu64, _i]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -667,6 +680,26 @@ class Context:
         hs = (_vp * max(n, 1))(*[x.h for x in indices])
         self._ck(self.lib.ltm_search_estimate_normals(self.h, n, hs, k, None if vp is None else vp.ctypes.data))
 
+    def cluster(self, indices, tolerance, min_size=1, max_size=None):
+        """ltm_search_cluster: pcl::EuclideanClusterExtraction over the targets of all `indices` (SearchIndex objects of this context; the same one may be
+        listed more than once) in one sequence of launches and one read-back.  Returns one Clusters per index.  max_size None: no upper limit."""
+        indices = list(indices)
+        p = cluster_params(tolerance, min_size, max_size)
+        for x in indices:
+            if not isinstance(x, SearchIndex):
+                raise TypeError("cluster takes SearchIndex objects (Context.search_index)")
+        n = len(indices)
+        hs = (_vp * max(n, 1))(*[x.h for x in indices])
+        out = (_vp * max(n, 1))()
+        self._ck(self.lib.ltm_search_cluster(self.h, n, hs, C.byref(p), out))
+        return [Clusters(self, out[i]) for i in range(n)]
+
+    def cluster_stats(self, reset=False):
+        """ltm_debug_cluster_stats: dict of the six counters since the last reset"""
+        a = (C.c_uint64 * 6)()
+        self._ck(self.lib.ltm_debug_cluster_stats(self.h, a, int(reset)))
+        return dict(zip(CLUSTER_STATS, [int(v) for v in a]))
+
     # ---- loop submaps
     def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
         """ltm_submaps_assemble: Session::loopFindNearKeyframesLocalCoord (affines=None) / CentralCoord (affines: (n_kf, 3, 4) float32, see
@@ -1041,9 +1074,99 @@ class SearchIndex:
         self.ctx._ck(self.ctx.lib.ltm_search_normals_download(self.ctx.h, self.h, out.ctypes.data))
         return out
 
+    def cluster(self, tolerance, min_size=1, max_size=None):
+        """ltm_search_cluster for this index alone: setClusterTolerance(tolerance), setMinClusterSize, setMaxClusterSize (None: no limit), extract"""
+        return self.ctx.cluster([self], tolerance, min_size, max_size)[0]
+
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.ltm_search_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CLUSTER_STATS = ("pairs_tested", "edges_found", "leaves_visited", "clique_leaves", "clique_early_exits", "hook_retries")
+
+
+def cluster_params(tolerance, min_size=1, max_size=None):
+    """ltm_cluster_params, checked: tolerance finite and > 0, 1 <= min_size <= max_size (None or 0: no upper limit)"""
+    tolerance = float(tolerance)
+    if not (np.isfinite(tolerance) and tolerance > 0.0):
+        raise ValueError("tolerance must be finite and > 0")
+    lo, hi = int(min_size), 0 if max_size is None else int(max_size)
+    if lo < 1 or hi < 0 or lo >= 2 ** 32 or hi >= 2 ** 32 or (hi != 0 and hi < lo):
+        raise ValueError("need 1 <= min_size <= max_size (max_size None: no limit)")
+    return ClusterParams(tolerance, lo, hi)
+
+
+class Clusters:
+    """ltm_clusters: the Euclidean clusters of one search index's target (semantics in include/ltm.h, "clusters").  Labels and point indices refer to the
+    target's ORIGINAL order; clusters are numbered by size descending, ties by the lowest original index."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        self._host = None
+
+    def info(self):
+        """(target points, clusters, clustered points)"""
+        a, b, c = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self.ctx._ck(self.ctx.lib.ltm_clusters_info(self.ctx.h, self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def __len__(self):
+        return self.info()[1]
+
+    def _device(self):
+        pl, po, pi = _vp(), _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_clusters_device(self.ctx.h, self.h, C.byref(pl), C.byref(po), C.byref(pi)))
+        return pl.value, po.value, pi.value
+
+    def labels(self, as_torch=False):
+        """int32 [n_target]: the cluster of every target point, -1 = none"""
+        return SearchIndex._out(self, self._device()[0], self.info()[0], np.int32, as_torch)
+
+    def indices(self, as_torch=False):
+        """CSR: (offsets uint64 [n_clusters + 1] (int64 as torch), idx int32 [clustered points]); row c = cluster c in ascending original index"""
+        _, nc, npts = self.info()
+        _, po, pi = self._device()
+        return SearchIndex._out(self, po, nc + 1, np.uint64, as_torch), SearchIndex._out(self, pi, npts, np.int32, as_torch)
+
+    def _download(self):
+        if self._host is None:
+            nc = self.info()[1]
+            sizes, first = np.empty(nc, np.uint32), np.empty(nc, np.int32)
+            box, cen = np.empty((nc, 6), np.float32), np.empty((nc, 3), np.float64)
+            self.ctx._ck(self.ctx.lib.ltm_clusters_download(self.ctx.h, self.h, None, sizes.ctypes.data, first.ctypes.data, box.ctypes.data, cen.ctypes.data))
+            self._host = (sizes, first, box, cen)
+        return self._host
+
+    sizes = property(lambda self: self._download()[0], doc="uint32 [n_clusters]")
+    first_index = property(lambda self: self._download()[1], doc="int32 [n_clusters]: lowest original index")
+    boxes = property(lambda self: self._download()[2], doc="float32 [n_clusters, 6]: min xyz, max xyz")
+    centroids = property(lambda self: self._download()[3], doc="float64 [n_clusters, 3]")
+
+    def extract(self, cloud):
+        """ltm_clusters_extract: the clustered points of `cloud` (the Cloud the index was built over, or its array) as a ScanSet, keyframe c = cluster c"""
+        if not isinstance(cloud, Cloud):
+            cloud = self.ctx.upload(_xyzi(cloud))
+        out = _u64()
+        self.ctx._ck(self.ctx.lib.ltm_clusters_extract(self.ctx.h, self.h, cloud.h, C.byref(out)))
+        return ScanSet(self.ctx, out.value)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ltm_clusters_free(self.ctx.h, self.h)
         self.h = None
 
     def __enter__(self):

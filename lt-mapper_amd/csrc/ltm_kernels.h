@@ -314,6 +314,37 @@ int        normals_block(int k);                // target points per workgroup o
 // out[j] = (nx, ny, nz, curvature) of target point t.pts[j] from its min(k, Mf) nearest target points, for every index of the table in one launch
 hipError_t estimate_normals(const NormalsSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, int k, hipStream_t s);
 
+// ---- Euclidean clusters over the targets of search indices (ltm_k_cluster.hip; include/ltm.h "clusters") ----
+static constexpr int kClusterBlock = 256;       // finite target points per workgroup of the per-point kernels
+static constexpr int kClusterChunk = 256;       // points per partial sum of a cluster's centroid
+// one listed index of the batch: its tree, its slice [fbase, fbase + Mf) of the batch's per-finite-point arrays (parent, root, size, ...), its slice
+// [tbase, tbase + n_target) of the labels, log2 of its tree's P and its workgroups [block0, block0 + ceil(Mf / kClusterBlock))
+struct ClusterSeg { SearchTree t; uint64_t fbase, tbase; uint32_t n_target, block0, logP, pad; };
+// init (every position its own root, clique leaves united), hook pass, flatten (root[], size and lowest original index per root); stats6 += pairs tested,
+// edges found, leaves visited, clique leaves among them, clique early exits, hook retries
+hipError_t cluster_hook(const ClusterSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, float r2, int clique_on, uint32_t* parent, uint32_t* root,
+                        uint32_t* size, uint32_t* minidx, int32_t* cid, unsigned long long* stats6, hipStream_t s);
+// keep[i] = 1 for the roots whose component has min_size <= size <= max_size; counts[2 k], counts[2 k + 1] += clusters and clustered points of index k
+hipError_t cluster_roots(const ClusterSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, const uint32_t* root, const uint32_t* size, uint32_t min_size,
+                         uint32_t max_size, uint8_t* keep, unsigned long long* counts, hipStream_t s);
+size_t     cluster_temp_bytes(size_t n_clusters, size_t n_segs);
+// the kept roots (pos: exclusive scan of keep) sorted per index by (size descending, lowest original index): cluster c of the batch, c in [coff[k], coff[k + 1])
+// for index k.  cid[root position] = c; csize / cfirst / cseg / cchunks per cluster (csize, cchunks: n_clusters + 1 entries), goff / choff their exclusive scans
+hipError_t cluster_number(const uint8_t* keep, const uint32_t* pos, size_t total, const uint32_t* size, const uint32_t* minidx, uint32_t n_clusters,
+                          const uint64_t* coff, uint32_t n_segs, uint64_t* keys, uint64_t* keys_sorted, uint32_t* vals, uint32_t* vals_sorted, int32_t* cid,
+                          uint32_t* csize, int32_t* cfirst, uint32_t* cseg, uint32_t* cchunks, uint32_t* goff, uint32_t* choff, void* temp, size_t temp_bytes,
+                          hipStream_t s);
+// labels[tbase + original index] = cluster number inside its index (the caller filled -1); keys / vals: every clustered point as (cluster << 32 | original
+// index, global position), unordered; cursor: one word
+hipError_t cluster_labels(const ClusterSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, const uint32_t* root, const int32_t* cid, const uint64_t* coff,
+                          int32_t* labels, uint64_t* keys, uint32_t* vals, uint32_t* cursor, hipStream_t s);
+inline size_t cluster_max_chunks(size_t n_clusters, size_t n_points) { return n_points / kClusterChunk + n_clusters; }      // >= sum of ceil(size / kClusterChunk)
+// from the sorted (cluster, original index) keys: the CSR point indices, and per cluster size, lowest index, box, centroid; offsets_out: n_clusters + n_segs
+// entries zeroed by the caller, index k's n_k + 1 offsets at coff[k] + k.  psum / pbox: 3 doubles / 6 words per cluster_max_chunks(n_clusters, n_points)
+hipError_t cluster_finish(const ClusterSeg* segs, const uint64_t* keys_sorted, const uint32_t* vals_sorted, uint32_t n_clusters, size_t n_points, const uint32_t* csize,
+                          const int32_t* cfirst, const uint32_t* cseg, const uint32_t* goff, const uint32_t* choff, const uint64_t* coff, double* psum, uint32_t* pbox,
+                          int32_t* idx_out, uint32_t* sizes_out, int32_t* first_out, float* box_out, double* centroid_out, uint64_t* offsets_out, hipStream_t s);
+
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
 // one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; workgroups [block0, block0 + ceil(n / 256))
 struct SubmapPiece { uint64_t src, dst; uint32_t n, block0, affine, pad; };
