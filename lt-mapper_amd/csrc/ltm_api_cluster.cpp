@@ -2,17 +2,9 @@
 // pcl::EuclideanClusterExtraction.  Kernels in ltm_k_cluster.hip, the union-find in ltm_unionfind.h.
 #include "ltm_internal.h"
 
-// the pool blocks that the cluster sets of one ltm_search_cluster share: back in the pool when the last of them is freed
-struct ClusterBatch {
-    ltm_ctx* c;
-    void* blocks[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // labels, offsets, idx, sizes, first, box, centroid
-    explicit ClusterBatch(ltm_ctx* c_) : c(c_) {}
-    ~ClusterBatch() { for (void* b : blocks) c->pool.free(b); }
-    ClusterBatch(const ClusterBatch&) = delete; ClusterBatch& operator=(const ClusterBatch&) = delete;
-};
 struct ltm_clusters {
     ltm_ctx* owner = nullptr;
-    std::shared_ptr<ClusterBatch> batch;      // every pointer below points into its blocks
+    std::shared_ptr<PoolBlocks> batch;        // every pointer below points into the blocks that the cluster sets of one ltm_search_cluster share
     size_t n_target = 0, n_clusters = 0, n_points = 0;
     int32_t* labels = nullptr;                // n_target, the target's original order
     uint64_t* offsets = nullptr;              // n_clusters + 1
@@ -22,21 +14,15 @@ struct ltm_clusters {
 
 namespace {
 
-ltm_clusters* get_clusters(ltm_ctx* c, ltm_clusters* s)
-{
-    LTM_REQUIRE(s && std::find(c->cluster_open.begin(), c->cluster_open.end(), s) != c->cluster_open.end(), "not a cluster set of this context");
-    return s;
-}
-
-template <class T> T* block(ClusterBatch& b, int i, size_t n) { return reinterpret_cast<T*>(b.blocks[i] = b.c->pool.alloc(std::max<size_t>(n, 1) * sizeof(T))); }
+ltm_clusters* get_clusters(ltm_ctx* c, ltm_clusters* s) { return open_handle(c->cluster_open, s, "not a cluster set of this context"); }
 
 void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_cluster_params& p, std::vector<std::unique_ptr<ltm_clusters>>& out)
 {
     const float r2 = (float)(p.tolerance * p.tolerance);
     const uint32_t min_size = p.min_size, max_size = p.max_size ? p.max_size : 0xffffffffu;
-    auto batch = std::make_shared<ClusterBatch>(c);
+    auto batch = std::make_shared<PoolBlocks>(c);
     std::vector<ClusterSeg> segs(n_idx);
-    std::vector<uint32_t> block_seg;
+    BlockTable table;
     uint64_t total_f = 0, total_t = 0;
     out.resize(n_idx);
     for (size_t k = 0; k < n_idx; ++k) {
@@ -48,11 +34,8 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
         if (ltm_search_info(c, idx[k], &nt, nullptr) != LTM_OK) throw Err{LTM_E_INVALID, c->err};
         S.n_target = (uint32_t)nt;
         S.fbase = total_f; S.tbase = total_t;
-        S.block0 = (uint32_t)block_seg.size();
         while (((uint32_t)1 << S.logP) < S.t.P) ++S.logP;
-        const uint32_t nb = (S.t.Mf + kClusterBlock - 1) / kClusterBlock;
-        if ((uint64_t)block_seg.size() + nb >= 0x7fffffffull) throw Err{LTM_E_UNSUPPORTED, "too many target points in one ltm_search_cluster"};
-        block_seg.insert(block_seg.end(), nb, (uint32_t)k);
+        if (!table.add((uint32_t)k, S.t.Mf, kClusterBlock, &S.span)) throw Err{LTM_E_UNSUPPORTED, "too many target points in one ltm_search_cluster"};
         total_f += S.t.Mf; total_t += nt;
         out[k].reset(new ltm_clusters);
         out[k]->owner = c;
@@ -60,15 +43,13 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
         out[k]->n_target = nt;
     }
     if (total_t >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, "the indices of one ltm_search_cluster must have fewer than 2^31 target points in all"};
-    const uint32_t n_blocks = (uint32_t)block_seg.size();
-    int32_t* labels = block<int32_t>(*batch, 0, total_t);
+    const uint32_t n_blocks = table.size();
+    int32_t* labels = batch->alloc<int32_t>(total_t);
     LTM_HIP(fill_u32(reinterpret_cast<uint32_t*>(labels), 0xffffffffu, total_t, c->stream));
     std::vector<uint64_t> coff(n_idx + 1, 0), poff(n_idx + 1, 0);
     if (total_f) {
         ProfScope ps(c, "cluster", (double)total_f, 48.0 * (double)total_f);
-        DevBuf d_segs(c, n_idx * sizeof(ClusterSeg)), d_bs(c, (size_t)n_blocks * 4);
-        h2d(c, d_segs.p, segs.data(), n_idx * sizeof(ClusterSeg));
-        h2d(c, d_bs.p, block_seg.data(), (size_t)n_blocks * 4);
+        DevBuf d_segs = to_device(c, segs), d_bs = to_device(c, table.owner());
         const size_t n_cnt = 6 + 2 * n_idx;
         DevBuf parent(c, total_f * 4), root(c, total_f * 4), size(c, total_f * 4), minidx(c, total_f * 4), cid(c, total_f * 4), keep(c, total_f), pos(c, total_f * 4),
             cnt(c, n_cnt * 8);
@@ -89,16 +70,15 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
             poff[k + 1] = poff[k] + out[k]->n_points;
         }
         const uint64_t nc = coff[n_idx], np = poff[n_idx];
-        uint64_t* offsets = block<uint64_t>(*batch, 1, nc + n_idx);
-        int32_t* pidx = block<int32_t>(*batch, 2, np);
-        uint32_t* sizes = block<uint32_t>(*batch, 3, nc);
-        int32_t* first = block<int32_t>(*batch, 4, nc);
-        float* box = block<float>(*batch, 5, nc * 6);
-        double* centroid = block<double>(*batch, 6, nc * 3);
+        uint64_t* offsets = batch->alloc<uint64_t>(nc + n_idx);      // (no cluster, no clustered point: the pool's smallest block)
+        int32_t* pidx = batch->alloc<int32_t>(np);
+        uint32_t* sizes = batch->alloc<uint32_t>(nc);
+        int32_t* first = batch->alloc<int32_t>(nc);
+        float* box = batch->alloc<float>(nc * 6);
+        double* centroid = batch->alloc<double>(nc * 3);
         LTM_HIP(hipMemsetAsync(offsets, 0, (nc + n_idx) * 8, c->stream));
         if (nc) {
-            DevBuf d_coff(c, (n_idx + 1) * 8);
-            h2d(c, d_coff.p, coff.data(), (n_idx + 1) * 8);
+            DevBuf d_coff = to_device(c, coff);
             const size_t tb = cluster_temp_bytes(nc, n_idx);
             DevBuf keys(c, nc * 8), keys_s(c, nc * 8), vals(c, nc * 4), vals_s(c, nc * 4), csize(c, (nc + 1) * 4), cfirst(c, nc * 4), cseg(c, nc * 4),
                 cchunks(c, (nc + 1) * 4), goff(c, (nc + 1) * 4), choff(c, (nc + 1) * 4), temp(c, tb);
@@ -129,7 +109,7 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
             s->sizes = sizes + coff[k]; s->first = first + coff[k]; s->box = box + 6 * coff[k]; s->centroid = centroid + 3 * coff[k];
         }
     } else {
-        uint64_t* offsets = block<uint64_t>(*batch, 1, n_idx);
+        uint64_t* offsets = batch->alloc<uint64_t>(n_idx);
         LTM_HIP(hipMemsetAsync(offsets, 0, n_idx * 8, c->stream));
         for (size_t k = 0; k < n_idx; ++k) out[k]->offsets = offsets + k;
     }
@@ -232,7 +212,7 @@ int ltm_clusters_free(ltm_ctx* c, ltm_clusters* h)
 {
     return guarded(c, [&] {
         get_clusters(c, h);
-        c->cluster_open.erase(std::remove(c->cluster_open.begin(), c->cluster_open.end(), h), c->cluster_open.end());
+        forget_handle(c->cluster_open, h);
         delete h;
     });
 }

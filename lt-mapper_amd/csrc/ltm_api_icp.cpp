@@ -44,7 +44,7 @@ void icp_align_impl(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* t
     std::vector<IcpPair> pairs(n_pairs);
     std::vector<IcpState> st(n_pairs);
     std::vector<uint64_t> off(n_pairs + 1, 0);
-    std::vector<uint32_t> block_pair;
+    BlockTable table;
     uint32_t active = 0;
     for (size_t i = 0; i < n_pairs; ++i) {
         IcpPair& P = pairs[i];
@@ -62,12 +62,11 @@ void icp_align_impl(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* t
         P.snrm = src.nrm;
         P.o[0] = P.f.ox; P.o[1] = P.f.oy; P.o[2] = P.f.oz;
         P.first = off[i];
-        P.n = run ? (uint32_t)src.n : 0u;
-        P.block0 = (uint32_t)block_pair.size();
-        P.n_blocks = (P.n + kIcpBlock - 1) / kIcpBlock;
+        P.n = P.n_gather = run ? (uint32_t)src.n : 0u;
         off[i + 1] = off[i] + P.n;
         LTM_REQUIRE(off[i + 1] < 0x80000000ull, "the sources of one batch must have fewer than 2^31 points in all");
-        block_pair.insert(block_pair.end(), P.n_blocks, (uint32_t)i);
+        // (unreachable in practice at the table's default limit: with fewer than 2^31 source points in all, checked above, it would take about 2^31 pairs of one point each)
+        if (!table.add((uint32_t)i, P.n, kIcpBlock, &P.span)) throw Err{LTM_E_UNSUPPORTED, "too many source points in one batch of ICP pairs"};
         IcpState& S = st[i];
         memset(&S, 0, sizeof S);
         const double* T0 = init16 ? init16 + 16 * i : nullptr;
@@ -80,17 +79,13 @@ void icp_align_impl(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* t
         active += run ? 1u : 0u;
     }
     const size_t total = off[n_pairs];
-    const uint32_t n_blocks = (uint32_t)block_pair.size();
+    const uint32_t n_blocks = table.size();
 
     if (active) {
-        DevBuf d_pairs(c, n_pairs * sizeof(IcpPair)), d_st(c, n_pairs * sizeof(IcpState)), d_off(c, (n_pairs + 1) * 8), d_bp(c, (size_t)n_blocks * 4);
+        DevBuf d_pairs = to_device(c, pairs), d_st = to_device(c, st), d_off = to_device(c, off), d_bp = to_device(c, table.owner());
         std::unique_ptr<DevBuf> d_sorted;      // the sources in their target's code order; generalized ICP reads its source indices in place and has none
         if (!gicp) d_sorted.reset(new DevBuf(c, total * sizeof(float4)));
         DevBuf d_part(c, (size_t)n_blocks * (wide ? kIcpPlanePartial : kIcpPartial) * sizeof(double)), d_unf(c, 4), d_trace(c, std::max<size_t>(trace_n, 1) * 8);
-        h2d(c, d_pairs.p, pairs.data(), n_pairs * sizeof(IcpPair));
-        h2d(c, d_st.p, st.data(), n_pairs * sizeof(IcpState));
-        h2d(c, d_off.p, off.data(), (n_pairs + 1) * 8);
-        h2d(c, d_bp.p, block_pair.data(), (size_t)n_blocks * 4);
         h2d(c, d_unf.p, &active, 4);
         if (trace_n) LTM_HIP(hipMemsetAsync(d_trace.p, 0xff, trace_n * 8, c->stream));      // all ones: a NaN
         const IcpPair* dp = d_pairs.as<IcpPair>();
@@ -101,11 +96,10 @@ void icp_align_impl(ltm_ctx* c, int method, size_t n_pairs, ltm_search* const* t
             // each source once into the code order of its target's frame: the lanes of a wavefront then walk the same part of the tree
             ProfScope ps(c, "icp_prepare", (double)total, 72.0 * (double)total);
             DevBuf keys(c, total * 8), keys_sorted(c, total * 8), idx(c, total * 4), order(c, total * 4);
-            const size_t tb = icp_sort_temp_bytes(total, n_pairs);
+            const size_t tb = seg_sort_pairs_temp_bytes(total, n_pairs);
             DevBuf temp(c, tb);
-            LTM_HIP(icp_source_keys(dp, bp, n_blocks, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
-            LTM_HIP(icp_sort_sources(dp, bp, n_blocks, n_pairs, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), idx.as<uint32_t>(),
-                                     order.as<uint32_t>(), d_sorted->as<float4>(), temp.p, tb, c->stream));
+            LTM_HIP(icp_order_sources(dp, bp, n_blocks, n_pairs, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), idx.as<uint32_t>(),
+                                      order.as<uint32_t>(), d_sorted->as<float4>(), temp.p, tb, c->stream));
         }
         const double max2 = prm.max_corr_dist * prm.max_corr_dist;
         const int poll = poll_interval();

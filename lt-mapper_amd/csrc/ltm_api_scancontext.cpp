@@ -21,12 +21,7 @@ void sc_release(ltm_ctx* c, ltm_sc* s)
     c->pool.free(s->desc); c->pool.free(s->ring_keys); c->pool.free(s->sector_keys); c->pool.free(s->norms);
     delete s;
 }
-// a handle of THIS context (a freed one, one of another context or a lane's is refused before it is dereferenced)
-ltm_sc* get_sc(ltm_ctx* c, ltm_sc* s)
-{
-    LTM_REQUIRE(s && std::find(c->sc_open.begin(), c->sc_open.end(), s) != c->sc_open.end(), "not a scan-context set of this context");
-    return s;
-}
+ltm_sc* get_sc(ltm_ctx* c, ltm_sc* s) { return open_handle(c->sc_open, s, "not a scan-context set of this context"); }
 
 ltm_sc_params params_or_default(const ltm_sc_params* p)
 {
@@ -254,7 +249,7 @@ int ltm_sc_free(ltm_ctx* c, ltm_sc* s)
 {
     return guarded(c, [&] {
         get_sc(c, s);
-        c->sc_open.erase(std::remove(c->sc_open.begin(), c->sc_open.end(), s), c->sc_open.end());
+        forget_handle(c->sc_open, s);
         sc_release(c, s);
     });
 }

@@ -2,27 +2,10 @@
 // pcl::KdTreeFLANN members (Session.cpp:18-23, :404, :457, :471, :489, :592, :627).  Kernels in ltm_k_search.hip.
 #include "ltm_internal.h"
 
-// the pool blocks that the indices of one ltm_search_build_scanset share: back in the pool when the last of them is released
-struct SearchBatch {
-    ltm_ctx* c;
-    void* blocks[4] = {nullptr, nullptr, nullptr, nullptr};
-    explicit SearchBatch(ltm_ctx* c_) : c(c_) {}
-    ~SearchBatch() { for (void* b : blocks) c->pool.free(b); }
-    SearchBatch(const SearchBatch&) = delete; SearchBatch& operator=(const SearchBatch&) = delete;
-};
-// the pool block that holds the normals of the indices of one ltm_search_estimate_normals: back in the pool when the last of them is released or
-// estimated again
-struct NormalsBlock {
-    ltm_ctx* c;
-    void* p;
-    NormalsBlock(ltm_ctx* c_, size_t bytes) : c(c_), p(c_->pool.alloc(bytes)) {}
-    ~NormalsBlock() { c->pool.free(p); }
-    NormalsBlock(const NormalsBlock&) = delete; NormalsBlock& operator=(const NormalsBlock&) = delete;
-};
 struct ltm_search {
     ltm_ctx* owner = nullptr;
-    std::shared_ptr<SearchBatch> batch;   // set: pts / idx / keys / box point into the batch's blocks
-    std::shared_ptr<NormalsBlock> nblock; // set: normals points into it
+    std::shared_ptr<PoolBlocks> batch;    // set: pts / idx / keys / box point into the blocks that the indices of one ltm_search_build_scanset share
+    std::shared_ptr<PoolBlocks> nblock;   // set: normals points into the block of one ltm_search_estimate_normals (released with the last index, or estimated again)
     float4* normals = nullptr;            // (nx, ny, nz, curvature) of pts[j], Mf of them
     int normals_k = 0;                    // 0: none estimated
     size_t n_target = 0;
@@ -52,17 +35,8 @@ void result_release(ltm_ctx* c, ltm_search_result* r)
     c->pool.free(r->off); c->pool.free(r->idx); c->pool.free(r->d2);
     delete r;
 }
-// a handle of THIS context (a freed one, one of another context or a lane's is refused before it is dereferenced)
-ltm_search* get_search(ltm_ctx* c, ltm_search* s)
-{
-    LTM_REQUIRE(s && std::find(c->search_open.begin(), c->search_open.end(), s) != c->search_open.end(), "not a search index of this context");
-    return s;
-}
-ltm_search_result* get_result(ltm_ctx* c, ltm_search_result* r)
-{
-    LTM_REQUIRE(r && std::find(c->result_open.begin(), c->result_open.end(), r) != c->result_open.end(), "not a search result of this context");
-    return r;
-}
+ltm_search* get_search(ltm_ctx* c, ltm_search* s) { return open_handle(c->search_open, s, "not a search index of this context"); }
+ltm_search_result* get_result(ltm_ctx* c, ltm_search_result* r) { return open_handle(c->result_open, r, "not a search result of this context"); }
 
 SearchFrame frame_of(const float mn[3], const float mx[3]);
 void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
@@ -110,11 +84,11 @@ void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std:
     const size_t nk = ke - kb;
     const uint64_t first = ss.off[kb], total = ss.off[ke] - first;
     if (total >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, "a batch of search indices must have fewer than 2^31 points in all"};
-    auto batch = std::make_shared<SearchBatch>(c);
+    auto batch = std::make_shared<PoolBlocks>(c);
     out.resize(nk);
     std::vector<SearchSeg> segs(nk);
     std::vector<uint64_t> off(nk + 1, 0);
-    std::vector<uint32_t> block_seg;
+    BlockTable table;
     for (size_t k = 0; k < nk; ++k) {
         out[k].reset(new ltm_search);
         out[k]->owner = c;
@@ -124,17 +98,14 @@ void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std:
         S.src = ss.d + ss.off[kb + k];
         S.first = ss.off[kb + k] - first;
         S.n = (uint32_t)out[k]->n_target;
-        S.block0 = (uint32_t)block_seg.size();
-        block_seg.insert(block_seg.end(), (S.n + kSearchSegChunk - 1) / kSearchSegChunk, (uint32_t)k);
+        // (unreachable in practice at the table's default limit: with fewer than 2^31 points in all, checked above, it would take about 2^31 keyframes of one point each)
+        if (!table.add((uint32_t)k, S.n, kSearchSegChunk, &S.span)) throw Err{LTM_E_UNSUPPORTED, "too many points in one batch of search indices"};
         off[k + 1] = S.first + S.n;
     }
     if (!total) return;
-    const uint32_t n_blocks = (uint32_t)block_seg.size();
+    const uint32_t n_blocks = table.size();
     ProfScope p(c, "search_build_batch", (double)total, 48.0 * (double)total);
-    DevBuf d_segs(c, nk * sizeof(SearchSeg)), d_bs(c, (size_t)n_blocks * 4), d_off(c, (nk + 1) * 8), bb(c, nk * 8 * sizeof(uint32_t));
-    h2d(c, d_segs.p, segs.data(), nk * sizeof(SearchSeg));
-    h2d(c, d_bs.p, block_seg.data(), (size_t)n_blocks * 4);
-    h2d(c, d_off.p, off.data(), (nk + 1) * 8);
+    DevBuf d_segs = to_device(c, segs), d_bs = to_device(c, table.owner()), d_off = to_device(c, off), bb(c, nk * 8 * sizeof(uint32_t));
     LTM_HIP(search_bbox_seg(d_segs.as<SearchSeg>(), nk, d_bs.as<uint32_t>(), n_blocks, bb.as<uint32_t>(), c->stream));
     std::vector<uint32_t> enc(nk * 8);
     d2h(c, enc.data(), bb.p, enc.size() * 4);      // the one read-back: every size below follows from it
@@ -142,7 +113,7 @@ void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std:
     for (size_t k = 0; k < nk; ++k) {
         ltm_search* s = out[k].get();
         SearchSeg& S = segs[k];
-        s->Mf = S.Mf = enc[8 * k + 6];
+        s->Mf = S.n_gather = enc[8 * k + 6];
         if (!s->Mf) continue;
         float mn[3], mx[3];
         decode_box(&enc[8 * k], mn, mx);
@@ -157,16 +128,15 @@ void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std:
     if (!box_total) return;      // no finite point anywhere: every index is a valid empty one
     h2d(c, d_segs.p, segs.data(), nk * sizeof(SearchSeg));
     DevBuf keys(c, total * 8), idx(c, total * 4);
-    uint64_t* keys_sorted = reinterpret_cast<uint64_t*>(batch->blocks[0] = c->pool.alloc(total * 8));
-    uint32_t* order = reinterpret_cast<uint32_t*>(batch->blocks[1] = c->pool.alloc(total * 4));
-    float4* pts = reinterpret_cast<float4*>(batch->blocks[2] = c->pool.alloc(total * sizeof(float4)));
-    float4* box = reinterpret_cast<float4*>(batch->blocks[3] = c->pool.alloc(box_total * sizeof(float4)));
-    LTM_HIP(search_keys_seg(d_segs.as<SearchSeg>(), d_bs.as<uint32_t>(), n_blocks, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
+    uint64_t* keys_sorted = batch->alloc<uint64_t>(total);
+    uint32_t* order = batch->alloc<uint32_t>(total);
+    float4* pts = batch->alloc<float4>(total);
+    float4* box = batch->alloc<float4>(box_total);
     {
-        const size_t tb = search_sort_seg_temp_bytes(total, nk);
+        const size_t tb = seg_sort_pairs_temp_bytes(total, nk);
         DevBuf temp(c, tb);
-        LTM_HIP(search_sort_gather_seg(d_segs.as<SearchSeg>(), d_bs.as<uint32_t>(), n_blocks, nk, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted,
-                                       idx.as<uint32_t>(), order, pts, temp.p, tb, c->stream));
+        LTM_HIP(search_order_seg(d_segs.as<SearchSeg>(), d_bs.as<uint32_t>(), n_blocks, nk, d_off.as<uint64_t>(), total, keys.as<uint64_t>(), keys_sorted,
+                                 idx.as<uint32_t>(), order, pts, temp.p, tb, c->stream));
     }
     LTM_HIP(search_tree_boxes_seg(d_segs.as<SearchSeg>(), nk, pts, box, c->stream));
     for (size_t k = 0; k < nk; ++k) {
@@ -229,7 +199,7 @@ int ltm_search_estimate_normals(ltm_ctx* c, size_t n_idx, ltm_search* const* idx
         LTM_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "an index is listed twice");
         const uint32_t block = (uint32_t)normals_block(k);
         std::vector<NormalsSeg> segs(n_idx);
-        std::vector<uint32_t> block_seg;
+        BlockTable table;
         uint64_t total = 0;
         for (size_t i = 0; i < n_idx; ++i) {
             NormalsSeg& S = segs[i];
@@ -239,24 +209,18 @@ int ltm_search_estimate_normals(ltm_ctx* c, size_t n_idx, ltm_search* const* idx
                 S.vp[d] = viewpoints3 ? (double)viewpoints3[3 * i + d] : 0.0;
                 LTM_REQUIRE(std::isfinite(S.vp[d]), "a viewpoint is not finite");
             }
-            S.block0 = (uint32_t)block_seg.size();
-            S.pad = (uint32_t)0;
-            const uint32_t nb = (S.t.Mf + block - 1) / block;
-            LTM_REQUIRE((uint64_t)block_seg.size() + nb < 0x7fffffffull, "too many target points in one call");
-            block_seg.insert(block_seg.end(), nb, (uint32_t)i);
+            LTM_REQUIRE(table.add((uint32_t)i, S.t.Mf, block, &S.span), "too many target points in one call");
             total += S.t.Mf;
         }
-        std::shared_ptr<NormalsBlock> nb;
+        std::shared_ptr<PoolBlocks> nb;
         if (total) {
-            nb = std::make_shared<NormalsBlock>(c, total * sizeof(float4));
+            nb = std::make_shared<PoolBlocks>(c);
+            float4* normals = nb->alloc<float4>(total);
             uint64_t at = 0;
-            for (size_t i = 0; i < n_idx; ++i) { segs[i].out = reinterpret_cast<float4*>(nb->p) + at; at += segs[i].t.Mf; }
-            const uint32_t n_blocks = (uint32_t)block_seg.size();
+            for (size_t i = 0; i < n_idx; ++i) { segs[i].out = normals + at; at += segs[i].t.Mf; }
             ProfScope ps(c, "normals", (double)total, (double)total * (32.0 + 16.0 * k));
-            DevBuf d_segs(c, n_idx * sizeof(NormalsSeg)), d_bs(c, (size_t)n_blocks * 4);
-            h2d(c, d_segs.p, segs.data(), n_idx * sizeof(NormalsSeg));
-            h2d(c, d_bs.p, block_seg.data(), (size_t)n_blocks * 4);
-            LTM_HIP(estimate_normals(d_segs.as<NormalsSeg>(), d_bs.as<uint32_t>(), n_blocks, k, c->stream));
+            DevBuf d_segs = to_device(c, segs), d_bs = to_device(c, table.owner());
+            LTM_HIP(estimate_normals(d_segs.as<NormalsSeg>(), d_bs.as<uint32_t>(), table.size(), k, c->stream));
         }
         for (size_t i = 0; i < n_idx; ++i) {
             ltm_search* s = idx[i];
@@ -337,7 +301,7 @@ int ltm_search_free(ltm_ctx* c, ltm_search* s)
 {
     return guarded(c, [&] {
         get_search(c, s);
-        c->search_open.erase(std::remove(c->search_open.begin(), c->search_open.end(), s), c->search_open.end());
+        forget_handle(c->search_open, s);
         search_release(c, s);
     });
 }
@@ -435,7 +399,7 @@ int ltm_search_result_free(ltm_ctx* c, ltm_search_result* r)
 {
     return guarded(c, [&] {
         get_result(c, r);
-        c->result_open.erase(std::remove(c->result_open.begin(), c->result_open.end(), r), c->result_open.end());
+        forget_handle(c->result_open, r);
         result_release(c, r);
     });
 }

@@ -50,7 +50,7 @@ int ltm_submaps_assemble(ltm_ctx* c, ltm_scanset hscans, const float* affine12, 
         }
         // the pieces (window, source keyframe, affine) and the table that names the piece of every workgroup
         std::vector<SubmapPiece> pieces;
-        std::vector<uint32_t> block_piece;
+        BlockTable table;
         pieces.reserve(n_pieces);
         for (size_t w = 0; w < n_windows; ++w) {
             int64_t lo, hi;
@@ -60,29 +60,29 @@ int ltm_submaps_assemble(ltm_ctx* c, ltm_scanset hscans, const float* affine12, 
                 const uint64_t n = s.off[(size_t)k + 1] - s.off[(size_t)k];
                 if (!n) continue;
                 SubmapPiece P;
-                P.src = s.off[(size_t)k]; P.dst = at; P.n = (uint32_t)n; P.block0 = (uint32_t)block_piece.size();
-                P.affine = affine12 ? (uint32_t)k : 0u; P.pad = 0;
-                block_piece.insert(block_piece.end(), (size_t)((n + 255) / 256), (uint32_t)pieces.size());
+                P.src = s.off[(size_t)k]; P.dst = at; P.n = (uint32_t)n;
+                P.affine = affine12 ? (uint32_t)k : 0u;
+                // (unreachable in practice at the table's default limit: with fewer than 2^32 - 1 points in all, checked above, it would take 2^31 - 2^24 pieces)
+                if (!table.add((uint32_t)pieces.size(), n, 256, &P.span)) throw Err{LTM_E_UNSUPPORTED, "too many points in one batch of submaps"};
                 pieces.push_back(P);
                 at += n;
             }
         }
         const uint64_t total = off[n_windows];
-        const uint32_t n_blocks = (uint32_t)block_piece.size();
         // the transformed concatenation, as a scan set of its own: the result (leaf == 0) or the input of the grid
-        struct Block { ltm_ctx* c; void* p; ~Block() { c->pool.free(p); } } d{c, c->pool.alloc(std::max<uint64_t>(total, 1) * sizeof(float4))};
+        PoolBlocks own(c);
+        float4* d = own.alloc<float4>(std::max<uint64_t>(total, 1));
         if (total) {
             static const float kIdentity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
             const size_t na = affine12 ? (size_t)nkf : 1;
-            DevBuf d_aff(c, na * 12 * sizeof(float)), d_pieces(c, pieces.size() * sizeof(SubmapPiece)), d_bp(c, (size_t)n_blocks * 4);
+            DevBuf d_aff(c, na * 12 * sizeof(float));
             h2d(c, d_aff.p, affine12 ? affine12 : kIdentity, na * 12 * sizeof(float));
-            h2d(c, d_pieces.p, pieces.data(), pieces.size() * sizeof(SubmapPiece));
-            h2d(c, d_bp.p, block_piece.data(), (size_t)n_blocks * 4);
+            DevBuf d_pieces = to_device(c, pieces), d_bp = to_device(c, table.owner());
             ProfScope ps(c, "submap_assemble", (double)total, 32.0 * (double)total);
-            LTM_HIP(submap_gather(s.d, d_pieces.as<SubmapPiece>(), d_bp.as<uint32_t>(), n_blocks, d_aff.as<float>(), reinterpret_cast<float4*>(d.p), c->stream));
+            LTM_HIP(submap_gather(s.d, d_pieces.as<SubmapPiece>(), d_bp.as<uint32_t>(), table.size(), d_aff.as<float>(), d, c->stream));
         }
-        const ltm_scanset cat = new_scanset(c, reinterpret_cast<float4*>(d.p), std::move(off));
-        d.p = nullptr;      // the scan set owns the block now
+        const ltm_scanset cat = new_scanset(c, d, std::move(off));
+        own.release(d);      // the scan set owns the block now
         if (leaf == 0.0f) { *out = cat; return; }
         const int rc = voxel_grid_scanset_ordered(c, cat, leaf, order, out);
         const std::string msg = c->err;

@@ -458,6 +458,37 @@ inline void d2d(ltm_ctx* c, void* dst, const void* src, size_t bytes)
     if (!bytes) return;
     LTM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
 }
+// a host table in pooled scratch: one h2d
+template <class T>
+inline DevBuf to_device(ltm_ctx* c, const std::vector<T>& v)
+{
+    DevBuf d(c, v.size() * sizeof(T));
+    h2d(c, d.p, v.data(), v.size() * sizeof(T));
+    return d;
+}
+
+// Pool blocks with one owner that several handles may share through a std::shared_ptr: back in the pool with the last of them
+struct PoolBlocks {
+    ltm_ctx* c;
+    std::vector<void*> blocks;
+    explicit PoolBlocks(ltm_ctx* c_) : c(c_) {}
+    ~PoolBlocks() { for (void* b : blocks) c->pool.free(b); }
+    PoolBlocks(const PoolBlocks&) = delete; PoolBlocks& operator=(const PoolBlocks&) = delete;
+    // n elements; n = 0 is allowed and gives the pool's smallest block (Pool::alloc rounds 0 bytes up to 1).  The slot first, so that a block is never allocated and then not recorded
+    template <class T> T* alloc(size_t n) { blocks.push_back(nullptr); return reinterpret_cast<T*>(blocks.back() = c->pool.alloc(n * sizeof(T))); }
+    void release(void* p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); }      // p has another owner now
+};
+
+// The open-handle lists of a context (search_open, result_open, ...): a handle of THIS context, or throw `what` -- a freed one, one of another context
+// or a lane's is refused before it is dereferenced; and the list forgetting one
+template <class H>
+inline H* open_handle(const std::vector<H*>& open, H* h, const char* what)
+{
+    LTM_REQUIRE(h && std::find(open.begin(), open.end(), h) != open.end(), what);
+    return h;
+}
+template <class H>
+inline void forget_handle(std::vector<H*>& open, H* h) { open.erase(std::remove(open.begin(), open.end(), h), open.end()); }
 
 // min / max corners of a box of six ordered keys
 inline void decode_box(const uint32_t* enc, float mn[3], float mx[3])

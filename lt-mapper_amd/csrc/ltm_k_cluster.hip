@@ -3,8 +3,7 @@
 // (gfx950 / CDNA4, wave64; part of libltm_hip.so -- shared definitions in ltm_kernels_common.h, launch wrappers declared in ltm_kernels.h)
 //
 // Hook pass: one thread per finite target point in the index's own (Morton) order -- the lanes of a wavefront are neighbours in space and walk the same part
-// of the box tree, no query sort.  All indices of a call go through ONE launch; a per-block table names the index (as ltm_k_icp.hip / ltm_k_normals.hip do),
-// so a workgroup never straddles two indices.  The thread walks the implicit tree with skip(lb) = lb >= r2 and, in a visited leaf, tests only the points at a
+// of the box tree, no query sort.  All indices of a call go through ONE launch over the batch's owner table (ltm_block_table.h).  The thread walks the implicit tree with skip(lb) = lb >= r2 and, in a visited leaf, tests only the points at a
 // LOWER sorted position: every edge is seen once, from its higher end.  The walk is the stackless one of ltm_search_walk.h with one addition: the leaves
 // come in ascending position, so it ends at the first node whose leaves all lie at or above the thread's own position (half of every walk).  On
 // d2 < r2 the two points are united in the lock-free union-find of ltm_unionfind.h over positions local to the index.
@@ -27,7 +26,6 @@
 #include "ltm_search_walk.h"      // box_lb
 #include "ltm_unionfind.h"
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 namespace ltm {
 
 namespace {
@@ -100,8 +98,9 @@ __global__ void __launch_bounds__(kClusterBlock)
 k_cluster_init(const ClusterSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, float r2, int clique_on, uint32_t* __restrict__ parent,
                uint32_t* __restrict__ size, uint32_t* __restrict__ minidx, int32_t* __restrict__ cid)
 {
-    const ClusterSeg& S = segs[block_seg[blockIdx.x]];
-    const uint32_t j = (blockIdx.x - S.block0) * kClusterBlock + threadIdx.x;
+    uint32_t j;
+    const ClusterSeg& S = block_record<kClusterBlock>(segs, block_seg, j);
+    j += threadIdx.x;
     if (j >= S.t.Mf) return;
     const uint32_t l = j / kSearchLeaf;
     const bool cl = clique_on && leaf_is_clique(S.t.box, S.t.P + l, r2);
@@ -116,9 +115,10 @@ __global__ void __launch_bounds__(kClusterBlock)
 k_cluster_hook(const ClusterSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, float r2, int clique_on, uint32_t* __restrict__ parent_all,
                unsigned long long* __restrict__ stats)
 {
-    const ClusterSeg& S = segs[block_seg[blockIdx.x]];
+    uint32_t j;
+    const ClusterSeg& S = block_record<kClusterBlock>(segs, block_seg, j);
+    j += threadIdx.x;
     const SearchTree t = S.t;
-    const uint32_t j = (blockIdx.x - S.block0) * kClusterBlock + threadIdx.x;
     uint32_t cnt[6] = {0u, 0u, 0u, 0u, 0u, 0u};
     if (j < t.Mf) {
         uint32_t* parent = parent_all + S.fbase;
@@ -153,8 +153,9 @@ __global__ void __launch_bounds__(kClusterBlock)
 k_cluster_flatten(const ClusterSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, const uint32_t* __restrict__ parent, uint32_t* __restrict__ root,
                   uint32_t* __restrict__ size, uint32_t* __restrict__ minidx)
 {
-    const ClusterSeg& S = segs[block_seg[blockIdx.x]];
-    const uint32_t j = (blockIdx.x - S.block0) * kClusterBlock + threadIdx.x;
+    uint32_t j;
+    const ClusterSeg& S = block_record<kClusterBlock>(segs, block_seg, j);
+    j += threadIdx.x;
     const bool active = j < S.t.Mf;
     uint32_t r = 0xffffffffu, oi = 0xffffffffu;
     if (active) {
@@ -178,9 +179,9 @@ __global__ void __launch_bounds__(kClusterBlock)
 k_cluster_roots(const ClusterSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, const uint32_t* __restrict__ root, const uint32_t* __restrict__ size,
                 uint32_t min_size, uint32_t max_size, uint8_t* __restrict__ keep, unsigned long long* __restrict__ counts)
 {
-    const uint32_t si = block_seg[blockIdx.x];
-    const ClusterSeg& S = segs[si];
-    const uint32_t j = (blockIdx.x - S.block0) * kClusterBlock + threadIdx.x;
+    uint32_t j, si;
+    const ClusterSeg& S = block_record<kClusterBlock>(segs, block_seg, j, &si);
+    j += threadIdx.x;
     uint32_t k = 0, n = 0;
     if (j < S.t.Mf) {
         const uint32_t sz = size[S.fbase + j];
@@ -226,9 +227,9 @@ __global__ void __launch_bounds__(kClusterBlock)
 k_cluster_labels(const ClusterSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, const uint32_t* __restrict__ root, const int32_t* __restrict__ cid,
                  const uint64_t* __restrict__ coff, int32_t* __restrict__ labels, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ cursor)
 {
-    const uint32_t si = block_seg[blockIdx.x];
-    const ClusterSeg& S = segs[si];
-    const uint32_t j = (blockIdx.x - S.block0) * kClusterBlock + threadIdx.x;
+    uint32_t j, si;
+    const ClusterSeg& S = block_record<kClusterBlock>(segs, block_seg, j, &si);
+    j += threadIdx.x;
     int32_t c = -1;
     uint32_t oi = 0;
     if (j < S.t.Mf) {
@@ -354,11 +355,9 @@ hipError_t cluster_roots(const ClusterSeg* segs, const uint32_t* block_seg, uint
 
 size_t cluster_temp_bytes(size_t n_clusters, size_t n_segs)
 {
-    size_t a = 0, b = 0;
-    (void)rocprim::segmented_radix_sort_pairs(nullptr, a, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                              (unsigned)n_clusters, (unsigned)n_segs, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, 64);
+    size_t b = 0;
     (void)rocprim::exclusive_scan(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, n_clusters + 1, rocprim::plus<uint32_t>());
-    return std::max<size_t>(std::max(a, b), 16);
+    return std::max(seg_sort_pairs_temp_bytes(n_clusters, n_segs), b);
 }
 
 hipError_t cluster_number(const uint8_t* keep, const uint32_t* pos, size_t total, const uint32_t* size, const uint32_t* minidx, uint32_t n_clusters,
@@ -368,8 +367,7 @@ hipError_t cluster_number(const uint8_t* keep, const uint32_t* pos, size_t total
 {
     if (!n_clusters) return hipSuccess;
     k_cluster_compact<<<dim3(grid_for(total)), dim3(kClusterBlock), 0, s>>>(keep, pos, total, size, minidx, keys, vals);
-    hipError_t e = rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, vals, vals_sorted, (unsigned)n_clusters, (unsigned)n_segs, coff, coff + 1,
-                                                       0, 64, s);
+    hipError_t e = seg_sort_pairs_u64(keys, keys_sorted, vals, vals_sorted, n_clusters, n_segs, coff, temp, temp_bytes, s);
     if (e != hipSuccess) return e;
     k_cluster_assign<<<dim3(grid_for((size_t)n_clusters + 1)), dim3(kClusterBlock), 0, s>>>(keys_sorted, vals_sorted, n_clusters, coff, n_segs, cid, csize, cfirst, cseg,
                                                                                              cchunks);

@@ -18,8 +18,7 @@
 // points are read in place in its own order, and the record (same layout as the plane record) holds the normal equations weighted per correspondence by
 // the inverse of the two regularised covariances the normals imply; the update kernel's plane instantiation serves it unchanged.
 #include "ltm_kernels_common.h"
-#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves
-#include <rocprim/device/device_segmented_radix_sort.hpp>
+#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves, seg_order_by_code
 #include <cfloat>
 #include <climits>
 namespace ltm {
@@ -161,48 +160,12 @@ __device__ bool plane_step(const double* ata, const double* atb, const double* o
 } // namespace
 
 // -------------------------------------------------------------------------------------------------- source order
-__global__ void __launch_bounds__(kIcpBlock)
-k_icp_source_keys(const IcpPair* __restrict__ pairs, const uint32_t* __restrict__ block_pair, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
+// each source once into the code order of its target's frame (the shared order of ltm_search_walk.h, kIcpBlock points per workgroup)
+hipError_t icp_order_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
+                             uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes, hipStream_t s)
 {
-    const IcpPair& P = pairs[block_pair[blockIdx.x]];
-    const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
-    if (local >= P.n) return;
-    const float4 p = P.src[local];
-    keys[P.first + local] = search_key(P.f, p.x, p.y, p.z);
-    idx[P.first + local] = local;
-}
-__global__ void __launch_bounds__(kIcpBlock)
-k_icp_gather_sources(const IcpPair* __restrict__ pairs, const uint32_t* __restrict__ block_pair, const uint32_t* __restrict__ order, float4* __restrict__ sorted)
-{
-    const IcpPair& P = pairs[block_pair[blockIdx.x]];
-    const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
-    if (local >= P.n) return;
-    const uint32_t j = order[P.first + local];
-    if (j < P.n) sorted[P.first + local] = P.src[j];
-}
-hipError_t icp_source_keys(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s)
-{
-    if (!n_blocks) return hipSuccess;
-    k_icp_source_keys<<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, block_pair, keys, idx);
-    return hipGetLastError();
-}
-size_t icp_sort_temp_bytes(size_t total, size_t n_pairs)
-{
-    size_t b = 0;
-    (void)rocprim::segmented_radix_sort_pairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                              (unsigned)total, (unsigned)n_pairs, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, 64);
-    return std::max<size_t>(b, 16);
-}
-hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
-                            const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes,
-                            hipStream_t s)
-{
-    if (!n_blocks || !total) return hipSuccess;
-    hipError_t e = rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, idx, order, (unsigned)total, (unsigned)n_pairs, offsets, offsets + 1,
-                                                       0, 64, s);
-    if (e != hipSuccess) return e;
-    k_icp_gather_sources<<<dim3(n_blocks), dim3(kIcpBlock), 0, s>>>(pairs, block_pair, order, sorted);
-    return hipGetLastError();
+    static_assert(kIcpBlock == kSegBlock, "the correspondence grid and the source order share one owner table");
+    return seg_order_by_code<IcpPair, 1>(pairs, block_pair, n_blocks, n_pairs, offsets, total, keys, keys_sorted, idx, order, sorted, temp, temp_bytes, s);
 }
 
 // ------------------------------------------------------------------------------------------------ correspondences
@@ -221,11 +184,11 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
     constexpr bool SCORE = MODE == kIcpScore;
     constexpr int NP = (MODE == kIcpPlane || MODE == kIcpGicp) ? kIcpPlanePartial : kIcpPartial;      // doubles per record
     __shared__ double lds[kIcpBlock / 64][NP];
-    const uint32_t pi = block_pair[blockIdx.x];
+    uint32_t local, pi;
+    const IcpPair& P = block_record<kIcpBlock>(pairs, block_pair, local, &pi);
+    local += threadIdx.x;
     const IcpState& S = st[pi];
     if (!SCORE && S.done) return;      // the whole workgroup: the flag was written by an earlier launch
-    const IcpPair& P = pairs[pi];
-    const uint32_t local = (blockIdx.x - P.block0) * kIcpBlock + threadIdx.x;
     constexpr int NV = SCORE ? 2 : NP;
     double v[NP];
 #pragma unroll
@@ -375,7 +338,7 @@ k_icp_update(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, const
     const IcpPair& P = pairs[pi];
     if (threadIdx.x < (unsigned)NP) {
         double a = 0.0;
-        for (uint32_t b = 0; b < P.n_blocks; ++b) a += partials[(size_t)(P.block0 + b) * NP + threadIdx.x];      // block order
+        for (uint32_t b = 0; b < P.span.n_blocks; ++b) a += partials[(size_t)(P.span.block0 + b) * NP + threadIdx.x];      // block order
         m[threadIdx.x] = a;
     }
     __syncthreads();
@@ -452,7 +415,7 @@ k_icp_fitness(const IcpPair* __restrict__ pairs, IcpState* __restrict__ st, cons
     if (threadIdx.x < 2) {
         const int c = threadIdx.x == 0 ? 0 : 16;
         double a = 0.0;
-        for (uint32_t b = 0; b < P.n_blocks; ++b) a += partials[(size_t)(P.block0 + b) * kIcpPartial + c];
+        for (uint32_t b = 0; b < P.span.n_blocks; ++b) a += partials[(size_t)(P.span.block0 + b) * kIcpPartial + c];
         m[threadIdx.x] = a;
     }
     __syncthreads();

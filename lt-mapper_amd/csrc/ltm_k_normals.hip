@@ -3,8 +3,8 @@
 // (gfx950 / CDNA4, wave64; part of libltm_hip.so -- shared definitions in ltm_kernels_common.h, launch wrappers declared in ltm_kernels.h)
 //
 // One thread per finite target point, in the index's Morton order: the lanes of a wavefront are neighbours in space and walk the same part of the box
-// tree, and the kNN seed is the point's own stored code (no query sort).  All indices of a call go through ONE launch; a per-block table names the index
-// (as ltm_k_icp.hip does for its pairs), so a workgroup never straddles two indices.  The neighbour lists hold (d2, target index, sorted position) in
+// tree, and the kNN seed is the point's own stored code (no query sort).  All indices of a call go through ONE launch over the batch's owner
+// table (ltm_block_table.h).  The neighbour lists hold (d2, target index, sorted position) in
 // ascending (d2, index) order -- in registers for k <= 16, in LDS [slot][lane] with one wavefront per workgroup above -- and the moments are summed in
 // that order in double, so a normal depends on its index alone: no atomics, nothing that depends on the walk or on the rest of the batch.
 #include "ltm_kernels_common.h"
@@ -93,9 +93,10 @@ template <int KT>
 __global__ void __launch_bounds__(kNormalsBlockReg)
 k_normals_reg(const NormalsSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, int k)
 {
-    const NormalsSeg& S = segs[block_seg[blockIdx.x]];
+    uint32_t j0;
+    const NormalsSeg& S = block_record<kNormalsBlockReg>(segs, block_seg, j0);
+    j0 += threadIdx.x;
     const SearchTree t = S.t;
-    const uint32_t j0 = (blockIdx.x - S.block0) * kNormalsBlockReg + threadIdx.x;
     if (j0 >= t.Mf) return;
     const int kk = (int)min((uint32_t)k, t.Mf);
     if (kk < 3) { S.out[j0] = nan4(); return; }
@@ -143,10 +144,11 @@ k_normals_lds(const NormalsSeg* __restrict__ segs, const uint32_t* __restrict__ 
     __shared__ float sd[kNormalsMaxK][kNormalsBlockLds];
     __shared__ int si[kNormalsMaxK][kNormalsBlockLds];
     __shared__ uint32_t sj[kNormalsMaxK][kNormalsBlockLds];
-    const NormalsSeg& S = segs[block_seg[blockIdx.x]];
+    uint32_t j0;
+    const NormalsSeg& S = block_record<kNormalsBlockLds>(segs, block_seg, j0);
+    j0 += threadIdx.x;
     const SearchTree t = S.t;
     const int lane = (int)threadIdx.x;
-    const uint32_t j0 = (blockIdx.x - S.block0) * kNormalsBlockLds + threadIdx.x;
     if (j0 >= t.Mf) return;
     const int kk = (int)min((uint32_t)min(k, kNormalsMaxK), t.Mf);
     if (kk < 3) { S.out[j0] = nan4(); return; }

@@ -14,7 +14,7 @@
 // evaluation is within 3e-7 relative of the exact value), is STRICTLY above the current k-th distance (kNN) or not below r2 (radius): no
 // point that could enter the result, a tie included, is ever skipped.  Ties are ordered by the smaller target index.
 #include "ltm_kernels_common.h"
-#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves
+#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves, seg_order_by_code
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -102,8 +102,7 @@ hipError_t search_tree_boxes(const float4* sorted_pts, uint32_t Mf, uint32_t L, 
 
 // ------------------------------------------------------------------------------------------------- batched build
 // One index per keyframe of a scan set (ltm_search_build_scanset), the stages of the build above in segmented form: the grid of the first three kernels is
-// over chunks of kSearchSegChunk points, a per-block table names the segment (as ltm_k_icp.hip does for its pairs), so a workgroup never straddles two
-// keyframes and its segment record is uniform.
+// over chunks of kSearchSegChunk points of the batch's owner table (ltm_block_table.h), the order by code is the shared one of ltm_search_walk.h.
 static constexpr int kSegPerThread = kSearchSegChunk / kBlock;
 __global__ void __launch_bounds__(kBlock)
 k_search_bbox_seg_init(uint32_t* __restrict__ b, size_t n_words)
@@ -115,9 +114,8 @@ __global__ void __launch_bounds__(kBlock)
 k_search_bbox_seg(const SearchSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, uint32_t* __restrict__ out)
 {
     __shared__ uint32_t scnt[kBlock / 64];
-    const uint32_t si = block_seg[blockIdx.x];
-    const SearchSeg& S = segs[si];
-    const uint32_t base = (blockIdx.x - S.block0) * kSearchSegChunk;
+    uint32_t base, si;
+    const SearchSeg& S = block_record<kSearchSegChunk>(segs, block_seg, base, &si);
     BoxAcc box;
     uint32_t cnt = 0;
 #pragma unroll
@@ -147,59 +145,22 @@ hipError_t search_bbox_seg(const SearchSeg* segs, size_t n_segs, const uint32_t*
     if (n_blocks) k_search_bbox_seg<<<dim3(n_blocks), dim3(kBlock), 0, s>>>(segs, block_seg, bbox8);
     return hipGetLastError();
 }
-__global__ void __launch_bounds__(kBlock)
-k_search_keys_seg(const SearchSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
-{
-    const SearchSeg& S = segs[block_seg[blockIdx.x]];
-    const uint32_t base = (blockIdx.x - S.block0) * kSearchSegChunk;
-#pragma unroll
-    for (int it = 0; it < kSegPerThread; ++it) {
-        const uint32_t local = base + it * kBlock + threadIdx.x;
-        if (local >= S.n) continue;
-        const float4 p = S.src[local];
-        keys[S.first + local] = search_key(S.f, p.x, p.y, p.z);
-        idx[S.first + local] = local;
-    }
-}
-hipError_t search_keys_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s)
-{
-    if (!n_blocks) return hipSuccess;
-    k_search_keys_seg<<<dim3(n_blocks), dim3(kBlock), 0, s>>>(segs, block_seg, keys, idx);
-    return hipGetLastError();
-}
-// sorted[first + j] = src[order[first + j]] for the Mf finite points of every segment (they sort in front: a non-finite point's code is ~0)
-__global__ void __launch_bounds__(kBlock)
-k_search_gather_seg(const SearchSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, const uint32_t* __restrict__ order, float4* __restrict__ sorted)
-{
-    const SearchSeg& S = segs[block_seg[blockIdx.x]];
-    const uint32_t base = (blockIdx.x - S.block0) * kSearchSegChunk;
-#pragma unroll
-    for (int it = 0; it < kSegPerThread; ++it) {
-        const uint32_t local = base + it * kBlock + threadIdx.x;
-        if (local >= S.Mf) continue;
-        const uint32_t j = order[S.first + local];
-        if (j < S.n) sorted[S.first + local] = S.src[j];
-    }
-}
-size_t search_sort_seg_temp_bytes(size_t total, size_t n_segs)
+size_t seg_sort_pairs_temp_bytes(size_t n, size_t n_segs)
 {
     size_t b = 0;
     (void)rocprim::segmented_radix_sort_pairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                              (unsigned)total, (unsigned)n_segs, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, 64);
+                                              (unsigned)n, (unsigned)n_segs, (const uint64_t*)nullptr, (const uint64_t*)nullptr, 0, 64);
     return std::max<size_t>(b, 16);
 }
-hipError_t search_sort_gather_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, size_t n_segs, const uint64_t* offsets, size_t total,
-                                  const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp,
-                                  size_t temp_bytes, hipStream_t s)
+hipError_t seg_sort_pairs_u64(const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* vals, uint32_t* vals_sorted, size_t n, size_t n_segs,
+                              const uint64_t* offsets, void* temp, size_t temp_bytes, hipStream_t s)
 {
-    if (!n_blocks || !total) return hipSuccess;
-    // the full 63-bit code leaves no room for a segment prefix in a 64-bit key: a segmented sort (not necessarily stable -- equal codes may change places,
-    // which no query result depends on)
-    hipError_t e = rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, idx, order, (unsigned)total, (unsigned)n_segs, offsets, offsets + 1,
-                                                       0, 64, s);
-    if (e != hipSuccess) return e;
-    k_search_gather_seg<<<dim3(n_blocks), dim3(kBlock), 0, s>>>(segs, block_seg, order, sorted);
-    return hipGetLastError();
+    return rocprim::segmented_radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, vals, vals_sorted, (unsigned)n, (unsigned)n_segs, offsets, offsets + 1, 0, 64, s);
+}
+hipError_t search_order_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, size_t n_segs, const uint64_t* offsets, size_t total,
+                            uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes, hipStream_t s)
+{
+    return seg_order_by_code<SearchSeg, kSegPerThread>(segs, block_seg, n_blocks, n_segs, offsets, total, keys, keys_sorted, idx, order, sorted, temp, temp_bytes, s);
 }
 // all box trees in one launch, one workgroup per segment: the leaf boxes, then the inner levels bottom-up with a barrier between two levels (a level reads
 // what the same workgroup wrote one level below).  The same min / max over the same leaves as k_search_leaf_boxes / k_search_inner_boxes.
@@ -208,7 +169,7 @@ __global__ void __launch_bounds__(kTreeBlock)
 k_search_tree_boxes_seg(const SearchSeg* __restrict__ segs, const float4* __restrict__ sorted, float4* __restrict__ box_all)
 {
     const SearchSeg& S = segs[blockIdx.x];
-    const uint32_t Mf = S.Mf, L = S.L, P = S.P;
+    const uint32_t Mf = S.n_gather, L = S.L, P = S.P;
     if (!P) return;
     const float4* __restrict__ pts = sorted + S.first;
     float4* box = box_all + S.box0;

@@ -3,9 +3,9 @@
 // for ALL the windows of a batch in one launch.
 // (gfx950 / CDNA4, wave64; part of libltm_hip.so -- shared definitions in ltm_kernels_common.h, launch wrappers declared in ltm_kernels.h)
 //
-// One thread per output point, one float4 load and one float4 store: a streaming kernel, 32 B / point.  The grid is over the concatenated windows; a
-// per-block table names the piece (window, source keyframe, affine) a workgroup belongs to, as ltm_k_icp.hip does for its pairs, so the piece's record
-// is uniform over the workgroup and its loads are scalar.  The host lays the pieces out from the scan set's host offsets: no size is read back.
+// One thread per output point, one float4 load and one float4 store: a streaming kernel, 32 B / point.  The grid is over the concatenated windows; the
+// batch's owner table (ltm_block_table.h) names the piece (window, source keyframe, affine) a workgroup belongs to, so the piece's record is uniform
+// over the workgroup and its loads are scalar.  The host lays the pieces out from the scan set's host offsets: no size is read back.
 #include "ltm_kernels_common.h"
 namespace ltm {
 
@@ -13,8 +13,9 @@ __global__ void __launch_bounds__(kBlock)
 k_submap_gather(const float4* __restrict__ scans, const SubmapPiece* __restrict__ pieces, const uint32_t* __restrict__ block_piece,
                 const float* __restrict__ affines12, float4* __restrict__ out)
 {
-    const SubmapPiece P = pieces[block_piece[blockIdx.x]];
-    const uint32_t local = (blockIdx.x - P.block0) * kBlock + threadIdx.x;
+    uint32_t local;
+    const SubmapPiece P = block_record<kBlock>(pieces, block_piece, local);
+    local += threadIdx.x;
     if (local >= P.n) return;
     const float* __restrict__ t = affines12 + (size_t)12 * P.affine;
     const float4 p = scans[P.src + local];

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "ltm_block_table.h"      // BlockSpan
 
 namespace ltm {
 
@@ -287,20 +288,25 @@ size_t     radius_sort_temp_bytes(size_t total, size_t n);
 hipError_t radius_fill(const float4* query, size_t n, const uint32_t* order, SearchTree t, float r2, const uint64_t* full_off, uint64_t total_full,
                        const uint64_t* out_off, uint64_t* pairs, uint64_t* pairs_sorted, int32_t* out_idx, float* out_d2, void* temp, size_t temp_bytes, hipStream_t s);
 
-// batched build (ltm_search_build_scanset): one segment per keyframe.  src: the keyframe's points, n of them; its slice [first, first + n) of the batch's
-// keys / order / sorted points; its workgroups [block0, block0 + ceil(n / kSearchSegChunk)) of the segmented kernels; f, Mf, L, P and box0 (first float4 of
-// its tree in the batch's box array) are filled in by the host once the boxes are known
+// ---- batches (DESIGN.md "batches"): every record struct below has a BlockSpan `span`, its workgroups in the launches over the batch's owner table ----
+// A cloud to be put in Morton order under a frame: src, n points; its slice [first, first + n) of the batch's keys / order / sorted points, of which the
+// first n_gather sorted positions are gathered (the finite points sort in front: a non-finite point's code is ~0)
+struct SegSource { SearchFrame f; const float4* src; uint64_t first; uint32_t n, n_gather; BlockSpan span; };
+// every segment sorted by (key bits 0..64, not stable); offsets: n_segs + 1 slice bounds
+size_t     seg_sort_pairs_temp_bytes(size_t n, size_t n_segs);
+hipError_t seg_sort_pairs_u64(const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* vals, uint32_t* vals_sorted, size_t n, size_t n_segs,
+                              const uint64_t* offsets, void* temp, size_t temp_bytes, hipStream_t s);
+
+// batched build (ltm_search_build_scanset): one segment per keyframe, kSearchSegChunk points per workgroup.  n_gather is Mf, the number of finite points;
+// f, n_gather, L, P and box0 (first float4 of its tree in the batch's box array) are filled in by the host once the boxes are known
 static constexpr int kSearchSegChunk = 1024;    // points per workgroup of the segmented build kernels
-struct SearchSeg { SearchFrame f; const float4* src; uint64_t first, box0; uint32_t n, Mf, L, P, block0, pad; };
+struct SearchSeg : SegSource { uint64_t box0; uint32_t L, P; };
 // bbox8: 8 words per segment (initialised here): box of its finite points as ordered keys, word 6 their number; one commit per workgroup and segment
 hipError_t search_bbox_seg(const SearchSeg* segs, size_t n_segs, const uint32_t* block_seg, uint32_t n_blocks, uint32_t* bbox8, hipStream_t s);
-// keys[first + j] = code of point j under its segment's frame (non-finite: ~0), idx[first + j] = j
-hipError_t search_keys_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s);
-size_t     search_sort_seg_temp_bytes(size_t total, size_t n_segs);
-// every segment sorted by code (offsets: n_segs + 1 slice bounds), then sorted[first + j] = src[order[first + j]] for j < Mf
-hipError_t search_sort_gather_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, size_t n_segs, const uint64_t* offsets, size_t total,
-                                  const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp,
-                                  size_t temp_bytes, hipStream_t s);
+// keys[first + j] = code of point j under its segment's frame (non-finite: ~0), idx[first + j] = j; every segment sorted by code (offsets: n_segs + 1
+// slice bounds; temp: seg_sort_pairs_temp_bytes(total, n_segs)); then sorted[first + j] = src[order[first + j]] for j < n_gather
+hipError_t search_order_seg(const SearchSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, size_t n_segs, const uint64_t* offsets, size_t total,
+                            uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes, hipStream_t s);
 // the box trees of all segments in one launch (one workgroup per segment): box + box0 of a segment is what search_tree_boxes gives for its points
 hipError_t search_tree_boxes_seg(const SearchSeg* segs, size_t n_segs, const float4* sorted, float4* box, hipStream_t s);
 
@@ -308,8 +314,8 @@ hipError_t search_tree_boxes_seg(const SearchSeg* segs, size_t n_segs, const flo
 static constexpr int kNormalsBlockReg = 256;    // target points per workgroup, lists in registers (k <= 16)
 static constexpr int kNormalsBlockLds = 64;     // ... lists in LDS (16 < k <= 64): one wavefront
 static constexpr int kNormalsMaxK = 64;
-// one index of the batch: its tree, where its Mf normals go (aligned with t.pts), the viewpoint, and its workgroups [block0, block0 + ceil(Mf / block))
-struct NormalsSeg { SearchTree t; float4* out; double vp[3]; uint32_t block0, pad; };
+// one index of the batch: its tree, where its Mf normals go (aligned with t.pts), the viewpoint; normals_block(k) target points per workgroup
+struct NormalsSeg { SearchTree t; float4* out; double vp[3]; BlockSpan span; };
 int        normals_block(int k);                // target points per workgroup of the kernel that k selects
 // out[j] = (nx, ny, nz, curvature) of target point t.pts[j] from its min(k, Mf) nearest target points, for every index of the table in one launch
 hipError_t estimate_normals(const NormalsSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, int k, hipStream_t s);
@@ -318,8 +324,8 @@ hipError_t estimate_normals(const NormalsSeg* segs, const uint32_t* block_seg, u
 static constexpr int kClusterBlock = 256;       // finite target points per workgroup of the per-point kernels
 static constexpr int kClusterChunk = 256;       // points per partial sum of a cluster's centroid
 // one listed index of the batch: its tree, its slice [fbase, fbase + Mf) of the batch's per-finite-point arrays (parent, root, size, ...), its slice
-// [tbase, tbase + n_target) of the labels, log2 of its tree's P and its workgroups [block0, block0 + ceil(Mf / kClusterBlock))
-struct ClusterSeg { SearchTree t; uint64_t fbase, tbase; uint32_t n_target, block0, logP, pad; };
+// [tbase, tbase + n_target) of the labels, log2 of its tree's P
+struct ClusterSeg { SearchTree t; uint64_t fbase, tbase; uint32_t n_target, logP; BlockSpan span; };
 // init (every position its own root, clique leaves united), hook pass, flatten (root[], size and lowest original index per root); stats6 += pairs tested,
 // edges found, leaves visited, clique leaves among them, clique early exits, hook retries
 hipError_t cluster_hook(const ClusterSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, float r2, int clique_on, uint32_t* parent, uint32_t* root,
@@ -346,8 +352,8 @@ hipError_t cluster_finish(const ClusterSeg* segs, const uint64_t* keys_sorted, c
                           int32_t* idx_out, uint32_t* sizes_out, int32_t* first_out, float* box_out, double* centroid_out, uint64_t* offsets_out, hipStream_t s);
 
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
-// one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; workgroups [block0, block0 + ceil(n / 256))
-struct SubmapPiece { uint64_t src, dst; uint32_t n, block0, affine, pad; };
+// one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; 256 points per workgroup
+struct SubmapPiece { uint64_t src, dst; uint32_t n, affine; BlockSpan span; };
 hipError_t submap_gather(const float4* scans, const SubmapPiece* pieces, const uint32_t* block_piece, uint32_t n_blocks, const float* affines12, float4* out,
                          hipStream_t s);
 
@@ -356,20 +362,17 @@ static constexpr int kIcpBlock = 256;           // source points per workgroup o
 static constexpr int kIcpPartial = 17;          // doubles per partial record: count, sum p (3), sum q (3), sum p q^T (9, row-major), sum d2
 static constexpr int kIcpPlanePartial = 29;     // point-to-plane: count, A^T A (21, upper triangle row-major), A^T b (6), sum d2
 enum IcpMode { kIcpPoint = 0, kIcpScore = 1, kIcpPlane = 2, kIcpGicp = 3 };      // kIcpGicp: records of kIcpPlanePartial doubles (sum A^T M A, sum A^T M d)
-// one pair of the batch: the target's tree and frame, the source as given (src, n points), its slice [first, first + n) of the batch's sorted sources and
-// its workgroups [block0, block0 + n_blocks) of the correspondence grid; o: the origin the moments are taken about (the corner of the target's frame);
-// nrm: the target's normals, aligned with t.pts (point-to-plane and generalized).  Generalized ICP reads its sources in place: src is then the source
-// index's own points (its finite points in its own code order, n = its Mf), snrm their normals, and `first` is not used
-struct IcpPair { SearchTree t; SearchFrame f; const float4* src; double o[3]; uint64_t first; uint32_t n, block0, n_blocks, pad; const float4* nrm; const float4* snrm; };
+// one pair of the batch: the source as given under the target's frame (SegSource; n_gather = n, kIcpBlock points per workgroup), the target's tree; o: the
+// origin the moments are taken about (the corner of the target's frame); nrm: the target's normals, aligned with t.pts (point-to-plane and generalized).
+// Generalized ICP reads its sources in place: src is then the source index's own points (its finite points in its own code order, n = its Mf), snrm
+// their normals, and `first` is not used
+struct IcpPair : SegSource { SearchTree t; double o[3]; const float4* nrm; const float4* snrm; };
 // what k_icp_update keeps per pair between iterations (T: rows 0..2 of the accumulated transform, row-major)
 struct IcpState { double T[12]; double prev_mse, last_mse, fitness; int32_t iterations, state, converged, done; uint32_t n_corr, pad; };
-// codes of every source point under its target's frame (keys) and its position in its source (idx); grid over the blocks of block_pair
-hipError_t icp_source_keys(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, uint64_t* keys, uint32_t* idx, hipStream_t s);
-size_t     icp_sort_temp_bytes(size_t total, size_t n_pairs);
-// every source sorted by code (offsets: n_pairs + 1 slice bounds), then sorted[first + j] = src[order[first + j]]
-hipError_t icp_sort_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
-                            const uint64_t* keys, uint64_t* keys_sorted, const uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes,
-                            hipStream_t s);
+// codes of every source point under its target's frame (keys) and its position in its source (idx), every source sorted by code (offsets: n_pairs + 1
+// slice bounds; temp: seg_sort_pairs_temp_bytes(total, n_pairs)), then sorted[first + j] = src[order[first + j]]
+hipError_t icp_order_sources(const IcpPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, size_t n_pairs, const uint64_t* offsets, size_t total,
+                             uint64_t* keys, uint64_t* keys_sorted, uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes, hipStream_t s);
 // one record per workgroup.  mode kIcpPoint: kIcpPartial doubles, correspondences within max_corr2 of the pairs not done yet; kIcpScore: count and sum d2
 // of every finite point of every pair, no limit (in a record of kIcpPartial); kIcpPlane: kIcpPlanePartial doubles, the normal equations of the
 // correspondences within max_corr2 whose target normal is finite; kIcpGicp: kIcpPlanePartial doubles, the weighted normal equations of the correspondences
@@ -381,6 +384,8 @@ hipError_t icp_correspond(const IcpPair* pairs, const IcpState* st, const uint32
 hipError_t icp_update(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, int max_iterations, double transformation_epsilon,
                       double euclidean_fitness_epsilon, double* trace, uint32_t* unfinished, hipStream_t s, int plane = 0);
 hipError_t icp_fitness(const IcpPair* pairs, IcpState* st, size_t n_pairs, const double* partials, hipStream_t s);
+static_assert(sizeof(SearchSeg) == 80 && sizeof(NormalsSeg) == 88 && sizeof(ClusterSeg) == 80 && sizeof(SubmapPiece) == 32 && sizeof(IcpPair) == 152,
+              "the batch records keep their sizes");
 
 // ---- scan context (ltm_k_scancontext.hip; Scancontext.cpp:69-324) ----
 struct ScGeom { double lidar_height, max_radius; int R, S; };      // rings x sectors

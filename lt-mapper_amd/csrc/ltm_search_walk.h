@@ -1,7 +1,7 @@
 // ltm_search_walk.h -- the device side of the search index that more than one kernel unit uses: the Morton code of a point under the index's frame,
-// the order of (distance, index) pairs, the lower bound of the distance to a node's box, the stackless walk of the implicit box tree and the kNN
-// seed (the index itself is described in ltm_k_search.hip, which builds it; ltm_k_icp.hip walks it for its correspondences).  Everything has
-// internal linkage: each unit that includes this gets its own copies, inlined into its kernels.
+// the order of (distance, index) pairs, the lower bound of the distance to a node's box, the stackless walk of the implicit box tree, the kNN seed
+// and the segmented order by code of the batched builds (the index itself is described in ltm_k_search.hip, which builds it; ltm_k_icp.hip walks it
+// for its correspondences).  Everything has internal linkage: each unit that includes this gets its own copies, inlined into its kernels.
 #pragma once
 #include "ltm_kernels_common.h"
 namespace ltm {
@@ -69,6 +69,53 @@ __device__ __forceinline__ void seed_leaves(const SearchTree& t, uint64_t qkey, 
     if (start + kk > t.Mf) start = t.Mf - kk;
     a = start / kSearchLeaf;
     b = (start + kk - 1) / kSearchLeaf;
+}
+
+// ---------------------------------------------------------------------------------------- segmented order by code
+// "Every record's points in Morton order under that record's frame" ("batches"): codes, one segmented sort, gather.  Rec is a SegSource; a
+// workgroup of kSegBlock threads takes kSegBlock * PER_THREAD points of one record.  keys[first + j] = code of point j (non-finite: ~0), idx[first + j] = j
+static constexpr int kSegBlock = 256;
+template <class Rec, int PER_THREAD>
+__global__ void __launch_bounds__(kSegBlock)
+k_seg_keys(const Rec* __restrict__ recs, const uint32_t* __restrict__ owner, uint64_t* __restrict__ keys, uint32_t* __restrict__ idx)
+{
+    uint32_t base;
+    const Rec& S = block_record<kSegBlock * PER_THREAD>(recs, owner, base);
+#pragma unroll
+    for (int it = 0; it < PER_THREAD; ++it) {
+        const uint32_t local = base + it * kSegBlock + threadIdx.x;
+        if (local >= S.n) continue;
+        const float4 p = S.src[local];
+        keys[S.first + local] = search_key(S.f, p.x, p.y, p.z);
+        idx[S.first + local] = local;
+    }
+}
+// sorted[first + j] = src[order[first + j]] for the first n_gather sorted positions of every record
+template <class Rec, int PER_THREAD>
+__global__ void __launch_bounds__(kSegBlock)
+k_seg_gather(const Rec* __restrict__ recs, const uint32_t* __restrict__ owner, const uint32_t* __restrict__ order, float4* __restrict__ sorted)
+{
+    uint32_t base;
+    const Rec& S = block_record<kSegBlock * PER_THREAD>(recs, owner, base);
+#pragma unroll
+    for (int it = 0; it < PER_THREAD; ++it) {
+        const uint32_t local = base + it * kSegBlock + threadIdx.x;
+        if (local >= S.n_gather) continue;
+        const uint32_t j = order[S.first + local];
+        if (j < S.n) sorted[S.first + local] = S.src[j];
+    }
+}
+// the full 63-bit code leaves no room for a record prefix in a 64-bit key: a segmented sort (not stable: equal codes may change places, no result depends on it)
+template <class Rec, int PER_THREAD>
+hipError_t seg_order_by_code(const Rec* recs, const uint32_t* owner, uint32_t n_blocks, size_t n_recs, const uint64_t* offsets, size_t total, uint64_t* keys,
+                             uint64_t* keys_sorted, uint32_t* idx, uint32_t* order, float4* sorted, void* temp, size_t temp_bytes, hipStream_t s)
+{
+    if (!n_blocks || !total) return hipSuccess;
+    k_seg_keys<Rec, PER_THREAD><<<dim3(n_blocks), dim3(kSegBlock), 0, s>>>(recs, owner, keys, idx);
+    hipError_t e = seg_sort_pairs_u64(keys, keys_sorted, idx, order, total, n_recs, offsets, temp, temp_bytes, s);
+    if (e != hipSuccess) return e;
+    k_seg_gather<Rec, PER_THREAD><<<dim3(n_blocks), dim3(kSegBlock), 0, s>>>(recs, owner, order, sorted);
+    return hipGetLastError();
 }
 
 } // namespace

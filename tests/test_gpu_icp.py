@@ -82,6 +82,23 @@ def test_tree_and_block_edges(gpu_ctx):
         i.close()
 
 
+def test_source_block_edges_in_one_batch_are_the_pairs_alone(gpu_ctx):
+    """sources on both sides of one and of two 256-point workgroups against one 1025-point target: in one batch (their spans of the block table lie one
+    behind the other) each gives, byte for byte, what the same pair gives alone"""
+    rng = np.random.default_rng(37)
+    target = rng.uniform(-8.0, 8.0, (1025, 3)).astype(np.float32)
+    sources = []
+    for k, ns in enumerate((256, 257, 512, 513)):
+        src = target[rng.choice(1025, ns, replace=False)].astype(np.float64) + rng.normal(0.0, 0.01, (ns, 3))
+        sources.append(fx.apply(np.linalg.inv(fx.rigid(2.0 + 0.3 * k, (0.05, -0.04, 0.03), pitch_deg=1.0)), src))
+    with gpu_ctx.search_index(target) as idx:
+        res, tr = gpu_ctx.icp_align([(idx, s) for s in sources], trace=True)
+        for k, s in enumerate(sources):
+            alone, ta = gpu_ctx.icp_align([(idx, s)], trace=True)
+            assert alone[0].tobytes() == res[k].tobytes() and ta[0].tobytes() == tr[k].tobytes(), len(s)
+            assert res[k]["converged"] == 1 and res[k]["iterations"] >= 1 and res[k]["n_corr"] == len(s), len(s)
+
+
 def _is_rotation(T):
     R = T[:3, :3]
     return np.isfinite(T).all() and np.abs(R @ R.T - np.eye(3)).max() < 1e-12 and abs(np.linalg.det(R) - 1.0) < 1e-12 and (T[3] == (0, 0, 0, 1)).all()

@@ -249,6 +249,39 @@ def test_batched_build_answers_like_the_single_build(gpu_ctx):
     scans.free()
 
 
+CHUNK_SIZES = [1023, 0, 1024, 2049]      # both sides of the 1024-point chunk of the segmented build kernels, an empty keyframe between, and past two chunks
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_scene():
+    rng = np.random.default_rng(23)
+    off = np.concatenate([[0], np.cumsum(CHUNK_SIZES)]).astype(np.uint64)
+    pts = np.concatenate([rng.uniform(-8.0, 8.0, (int(off[-1]), 3)), np.zeros((int(off[-1]), 1))], axis=1).astype(np.float32)
+    pts[int(off[3]) + 2048, 2] = np.inf      # the one point of the last keyframe's third chunk is not finite
+    queries = np.concatenate([rng.uniform(-9.0, 9.0, (254, 3)), [[np.nan, 0.0, 0.0]], [[100.0, 100.0, 100.0]]]).astype(np.float32)
+    return pts, off, queries
+
+
+def test_batched_build_at_the_chunk_edges_answers_like_the_single_build(gpu_ctx):
+    pts, off, q = chunk_scene()
+    scans = gpu_ctx.upload_scans(pts, off)
+    qc = gpu_ctx.upload(np.concatenate([q, np.zeros((len(q), 1), np.float32)], axis=1))
+    live = gpu_ctx.pool_live()
+    batch = gpu_ctx.search_index_batch(scans)
+    infos = []
+    for kf, b in enumerate(batch):
+        cloud = gpu_ctx.scan_of_keyframe(scans, kf)
+        with gpu_ctx.search_index(cloud) as single:
+            infos.append(_same_queries(b, single, qc, f"keyframe {kf}"))
+        cloud.free()
+    assert infos == [(1023, 1023), (0, 0), (1024, 1024), (2049, 2048)]
+    for b in batch:
+        b.close()
+    assert gpu_ctx.pool_live() == live
+    qc.free()
+    scans.free()
+
+
 def test_batched_build_serves_icp_like_the_single_build(gpu_ctx):
     near, far = fx.lattice_pair(), fx.lattice_pair(fx.FAR)
     tg = np.concatenate([near[0], far[0]])
