@@ -78,6 +78,11 @@ int ltm_cloud_size(ltm_ctx*, ltm_cloud, size_t* n);
 int ltm_cloud_download(ltm_ctx*, ltm_cloud, void* dst, size_t cap_pts, size_t stride_bytes);
 int ltm_cloud_device_ptr(ltm_ctx*, ltm_cloud, const void** dev_xyzi);                 /* borrowed, valid until free */
 int ltm_cloud_clone(ltm_ctx*, ltm_cloud, ltm_cloud* out);                              /* `*a = *b` deep copies */
+/* A cloud that came out of ltm_voxel_centroid[_batch] remembers the octree frame it was gridded under; ltm_cloud_clone, ltm_cloud_lend / _give and the
+ * kept / flagged parts of a partition keep it.  Writing the array behind ltm_cloud_device_ptr in place does NOT drop it: the cloud keeps the frame it was
+ * gridded under.  That is safe because ltm_voxel_centroid never trusts the frame: every call re-derives the frame from the points' bounding box and
+ * re-checks, point by point, that the cloud still is its own grid under it (codes strictly increasing, no -0.0) before it answers with a copy; rows
+ * swapped, duplicated or overwritten are gridded in full (tests/test_gpu_voxel_edges.py, the stale-frame cases). */
 int ltm_cloud_concat(ltm_ctx*, const ltm_cloud* in, size_t n, ltm_cloud* out);         /* `*a += *b` (order kept) */
 /* pcl::transformPointCloud(cloud, out, Matrix4d) applied once or twice (row-major 4x4, NULL = skip), the float result of the first
  * being the input of the second: local2global = (T1 = lidar->base, T2 = pose), global2local / transformGlobalMapToLocal =
