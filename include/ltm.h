@@ -646,6 +646,84 @@ int  ltm_clusters_download(ltm_ctx*, ltm_clusters*, int32_t* labels, uint32_t* s
 int  ltm_clusters_extract(ltm_ctx*, ltm_clusters*, ltm_cloud cloud, ltm_scanset* out);
 int  ltm_clusters_free(ltm_ctx*, ltm_clusters*);
 
+/* ------------------------------------------------------------------ planes ---- */
+/* RANSAC plane segmentation of the keyframes of a scan set, or of one cloud: pcl::SACSegmentation (setModelType SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE,
+ * setMethodType SAC_RANSAC, setDistanceThreshold, setMaxIterations, setAxis, setEpsAngle, setOptimizeCoefficients, segment), the step that takes the ground out
+ * of a scan before it is clustered.  The reference does not call it and PCL is not available to compare against; this is what this library takes PCL 1.10's
+ * SACSegmentation::segment (RandomSampleConsensus::computeModel over SampleConsensusModelPlane / ...PerpendicularPlane, then optimizeModelCoefficients and
+ * selectWithinDistance) to do, as understood.  tools/plane_numpy.py restates this text in numpy and the tests compare against that: for equality in everything
+ * but the coefficients.
+ *  A RECORD is one keyframe of the range, or the cloud.  Each record is handled on its own: its result depends neither on the rest of the batch, nor on its
+ *   keyframe number, nor on the schedule.  Points are the record's points in its own order, position 0 .. n - 1.
+ *  Hypotheses: hypothesis h (0 <= h < max_iterations) of a record of n points draws the three positions s_j = ((uint64)mix(seed, h, j) * n) >> 32, j = 0, 1, 2,
+ *   with mix the 32-bit hash  x = seed + 0x9E3779B9 * (3 h + j + 1);  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16  (all modulo
+ *   2^32: murmur3's finaliser).  The hypothesis is INVALID if two positions coincide or a drawn point has a non-finite coordinate; there is no redraw.  With
+ *   p0, p1, p2 the drawn points converted to double, u = p1 - p0, v = p2 - p0 and N = u x v, every component the difference of two products
+ *   (Nx = uy vz - uz vy, Ny = uz vx - ux vz, Nz = ux vy - uy vx), n2 = (Nx Nx + Ny Ny) + Nz Nz; the hypothesis is invalid unless n2 > 0 and finite.
+ *   T = (thr thr) n2 with thr the double distance_threshold.
+ *  Axis constraint (SACMODEL_PERPENDICULAR_PLANE: the plane's normal lies within eps_angle of the axis): with A the axis and c2 = cos(eps_angle)^2 (the C
+ *   library's cos, on the host), the hypothesis is invalid unless  ((Nx Ax + Ny Ay) + Nz Az)^2 >= (c2 n2) ((Ax Ax + Ay Ay) + Az Az).  An axis of (0, 0, 0) means no
+ *   constraint, and so does eps_angle >= pi / 2 (1.5707963267948966).
+ *  Inlier test: point q is an inlier of a valid hypothesis iff its three coordinates are finite and, with d = (double)q - p0 and
+ *   s = (Nx dx + Ny dy) + Nz dz,  s s < T  (strict, as PCL's countWithinDistance).  The count of an invalid hypothesis is 0.  Up to here there is no square
+ *   root, no division and no fused multiply-add: only + - x in double.
+ *  Best hypothesis: the valid hypothesis with the largest inlier count (its CONSENSUS), ties to the smaller h.  A record without a valid hypothesis (fewer than
+ *   three finite points, all coincident, all collinear, every normal outside the angle) has no plane: found = 0, best = -1, coefficients and plane point NaN,
+ *   every label 0.
+ *  Coefficients (a, b, c, d), a^2 + b^2 + c^2 = 1, and the PLANE POINT the device keeps with them.  Unrefined: n = N / sqrt(n2), plane point p0,
+ *   d = -((a p0x + b p0y) + c p0z).  Sign: with a non-zero axis, (a Ax + b Ay) + c Az > 0; without one, or where that sum is 0, the component of largest
+ *   magnitude is positive (the lower axis among equals), the rule of "normals".
+ *  Refinement (refine != 0; setOptimizeCoefficients(true), PCL's default): the moments of the best hypothesis's inliers about its p0 in double -- sum d and the
+ *   six sums dx dx, dx dy, dx dz, dy dy, dy dz, dz dz; the count is the consensus -- summed in the fixed shape of "clusters" over the record's points in their
+ *   own order: chunks of 256 consecutive points of the record, points that are no inliers entering as zeros and the last chunk padded with zeros, each chunk
+ *   by a binary tree (entries 128 apart first, then 64, ... 1); the chunk sums 64 at a time, the last group padded with zeros, each group by a binary tree
+ *   (32 apart first, ... 1), the group sums added in order.  The normal is the eigenvector of the smallest eigenvalue of the covariance
+ *   (sum d d^T / count - m m^T, m = sum d / count, with 1 / count formed once and multiplied) by the cyclic Jacobi iteration of "normals" -- one routine for
+ *   both (ltm_covariance.h) -- normalised, signed as above.  The plane point is c = p0 + sum d / count (a division), d = -((a cx + b cy) + c cz).  The
+ *   refinement is SKIPPED, and the unrefined plane stands with refined = 0, when the consensus is below 3, when the two smallest eigenvalues coincide, or
+ *   when the eigenvector is not finite.
+ *  Labels: the inliers are selected again with the final plane, refined or not (PCL: selectWithinDistance after optimizeModelCoefficients): label 1 iff the
+ *   point is finite and |(a ex + b ey) + c ez| < thr with e = (double)q - plane point.  n_inliers is the number of labels set; without refinement it may
+ *   differ from the consensus by points within rounding of the threshold, because the unit normal is rounded.
+ *  Domain: distance_threshold finite and > 0; 1 <= max_iterations <= 4096; axis finite; with a non-zero axis eps_angle finite and >= 0; kf_begin <= kf_end <=
+ *   n_kf; a record has fewer than 2^31 points (LTM_E_UNSUPPORTED beyond).  A handle of another context (a lane included), a NULL pointer or anything else
+ *   outside the domain: LTM_E_INVALID before the device is touched, and no handle is returned (*out = NULL).  An empty range and empty keyframes are valid.
+ *  DEPARTURES from PCL: all max_iterations hypotheses are always evaluated (PCL stops early by its probability rule); the draws come from the hash above, not
+ *   rand(), and a degenerate draw is not repeated; PCL's perpendicular-plane model tests the angle with acos, here squared cosines are compared; the sign of
+ *   the coefficients is canonical; PCL's optimizeModelCoefficients takes the eigenvector from Eigen's solver, here from the Jacobi iteration.
+ * The count kernel gives a workgroup LTM_PLANE_BLOCK_POINTS consecutive points of one record (ltm_plane_block_points() returns it).
+ * ltm_scanset_segment_planes segments ALL keyframes of the range in ONE fixed sequence of launches and returns ONE handle; it reads nothing back from the
+ * device (two small tables go up) and returns with the launches queued on the context's stream.  Memory comes from the context's pool; scratch is back when
+ * the call returns, on every error path too; ltm_destroy releases open handles. */
+#define LTM_PLANE_BLOCK_POINTS 2048
+typedef struct ltm_planes ltm_planes;
+typedef struct {
+    double   distance_threshold;   /* 0 (must be set)  setDistanceThreshold [m] */
+    uint32_t max_iterations;       /* 128              setMaxIterations: hypotheses per record, all evaluated */
+    uint32_t seed;                 /* 0                of the draws */
+    double   axis[3];              /* (0, 0, 0)        setAxis; zero = SACMODEL_PLANE, non-zero = SACMODEL_PERPENDICULAR_PLANE */
+    double   eps_angle;            /* 0                setEpsAngle [rad] */
+    int32_t  refine;               /* 1                setOptimizeCoefficients */
+} ltm_plane_params;
+void     ltm_plane_default_params(ltm_plane_params*);      /* host only, needs no device */
+uint32_t ltm_plane_block_points(void);                     /* LTM_PLANE_BLOCK_POINTS; host only */
+int  ltm_scanset_segment_planes(ltm_ctx*, ltm_scanset, size_t kf_begin, size_t kf_end, const ltm_plane_params*, ltm_planes** out /* one handle */);
+int  ltm_cloud_segment_plane(ltm_ctx*, ltm_cloud, const ltm_plane_params*, ltm_planes** out /* one record */);
+int  ltm_planes_info(ltm_ctx*, ltm_planes*, size_t* n_records, size_t* n_points, uint32_t* max_iterations);
+/* the set's device arrays, borrowed until ltm_planes_free: labels (uint8, n_points, the order of the scan set's range / the cloud), hypothesis inlier counts
+ * (uint32, n_records x max_iterations, 0 where invalid) and valid bytes (uint8, n_records x max_iterations) */
+int  ltm_planes_device(ltm_ctx*, ltm_planes*, const uint8_t** labels_dev, const uint32_t** hyp_counts_dev, const uint8_t** hyp_valid_dev);
+/* host copies, any pointer may be NULL: per record found, best (-1: none), consensus, n_valid (valid hypotheses), n_inliers (labels set), refined, coeff4
+ * (n_records x 4 doubles), point3 (n_records x 3 doubles); labels n_points; hyp_counts and hyp_valid n_records x max_iterations */
+int  ltm_planes_download(ltm_ctx*, ltm_planes*, uint8_t* found, int32_t* best, uint32_t* consensus, uint32_t* n_valid, uint32_t* n_inliers, uint8_t* refined,
+                         double* coeff4, double* point3, uint8_t* labels, uint32_t* hyp_counts, uint8_t* hyp_valid);
+/* The scan set the handle was made from -- the same keyframe range with the same point counts, else LTM_E_INVALID -- split by the labels into two scan sets
+ * with the keyframes of the range: the inliers and the rest, input order kept (the order-preserving compaction of ltm_knn_partition).  The ONE call of the
+ * section that reads back (the sizes).  ltm_planes_split_cloud is its twin for a handle of ltm_cloud_segment_plane and returns two clouds. */
+int  ltm_planes_split_scanset(ltm_ctx*, ltm_planes*, ltm_scanset, ltm_scanset* inliers, ltm_scanset* rest);
+int  ltm_planes_split_cloud(ltm_ctx*, ltm_planes*, ltm_cloud, ltm_cloud* inliers, ltm_cloud* rest);
+int  ltm_planes_free(ltm_ctx*, ltm_planes*);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections
@@ -782,6 +860,9 @@ int ltm_debug_knn_stats(ltm_ctx*, uint64_t* queries, uint64_t* undecided, uint64
  * beforehand), walks that left a clique leaf at its first hit, compare-and-swaps of the union-find that failed and were retried.  Always counted; context
  * switch LTM_CLUSTER_CLIQUE=0 (read by ltm_create) turns the clique leaves off -- same results, the counters show which form ran. */
 int ltm_debug_cluster_stats(ltm_ctx*, uint64_t* stats /* 6 */, int reset);
+/* counters of the plane segmentation since the last reset, stats[4]: point-hypothesis tests (per record its finite points x its valid hypotheses), valid
+ * hypotheses, records, records refined.  Counted on the device (the segmentation reads nothing back); this call reads them. */
+int ltm_debug_plane_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
 /* which kernel forms a Scan Context shape gets (host arithmetic only, needs no device; the launch wrappers' own expressions): *scatter_in_lds = 1 if
  * ltm_sc_from_scanset pre-reduces a block's points in LDS (up to 4096 bins), 0 if it goes straight to device memory; *pair_in_lds = 1 if the pair
  * distance of ltm_sc_distance / ltm_sc_detect stages both descriptors in LDS (up to 60 KB with the keys and norms), 0 if it reads them from device

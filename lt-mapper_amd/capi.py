@@ -39,6 +39,12 @@ class ClusterParams(C.Structure):
     _fields_ = [("tolerance", C.c_double), ("min_size", C.c_uint32), ("max_size", C.c_uint32)]
 
 
+class PlaneParams(C.Structure):
+    """ltm_plane_params"""
+    _fields_ = [("distance_threshold", C.c_double), ("max_iterations", C.c_uint32), ("seed", C.c_uint32), ("axis", C.c_double * 3),
+                ("eps_angle", C.c_double), ("refine", C.c_int32)]
+
+
 class IcpParams(C.Structure):
     """ltm_icp_params (LTslam.cpp:207-210)"""
     _fields_ = [("max_corr_dist", C.c_double), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
@@ -180,6 +186,17 @@ SIGNATURES = {
     "ltm_clusters_extract": (_i, [_vp, _vp, _u64, _pu64]),
     "ltm_clusters_free": (_i, [_vp, _vp]),
     "ltm_debug_cluster_stats": (_i, [_vp, _pu64, _i]),
+    "ltm_plane_default_params": (None, [C.POINTER(PlaneParams)]),
+    "ltm_plane_block_points": (C.c_uint32, []),
+    "ltm_scanset_segment_planes": (_i, [_vp, _u64, _sz, _sz, C.POINTER(PlaneParams), C.POINTER(_vp)]),
+    "ltm_cloud_segment_plane": (_i, [_vp, _u64, C.POINTER(PlaneParams), C.POINTER(_vp)]),
+    "ltm_planes_info": (_i, [_vp, _vp, _psz, _psz, C.POINTER(C.c_uint32)]),
+    "ltm_planes_device": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_planes_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltm_planes_split_scanset": (_i, [_vp, _vp, _u64, _pu64, _pu64]),
+    "ltm_planes_split_cloud": (_i, [_vp, _vp, _u64, _pu64, _pu64]),
+    "ltm_planes_free": (_i, [_vp, _vp]),
+    "ltm_debug_plane_stats": (_i, [_vp, _pu64, _i]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -700,6 +717,37 @@ class Context:
         self._ck(self.lib.ltm_debug_cluster_stats(self.h, a, int(reset)))
         return dict(zip(CLUSTER_STATS, [int(v) for v in a]))
 
+    def segment_planes(self, scans, distance_threshold, max_iterations=128, axis=None, eps_angle=0.0, seed=0, refine=True, kf_begin=0, kf_end=None):
+        """ltm_scanset_segment_planes: pcl::SACSegmentation (SACMODEL_PLANE, or SACMODEL_PERPENDICULAR_PLANE with `axis` and `eps_angle` [rad]; SAC_RANSAC)
+        of every keyframe [kf_begin, kf_end) of a ScanSet in one sequence of launches; nothing is read back.  Returns one Planes for the range."""
+        p = plane_params(distance_threshold, max_iterations, axis, eps_angle, seed, refine)
+        if not isinstance(scans, ScanSet):
+            raise TypeError("segment_planes takes a ScanSet (Context.upload_scans); segment_plane takes a cloud")
+        kb = int(kf_begin)
+        ke = scans.n_kf if kf_end is None else int(kf_end)
+        if kb < 0 or ke < kb:
+            raise ValueError("need 0 <= kf_begin <= kf_end")
+        h = _vp()
+        self._ck(self.lib.ltm_scanset_segment_planes(self.h, scans.h, kb, ke, C.byref(p), C.byref(h)))
+        return Planes(self, h.value)
+
+    def segment_plane(self, cloud, distance_threshold, max_iterations=128, axis=None, eps_angle=0.0, seed=0, refine=True):
+        """ltm_cloud_segment_plane: the same for one Cloud of this context, or an (n, 4) / (n, 3) array; one record"""
+        p = plane_params(distance_threshold, max_iterations, axis, eps_angle, seed, refine)
+        if isinstance(cloud, ScanSet) or cloud is None:
+            raise TypeError("segment_plane takes a Cloud or an array of points")
+        if not isinstance(cloud, Cloud):
+            cloud = self.upload(_xyzi(cloud))
+        h = _vp()
+        self._ck(self.lib.ltm_cloud_segment_plane(self.h, cloud.h, C.byref(p), C.byref(h)))
+        return Planes(self, h.value)
+
+    def plane_stats(self, reset=False):
+        """ltm_debug_plane_stats: dict of the four counters since the last reset"""
+        a = (C.c_uint64 * 4)()
+        self._ck(self.lib.ltm_debug_plane_stats(self.h, a, int(reset)))
+        return dict(zip(PLANE_STATS, [int(v) for v in a]))
+
     # ---- loop submaps
     def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
         """ltm_submaps_assemble: Session::loopFindNearKeyframesLocalCoord (affines=None) / CentralCoord (affines: (n_kf, 3, 4) float32, see
@@ -1012,7 +1060,7 @@ class SearchIndex:
         """n elements of a library device array -> numpy array or torch CUDA tensor (a copy either way)"""
         if as_torch:
             import torch
-            t = torch.empty(n, dtype={np.int32: torch.int32, np.float32: torch.float32, np.uint64: torch.int64}[dtype],
+            t = torch.empty(n, dtype={np.int32: torch.int32, np.float32: torch.float32, np.uint64: torch.int64, np.uint8: torch.uint8}[dtype],
                             device=f"cuda:{self.ctx.device}")
             if n:
                 torch.cuda.synchronize(t.device)
@@ -1229,6 +1277,121 @@ def sc_paths(num_ring, num_sector):
     if rc != 0:
         raise LtmError(rc, "ltm_debug_sc_paths")
     return bool(a.value), bool(b.value)
+
+
+PLANE_STATS = ("point_hypothesis_tests", "valid_hypotheses", "records", "records_refined")
+PLANE_MAX_ITERATIONS = 4096
+
+
+def plane_block_points():
+    """ltm_plane_block_points: the points of one record that a workgroup of the count kernel takes (needs no device)"""
+    return int(load_library().ltm_plane_block_points())
+
+
+def plane_params(distance_threshold, max_iterations=128, axis=None, eps_angle=0.0, seed=0, refine=True):
+    """ltm_plane_params, checked: distance_threshold finite and > 0, 1 <= max_iterations <= 4096, axis None or three finite numbers, with a non-zero axis
+    eps_angle finite and >= 0, 0 <= seed < 2^32"""
+    thr = float(distance_threshold)
+    if not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError("distance_threshold must be finite and > 0")
+    it = int(max_iterations)
+    if it != max_iterations or not 1 <= it <= PLANE_MAX_ITERATIONS:
+        raise ValueError("need 1 <= max_iterations <= 4096")
+    sd = int(seed)
+    if sd != seed or not 0 <= sd < 2 ** 32:
+        raise ValueError("need 0 <= seed < 2^32")
+    ax = np.zeros(3) if axis is None else np.asarray(axis, dtype=np.float64).reshape(-1)
+    if ax.shape != (3,) or not np.isfinite(ax).all():
+        raise ValueError("axis must be three finite numbers")
+    eps = float(eps_angle)
+    if ax.any() and not (np.isfinite(eps) and eps >= 0.0):
+        raise ValueError("eps_angle must be finite and >= 0")
+    if not ax.any():
+        eps = eps if np.isfinite(eps) else 0.0
+    return PlaneParams(thr, it, sd, (C.c_double * 3)(*ax.tolist()), eps, 1 if refine else 0)
+
+
+class Planes:
+    """ltm_planes: the RANSAC plane of every record (keyframe of a scan-set range, or one cloud); semantics in include/ltm.h, "planes".  Labels are in the order
+    of the range's points."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        self._host = None
+
+    def info(self):
+        """(records, points, max_iterations)"""
+        a, b, m = C.c_size_t(), C.c_size_t(), C.c_uint32()
+        self.ctx._ck(self.ctx.lib.ltm_planes_info(self.ctx.h, self.h, C.byref(a), C.byref(b), C.byref(m)))
+        return a.value, b.value, m.value
+
+    def __len__(self):
+        return self.info()[0]
+
+    def _device(self):
+        pl, pc, pv = _vp(), _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_planes_device(self.ctx.h, self.h, C.byref(pl), C.byref(pc), C.byref(pv)))
+        return pl.value, pc.value, pv.value
+
+    def _download(self):
+        if self._host is None:
+            nr = self.info()[0]
+            found, best, cons, nval = np.empty(nr, np.uint8), np.empty(nr, np.int32), np.empty(nr, np.uint32), np.empty(nr, np.uint32)
+            nin, ref, coeff, point = np.empty(nr, np.uint32), np.empty(nr, np.uint8), np.empty((nr, 4), np.float64), np.empty((nr, 3), np.float64)
+            self.ctx._ck(self.ctx.lib.ltm_planes_download(self.ctx.h, self.h, found.ctypes.data, best.ctypes.data, cons.ctypes.data, nval.ctypes.data,
+                                                          nin.ctypes.data, ref.ctypes.data, coeff.ctypes.data, point.ctypes.data, None, None, None))
+            self._host = (found, best, cons, nval, nin, ref, coeff, point)
+        return self._host
+
+    found = property(lambda self: self._download()[0], doc="uint8 [n_records]: 1 = the record has a plane")
+    best = property(lambda self: self._download()[1], doc="int32 [n_records]: the best hypothesis, -1 = none")
+    consensus = property(lambda self: self._download()[2], doc="uint32 [n_records]: its inlier count")
+    n_valid = property(lambda self: self._download()[3], doc="uint32 [n_records]: valid hypotheses")
+    n_inliers = property(lambda self: self._download()[4], doc="uint32 [n_records]: labels set by the final plane")
+    refined = property(lambda self: self._download()[5], doc="uint8 [n_records]: 1 = the coefficients are the refined ones")
+    coefficients = property(lambda self: self._download()[6], doc="float64 [n_records, 4]: a, b, c, d")
+    points = property(lambda self: self._download()[7], doc="float64 [n_records, 3]: the plane point the labels were taken about")
+
+    def labels(self, as_torch=False):
+        """uint8 [n_points]: 1 = inlier of its record's final plane"""
+        return SearchIndex._out(self, self._device()[0], self.info()[1], np.uint8, as_torch)
+
+    def hypothesis_counts(self):
+        """uint32 [n_records, max_iterations]: the inlier count of every hypothesis, 0 where invalid"""
+        nr, _, m = self.info()
+        return SearchIndex._out(self, self._device()[1], nr * m, np.uint32, False).reshape(nr, m)
+
+    def hypothesis_valid(self):
+        """uint8 [n_records, max_iterations]"""
+        nr, _, m = self.info()
+        return SearchIndex._out(self, self._device()[2], nr * m, np.uint8, False).reshape(nr, m)
+
+    def split(self, scans_or_cloud):
+        """ltm_planes_split_scanset / _cloud: (inliers, rest) of the ScanSet or Cloud the set was made from, input order kept"""
+        a, b = _u64(), _u64()
+        if isinstance(scans_or_cloud, ScanSet):
+            self.ctx._ck(self.ctx.lib.ltm_planes_split_scanset(self.ctx.h, self.h, scans_or_cloud.h, C.byref(a), C.byref(b)))
+            return ScanSet(self.ctx, a.value), ScanSet(self.ctx, b.value)
+        cloud = scans_or_cloud if isinstance(scans_or_cloud, Cloud) else self.ctx.upload(_xyzi(scans_or_cloud))
+        self.ctx._ck(self.ctx.lib.ltm_planes_split_cloud(self.ctx.h, self.h, cloud.h, C.byref(a), C.byref(b)))
+        return Cloud(self.ctx, a.value), Cloud(self.ctx, b.value)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ltm_planes_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ScanContexts:

@@ -9,6 +9,7 @@
 // that order in double, so a normal depends on its index alone: no atomics, nothing that depends on the walk or on the rest of the batch.
 #include "ltm_kernels_common.h"
 #include "ltm_search_walk.h"      // pair_less, walk, seed_leaves
+#include "ltm_covariance.h"       // smallest_axis_from_moments: covariance, cyclic Jacobi, canonical sign
 #include <climits>
 namespace ltm {
 
@@ -26,54 +27,15 @@ struct Moments {
     }
 };
 
-// normal and curvature from the moments of n >= 3 neighbours (include/ltm.h, "normals": covariance, cyclic Jacobi, canonical sign, viewpoint flip)
+// normal and curvature from the moments of n >= 3 neighbours (include/ltm.h, "normals": covariance, cyclic Jacobi and canonical sign in ltm_covariance.h, then
+// curvature and viewpoint flip)
 __device__ float4 normal_from_moments(const Moments& M, int n, const float4& p, const double* vp)
 {
-    const double inv = 1.0 / (double)n;
-    const double mx = M.s[0] * inv, my = M.s[1] * inv, mz = M.s[2] * inv;
-    double A[3][3], V[3][3];
-    A[0][0] = M.c[0] * inv - mx * mx; A[0][1] = M.c[1] * inv - mx * my; A[0][2] = M.c[2] * inv - mx * mz;
-    A[1][1] = M.c[3] * inv - my * my; A[1][2] = M.c[4] * inv - my * mz; A[2][2] = M.c[5] * inv - mz * mz;
-    A[1][0] = A[0][1]; A[2][0] = A[0][2]; A[2][1] = A[1][2];
-    for (int r = 0; r < 3; ++r)
-        for (int k = 0; k < 3; ++k) V[r][k] = r == k ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-        for (int i = 0; i < 2; ++i)
-            for (int j = i + 1; j < 3; ++j) {
-                const double apq = A[i][j];
-                if (apq == 0.0 || fabs(apq) <= 1.0e-17 * sqrt(fabs(A[i][i] * A[j][j]))) continue;
-                rotated = true;
-                const double theta = (A[j][j] - A[i][i]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-                const int l = 3 - i - j;      // the third axis
-                const double aii = A[i][i], ajj = A[j][j], ail = A[i][l], ajl = A[j][l];
-                A[i][i] = aii - t * apq; A[j][j] = ajj + t * apq;
-                A[i][j] = A[j][i] = 0.0;
-                A[i][l] = A[l][i] = cs * ail - sn * ajl;
-                A[j][l] = A[l][j] = sn * ail + cs * ajl;
-                for (int k = 0; k < 3; ++k) {
-                    const double vi = V[k][i], vj = V[k][j];
-                    V[k][i] = cs * vi - sn * vj; V[k][j] = sn * vi + cs * vj;
-                }
-            }
-        if (!rotated) break;
-    }
-    int e = 0;      // the smallest eigenvalue, the lower axis among equals
-    if (A[1][1] < A[e][e]) e = 1;
-    if (A[2][2] < A[e][e]) e = 2;
-    const double tr = (A[0][0] + A[1][1]) + A[2][2];
-    const double lmin = fmax(A[e][e], 0.0);
+    double nx, ny, nz, lam[3];
+    const int e = smallest_axis_from_moments(M.s, M.c, n, nx, ny, nz, lam);
+    const double tr = (lam[0] + lam[1]) + lam[2];
+    const double lmin = fmax(lam[e], 0.0);
     const double curv = tr > 0.0 ? lmin / tr : 0.0;
-    double nx = V[0][e], ny = V[1][e], nz = V[2][e];
-    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
-    nx /= len; ny /= len; nz /= len;
-    // canonical sign: the component of largest magnitude is positive, the lower axis among equals
-    double big = nx;
-    if (fabs(ny) > fabs(big)) big = ny;
-    if (fabs(nz) > fabs(big)) big = nz;
-    if (big < 0.0) { nx = -nx; ny = -ny; nz = -nz; }
     // flipNormalTowardsViewpoint
     const double dot = ((vp[0] - (double)p.x) * nx + (vp[1] - (double)p.y) * ny) + (vp[2] - (double)p.z) * nz;
     if (dot < 0.0) { nx = -nx; ny = -ny; nz = -nz; }

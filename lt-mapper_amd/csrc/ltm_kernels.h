@@ -351,6 +351,28 @@ hipError_t cluster_finish(const ClusterSeg* segs, const uint64_t* keys_sorted, c
                           const int32_t* cfirst, const uint32_t* cseg, const uint32_t* goff, const uint32_t* choff, const uint64_t* coff, double* psum, uint32_t* pbox,
                           int32_t* idx_out, uint32_t* sizes_out, int32_t* first_out, float* box_out, double* centroid_out, uint64_t* offsets_out, hipStream_t s);
 
+// ---- RANSAC plane segmentation of records of points (ltm_k_plane.hip; include/ltm.h "planes") ----
+static constexpr int kPlaneBlock = 256;                                      // threads per workgroup of the per-point kernels
+static constexpr int kPlanePointsPerThread = 8;                              // points a thread of the count kernel keeps in registers
+static constexpr int kPlaneBlockPoints = kPlaneBlock * kPlanePointsPerThread;   // points of one record per workgroup (LTM_PLANE_BLOCK_POINTS)
+static constexpr int kPlaneChunk = 256;                                      // points per partial record of the moments: the chunk of "clusters"
+static constexpr int kPlaneMaxIterations = 4096;                             // counters of a workgroup in LDS
+static constexpr int kPlaneMoments = 9;                                      // doubles per partial record: sum d (3), sum d d^T (xx xy xz yy yz zz)
+// one record of the batch: its n points, base = its first point among the call's points (labels), its first chunk among the batch's partial records
+// (ceil(n / kPlaneChunk) of them); kPlaneBlockPoints points per workgroup
+struct PlaneRec { const float4* pts; uint64_t base; uint32_t n, chunk0; BlockSpan span; };
+// one hypothesis: the seven values the count kernel reads (N, p0, T; T = 0 where the hypothesis is invalid) in a 64-byte row
+struct PlaneHyp { double N[3], p0[3], T, pad; };
+// what a record ends with (ltm_planes_download)
+struct PlaneOut { double coeff[4], point[3]; int32_t best; uint32_t consensus, n_valid, n_inliers; uint8_t found, refined, pad[6]; };
+struct PlaneLaunch { double thr, axis[3], c2; uint32_t max_iterations, seed; int constrained, has_axis, refine; };
+static_assert(sizeof(PlaneRec) == 32 && sizeof(PlaneHyp) == 64 && sizeof(PlaneOut) == 80, "the plane records keep their sizes");
+// The fixed launch sequence of ltm_scanset_segment_planes for n_recs records (out zeroed, counts zeroed by the caller): hypotheses, counts, best, moments
+// and combine (refine only), labels.  hyp / valid / counts: n_recs x max_iterations; partials: kPlaneMoments doubles per chunk; labels[base + i]: point i
+// of a record; stats4 += point-hypothesis tests, valid hypotheses, records, records refined
+hipError_t plane_segment(const PlaneRec* recs, const uint32_t* block_rec, uint32_t n_blocks, uint32_t n_recs, const PlaneLaunch& L, PlaneHyp* hyp, uint8_t* valid,
+                         uint32_t* counts, double* partials, PlaneOut* out, uint8_t* labels, unsigned long long* stats4, hipStream_t s);
+
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
 // one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; 256 points per workgroup
 struct SubmapPiece { uint64_t src, dst; uint32_t n, affine; BlockSpan span; };
