@@ -724,6 +724,79 @@ int  ltm_planes_split_scanset(ltm_ctx*, ltm_planes*, ltm_scanset, ltm_scanset* i
 int  ltm_planes_split_cloud(ltm_ctx*, ltm_planes*, ltm_cloud, ltm_cloud* inliers, ltm_cloud* rest);
 int  ltm_planes_free(ltm_ctx*, ltm_planes*);
 
+/* --------------------------------------------------------- outlier filters ---- */
+/* Statistical and radius outlier removal over the targets of search indices: pcl::StatisticalOutlierRemoval (setMeanK, setStddevMulThresh, filter) and
+ * pcl::RadiusOutlierRemoval (setRadiusSearch, setMinNeighborsInRadius, filter), the filters that go between the other steps: they take the isolated speckle
+ * out of a change map before it is clustered and the stray returns out of a scan before normals, ICP, RANSAC or a Scan Context see them.  The reference
+ * calls neither and PCL is not available to compare against; this is what this library takes PCL 1.10's two applyFilterIndices to do, as understood.
+ * tools/outlier_numpy.py restates this text in numpy and the tests compare against that, for equality.
+ *  A RECORD is one listed index (ltm_search_build or ltm_search_build_scanset; the same index may be listed more than once).  A record's result is a function
+ *   of its index and the parameters alone: it depends neither on the rest of the batch nor on the schedule, and there are no floating-point atomics.  The
+ *   points are the index's target points in their ORIGINAL order, position 0 .. n_target - 1; n_finite of them have three finite coordinates.  d2 is the
+ *   index's own distance (FLANN's L2_Simple in float, ((dx*dx)+dy*dy)+dz*dz, no fused multiply-add).
+ *  STATISTICAL, 1 <= mean_k <= 63 (the neighbourhood is mean_k + 1 <= 64 points, the limit of ltm_knn_search), stddev_mul finite (negative allowed, as in
+ *   PCL):
+ *   Neighbourhood of a finite point: its min(mean_k + 1, n_finite) nearest finite target points in the order of ltm_knn_search, the point itself among them
+ *    at distance 0.
+ *   Distance d_i = (float)(S / mean_k), S the sum in double of sqrt((double)d2_j) over the neighbours AFTER THE FIRST in ascending d2 (equal d2 give equal
+ *    terms, so the order among them cannot matter); sqrt and / are the correctly rounded IEEE operations.  mean_k stays the divisor when the index holds
+ *    fewer than mean_k + 1 finite points (the convention of ltm_knn_partition).  A non-finite point has d_i = 0.
+ *   Record statistics in double over the d_i in original order (n_target entries, the zeros of the non-finite points included, as PCL adds them):
+ *    sum = SUM d_i and sq_sum = SUM (double)d_i (double)d_i, each in the fixed shape of "clusters": chunks of 256 consecutive positions, the last one padded
+ *    with zeros, each summed by a binary tree (entries 128 apart first, then 64, ... 1); the chunk sums 64 at a time, the last group padded with zeros, each
+ *    group by a binary tree (32 apart first, ... 1), the group sums added in order to 0.  With n = n_finite:  mean = sum / n;  variance =
+ *    (sq_sum - (sum sum) / n) / (n - 1), and a variance that is not above 0 is 0;  stddev = sqrt(variance);  threshold = mean + stddev_mul stddev -- in
+ *    the order written, no fused multiply-add.  n < 2: stddev = 0.  n = 0: mean = stddev = threshold = 0.
+ *   Label 1 (kept) iff the point is finite and (double)d_i <= threshold.
+ *  RADIUS, radius finite and > 0, min_neighbors >= 1:
+ *   neighbours_i = the number of finite target points j, i itself included, with d2(i, j) < r2, r2 = (float)((double)radius * radius), strict <: exactly the
+ *    relation of ltm_radius_search and of "clusters".  The stored count is min(neighbours_i, min_neighbors): the walk stops as soon as it is reached.
+ *   Label 1 (kept) iff the point is finite and its count equals min_neighbors.  A non-finite point has count 0.
+ *  Both: labels are uint8 in the target's original order; per record n_target, n_finite and n_kept (labels set), for the statistical filter also mean, stddev
+ *   and threshold.
+ *  Domain: the parameter ranges above; a NULL pointer, a NULL handle, a handle of another context (a lane included) or a parameter outside its range is
+ *   LTM_E_INVALID before the device is touched, and no handle is returned (*out = NULL).  An empty index, one without a finite point and an empty list are
+ *   valid.  All indices of a call together: fewer than 2^31 target points (LTM_E_UNSUPPORTED beyond).
+ *  DEPARTURES from PCL: non-finite points are removed (PCL 1.10 gives them distance 0 and so keeps them; they still enter the statistics as zeros over
+ *   n_finite, as written above); the variance is clamped at 0 (PCL takes the square root of a negative rounding residue and then removes every point);
+ *   stddev = 0 below two points; the sums have the fixed shape above (PCL adds in index order); there are no `negative` / `keep_organized` flags (the split
+ *   gives both sides); the radius filter's counts saturate at min_neighbors.
+ * Each filter call handles ALL listed indices in ONE fixed sequence of launches and returns ONE handle with n_idx records; it reads nothing back from the
+ * device (small tables go up) and returns with the launches queued on the context's stream.  Memory comes from the context's pool; scratch is back when the
+ * call returns, on every error path too; the handle keeps no reference to its indices (either may be freed first); ltm_destroy releases open handles. */
+#define LTM_OUTLIERS_STATISTICAL 0
+#define LTM_OUTLIERS_RADIUS      1
+typedef struct ltm_outliers ltm_outliers;
+typedef struct {
+    uint32_t mean_k;          /* 1     setMeanK (PCL's constructor) */
+    double   stddev_mul;      /* 0.0   setStddevMulThresh */
+} ltm_sor_params;
+typedef struct {
+    double   radius;          /* 0 (must be set)  setRadiusSearch [m] */
+    uint32_t min_neighbors;   /* 1                setMinNeighborsInRadius */
+} ltm_ror_params;
+void ltm_sor_default_params(ltm_sor_params*);      /* host only, needs no device; NULL is a no-op */
+void ltm_ror_default_params(ltm_ror_params*);
+/* pcl::StatisticalOutlierRemoval::filter / pcl::RadiusOutlierRemoval::filter over every listed index */
+int  ltm_search_filter_statistical(ltm_ctx*, size_t n_idx, ltm_search* const* idx, const ltm_sor_params*, ltm_outliers** out /* one handle */);
+int  ltm_search_filter_radius(ltm_ctx*, size_t n_idx, ltm_search* const* idx, const ltm_ror_params*, ltm_outliers** out /* one handle */);
+int  ltm_outliers_info(ltm_ctx*, ltm_outliers*, int* kind /* LTM_OUTLIERS_... */, size_t* n_records, size_t* n_points /* the records' n_target, summed */);
+/* the set's device arrays, borrowed until ltm_outliers_free: record offsets (uint64, n_records + 1: record r has positions [off[r], off[r + 1])), labels (uint8,
+ * n_points) and, per position, distances (float; NULL for a radius set) or counts (uint32; NULL for a statistical set) */
+int  ltm_outliers_device(ltm_ctx*, ltm_outliers*, const uint64_t** offsets_dev, const uint8_t** labels_dev, const float** distances_dev,
+                         const uint32_t** counts_dev);
+/* host copies, any pointer may be NULL: per record n_target, n_finite, n_kept, mean, stddev, threshold; per position labels, distances, counts.  Asking a
+ * radius set for statistics or distances, or a statistical set for counts, is LTM_E_INVALID */
+int  ltm_outliers_download(ltm_ctx*, ltm_outliers*, uint32_t* n_target, uint32_t* n_finite, uint32_t* n_kept, double* mean, double* stddev, double* threshold,
+                           uint8_t* labels, float* distances, uint32_t* counts);
+/* A scan set with one keyframe per record, keyframe r with as many points as record r's target (the scan set the indices were built over), else
+ * LTM_E_INVALID, split by the labels into two scan sets with the same keyframes: the kept points and the removed ones, input order kept on both sides (the
+ * planes' split path).  The ONE call of the section that reads back (the sizes).  ltm_outliers_split_cloud is its twin for a handle of ONE record and
+ * returns two clouds. */
+int  ltm_outliers_split_scanset(ltm_ctx*, ltm_outliers*, ltm_scanset, ltm_scanset* kept, ltm_scanset* removed);
+int  ltm_outliers_split_cloud(ltm_ctx*, ltm_outliers*, ltm_cloud, ltm_cloud* kept, ltm_cloud* removed);
+int  ltm_outliers_free(ltm_ctx*, ltm_outliers*);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections
@@ -863,6 +936,9 @@ int ltm_debug_cluster_stats(ltm_ctx*, uint64_t* stats /* 6 */, int reset);
 /* counters of the plane segmentation since the last reset, stats[4]: point-hypothesis tests (per record its finite points x its valid hypotheses), valid
  * hypotheses, records, records refined.  Counted on the device (the segmentation reads nothing back); this call reads them. */
 int ltm_debug_plane_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
+/* counters of the outlier filters since the last reset, stats[4]: finite points processed, point pairs whose distance was evaluated, radius walks that
+ * refused a node because min_neighbors had been counted, records.  Counted on the device (the filters read nothing back); this call reads them. */
+int ltm_debug_outlier_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
 /* which kernel forms a Scan Context shape gets (host arithmetic only, needs no device; the launch wrappers' own expressions): *scatter_in_lds = 1 if
  * ltm_sc_from_scanset pre-reduces a block's points in LDS (up to 4096 bins), 0 if it goes straight to device memory; *pair_in_lds = 1 if the pair
  * distance of ltm_sc_distance / ltm_sc_detect stages both descriptors in LDS (up to 60 KB with the keys and norms), 0 if it reads them from device

@@ -45,6 +45,16 @@ class PlaneParams(C.Structure):
                 ("eps_angle", C.c_double), ("refine", C.c_int32)]
 
 
+class SorParams(C.Structure):
+    """ltm_sor_params"""
+    _fields_ = [("mean_k", C.c_uint32), ("stddev_mul", C.c_double)]
+
+
+class RorParams(C.Structure):
+    """ltm_ror_params"""
+    _fields_ = [("radius", C.c_double), ("min_neighbors", C.c_uint32)]
+
+
 class IcpParams(C.Structure):
     """ltm_icp_params (LTslam.cpp:207-210)"""
     _fields_ = [("max_corr_dist", C.c_double), ("max_iterations", C.c_int), ("transformation_epsilon", C.c_double),
@@ -197,6 +207,17 @@ SIGNATURES = {
     "ltm_planes_split_cloud": (_i, [_vp, _vp, _u64, _pu64, _pu64]),
     "ltm_planes_free": (_i, [_vp, _vp]),
     "ltm_debug_plane_stats": (_i, [_vp, _pu64, _i]),
+    "ltm_sor_default_params": (None, [C.POINTER(SorParams)]),
+    "ltm_ror_default_params": (None, [C.POINTER(RorParams)]),
+    "ltm_search_filter_statistical": (_i, [_vp, _sz, C.POINTER(_vp), C.POINTER(SorParams), C.POINTER(_vp)]),
+    "ltm_search_filter_radius": (_i, [_vp, _sz, C.POINTER(_vp), C.POINTER(RorParams), C.POINTER(_vp)]),
+    "ltm_outliers_info": (_i, [_vp, _vp, C.POINTER(_i), _psz, _psz]),
+    "ltm_outliers_device": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_outliers_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltm_outliers_split_scanset": (_i, [_vp, _vp, _u64, _pu64, _pu64]),
+    "ltm_outliers_split_cloud": (_i, [_vp, _vp, _u64, _pu64, _pu64]),
+    "ltm_outliers_free": (_i, [_vp, _vp]),
+    "ltm_debug_outlier_stats": (_i, [_vp, _pu64, _i]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -748,6 +769,37 @@ class Context:
         self._ck(self.lib.ltm_debug_plane_stats(self.h, a, int(reset)))
         return dict(zip(PLANE_STATS, [int(v) for v in a]))
 
+    def _outlier_indices(self, indices, what):
+        indices = list(indices)
+        for x in indices:
+            if not isinstance(x, SearchIndex):
+                raise TypeError(f"{what} takes SearchIndex objects (Context.search_index)")
+        return indices, (_vp * max(len(indices), 1))(*[x.h for x in indices])
+
+    def statistical_outliers(self, indices, mean_k, stddev_mul):
+        """ltm_search_filter_statistical: pcl::StatisticalOutlierRemoval (setMeanK, setStddevMulThresh) over the targets of all `indices` (SearchIndex objects
+        of this context; the same one may be listed more than once) in one sequence of launches; nothing is read back.  Returns one Outliers with one
+        record per index."""
+        p = sor_params(mean_k, stddev_mul)
+        indices, hs = self._outlier_indices(indices, "statistical_outliers")
+        h = _vp()
+        self._ck(self.lib.ltm_search_filter_statistical(self.h, len(indices), hs, C.byref(p), C.byref(h)))
+        return Outliers(self, h.value)
+
+    def radius_outliers(self, indices, radius, min_neighbors=1):
+        """ltm_search_filter_radius: pcl::RadiusOutlierRemoval (setRadiusSearch, setMinNeighborsInRadius) likewise"""
+        p = ror_params(radius, min_neighbors)
+        indices, hs = self._outlier_indices(indices, "radius_outliers")
+        h = _vp()
+        self._ck(self.lib.ltm_search_filter_radius(self.h, len(indices), hs, C.byref(p), C.byref(h)))
+        return Outliers(self, h.value)
+
+    def outlier_stats(self, reset=False):
+        """ltm_debug_outlier_stats: dict of the four counters since the last reset"""
+        a = (C.c_uint64 * 4)()
+        self._ck(self.lib.ltm_debug_outlier_stats(self.h, a, int(reset)))
+        return dict(zip(OUTLIER_STATS, [int(v) for v in a]))
+
     # ---- loop submaps
     def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
         """ltm_submaps_assemble: Session::loopFindNearKeyframesLocalCoord (affines=None) / CentralCoord (affines: (n_kf, 3, 4) float32, see
@@ -1126,6 +1178,14 @@ class SearchIndex:
         """ltm_search_cluster for this index alone: setClusterTolerance(tolerance), setMinClusterSize, setMaxClusterSize (None: no limit), extract"""
         return self.ctx.cluster([self], tolerance, min_size, max_size)[0]
 
+    def statistical_outliers(self, mean_k, stddev_mul):
+        """ltm_search_filter_statistical for this index alone: setMeanK(mean_k), setStddevMulThresh(stddev_mul), filter; an Outliers of one record"""
+        return self.ctx.statistical_outliers([self], mean_k, stddev_mul)
+
+    def radius_outliers(self, radius, min_neighbors=1):
+        """ltm_search_filter_radius for this index alone: setRadiusSearch(radius), setMinNeighborsInRadius(min_neighbors), filter"""
+        return self.ctx.radius_outliers([self], radius, min_neighbors)
+
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.ltm_search_free(self.ctx.h, self.h)
@@ -1379,6 +1439,123 @@ class Planes:
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.lib.ltm_planes_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+OUTLIER_STATS = ("finite_points", "distance_evaluations", "radius_early_stops", "records")
+OUTLIERS_STATISTICAL, OUTLIERS_RADIUS = 0, 1
+SOR_MAX_MEAN_K = 63      # mean_k + 1 neighbours: the limit of ltm_knn_search
+
+
+def sor_params(mean_k, stddev_mul):
+    """ltm_sor_params, checked: 1 <= mean_k <= 63, stddev_mul finite"""
+    k = int(mean_k)
+    if k != mean_k or not 1 <= k <= SOR_MAX_MEAN_K:
+        raise ValueError("need 1 <= mean_k <= 63")
+    mul = float(stddev_mul)
+    if not np.isfinite(mul):
+        raise ValueError("stddev_mul must be finite")
+    return SorParams(k, mul)
+
+
+def ror_params(radius, min_neighbors=1):
+    """ltm_ror_params, checked: radius finite and > 0, 1 <= min_neighbors < 2^32"""
+    r = float(radius)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError("radius must be finite and > 0")
+    m = int(min_neighbors)
+    if m != min_neighbors or not 1 <= m < 2 ** 32:
+        raise ValueError("need 1 <= min_neighbors < 2^32")
+    return RorParams(r, m)
+
+
+class Outliers:
+    """ltm_outliers: the labels of a statistical or radius outlier filter, one record per listed search index (semantics in include/ltm.h, "outlier
+    filters").  The per-position arrays hold the records one after the other, each in its target's ORIGINAL order; offsets() says where each begins."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        self._host = None
+
+    def info(self):
+        """(kind, records, positions)"""
+        k, a, b = _i(), C.c_size_t(), C.c_size_t()
+        self.ctx._ck(self.ctx.lib.ltm_outliers_info(self.ctx.h, self.h, C.byref(k), C.byref(a), C.byref(b)))
+        return k.value, a.value, b.value
+
+    def __len__(self):
+        return self.info()[1]
+
+    kind = property(lambda self: ("statistical", "radius")[self.info()[0]])
+
+    def _device(self):
+        po, pl, pd, pc = _vp(), _vp(), _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_outliers_device(self.ctx.h, self.h, C.byref(po), C.byref(pl), C.byref(pd), C.byref(pc)))
+        return po.value, pl.value, pd.value, pc.value
+
+    def _download(self):
+        if self._host is None:
+            kind, nr, _ = self.info()
+            nt, nf, nk = np.empty(nr, np.uint32), np.empty(nr, np.uint32), np.empty(nr, np.uint32)
+            mean, sd, thr = np.zeros(nr, np.float64), np.zeros(nr, np.float64), np.zeros(nr, np.float64)
+            stats = (mean.ctypes.data, sd.ctypes.data, thr.ctypes.data) if kind == OUTLIERS_STATISTICAL else (None, None, None)
+            self.ctx._ck(self.ctx.lib.ltm_outliers_download(self.ctx.h, self.h, nt.ctypes.data, nf.ctypes.data, nk.ctypes.data, *stats, None, None, None))
+            self._host = (nt, nf, nk, mean, sd, thr)
+        return self._host
+
+    n_target = property(lambda self: self._download()[0], doc="uint32 [n_records]: target points of the record's index")
+    n_finite = property(lambda self: self._download()[1], doc="uint32 [n_records]: finite ones among them")
+    n_kept = property(lambda self: self._download()[2], doc="uint32 [n_records]: labels set")
+    mean = property(lambda self: self._download()[3], doc="float64 [n_records]: mean of the distances (statistical; zeros for a radius set)")
+    stddev = property(lambda self: self._download()[4], doc="float64 [n_records]")
+    threshold = property(lambda self: self._download()[5], doc="float64 [n_records]: mean + stddev_mul * stddev")
+
+    def offsets(self):
+        """uint64 [n_records + 1]: record r owns positions [offsets[r], offsets[r + 1]) of labels / distances / counts"""
+        return SearchIndex._out(self, self._device()[0], self.info()[1] + 1, np.uint64, False)
+
+    def labels(self, as_torch=False):
+        """uint8 [n_points]: 1 = kept"""
+        return SearchIndex._out(self, self._device()[1], self.info()[2], np.uint8, as_torch)
+
+    def distances(self, as_torch=False):
+        """float32 [n_points]: the mean neighbour distance of every position, 0 for a non-finite point (statistical sets only)"""
+        if self.info()[0] != OUTLIERS_STATISTICAL:
+            raise ValueError("a radius outlier set has no distances")
+        return SearchIndex._out(self, self._device()[2], self.info()[2], np.float32, as_torch)
+
+    def counts(self):
+        """uint32 [n_points]: neighbours within the radius, the point included, saturated at min_neighbors (radius sets only)"""
+        if self.info()[0] != OUTLIERS_RADIUS:
+            raise ValueError("a statistical outlier set has no counts")
+        return SearchIndex._out(self, self._device()[3], self.info()[2], np.uint32, False)
+
+    def split(self, scans_or_cloud):
+        """ltm_outliers_split_scanset / _cloud: (kept, removed) of a ScanSet with one keyframe per record, or of the Cloud (or array) of a one-record
+        set; input order kept on both sides"""
+        a, b = _u64(), _u64()
+        if isinstance(scans_or_cloud, ScanSet):
+            self.ctx._ck(self.ctx.lib.ltm_outliers_split_scanset(self.ctx.h, self.h, scans_or_cloud.h, C.byref(a), C.byref(b)))
+            return ScanSet(self.ctx, a.value), ScanSet(self.ctx, b.value)
+        cloud = scans_or_cloud if isinstance(scans_or_cloud, Cloud) else self.ctx.upload(_xyzi(scans_or_cloud))
+        self.ctx._ck(self.ctx.lib.ltm_outliers_split_cloud(self.ctx.h, self.h, cloud.h, C.byref(a), C.byref(b)))
+        return Cloud(self.ctx, a.value), Cloud(self.ctx, b.value)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ltm_outliers_free(self.ctx.h, self.h)
         self.h = None
 
     def __enter__(self):

@@ -297,6 +297,7 @@ void ltm_destroy(ltm_ctx* c)
     sc_release_all(c);
     cluster_release_all(c);
     plane_release_all(c);
+    outlier_release_all(c);
     for (Pending& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }

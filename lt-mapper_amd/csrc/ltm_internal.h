@@ -332,6 +332,8 @@ struct ltm_ctx {
     uint64_t cluster_stats[6] = {0, 0, 0, 0, 0, 0};      // ltm_debug_cluster_stats: pairs tested, edges found, leaves visited, clique leaves, clique early exits, hook retries
     std::vector<struct ltm_planes*> plane_open;             // plane sets (ltm_scanset_segment_planes, ltm_cloud_segment_plane) not freed yet: released by ltm_destroy at the latest
     unsigned long long* plane_stats_dev = nullptr;          // device, 4 counters (ltm_debug_plane_stats): the segmentation reads nothing back, so they are kept there; made on first use
+    std::vector<struct ltm_outliers*> outlier_open;         // outlier sets (ltm_search_filter_statistical, ltm_search_filter_radius) not freed yet: released by ltm_destroy at the latest
+    unsigned long long* outlier_stats_dev = nullptr;        // device, 4 counters (ltm_debug_outlier_stats): the filters read nothing back; made on first use
 };
 
 namespace ltm_detail {
@@ -721,6 +723,7 @@ const float4* search_normals(ltm_ctx* c, struct ltm_search* s, int* k);         
 void sc_release_all(ltm_ctx* c);                                                  // ltm_api_scancontext.cpp: open descriptor sets, at ltm_destroy
 void cluster_release_all(ltm_ctx* c);                                             // ltm_api_cluster.cpp: open cluster sets, at ltm_destroy
 void plane_release_all(ltm_ctx* c);                                               // ltm_api_plane.cpp: open plane sets and the device counters, at ltm_destroy
+void outlier_release_all(ltm_ctx* c);                                             // ltm_api_outlier.cpp: open outlier sets and the device counters, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp
 

@@ -373,6 +373,28 @@ static_assert(sizeof(PlaneRec) == 32 && sizeof(PlaneHyp) == 64 && sizeof(PlaneOu
 hipError_t plane_segment(const PlaneRec* recs, const uint32_t* block_rec, uint32_t n_blocks, uint32_t n_recs, const PlaneLaunch& L, PlaneHyp* hyp, uint8_t* valid,
                          uint32_t* counts, double* partials, PlaneOut* out, uint8_t* labels, unsigned long long* stats4, hipStream_t s);
 
+// ---- outlier filters over the targets of search indices (ltm_k_outlier.hip; include/ltm.h "outlier filters") ----
+static constexpr int kOutlierBlock = 256;       // finite target points per workgroup: distance lists in registers (at most 16 slots), radius counts
+static constexpr int kOutlierBlockLds = 64;     // ... distance lists in LDS (17 .. 64 slots): one wavefront
+static constexpr int kOutlierMaxSlots = 64;     // mean_k + 1 at most: the limit of ltm_knn_search
+static constexpr int kOutlierChunk = 256;       // original positions per partial sum of the record statistics: the chunk of "clusters"
+// one listed index of the batch: its tree, its slice [tbase, tbase + n_target) of the call's per-position arrays (labels, distances or counts); span: its
+// workgroups over its finite points, tspan: its chunks (tspan.block0 is its first chunk among the call's partial sums)
+struct OutlierSeg { SearchTree t; uint64_t tbase; uint32_t n_target, pad; BlockSpan span, tspan; };
+// what a record ends with: the statistics (statistical filter; zeros for the radius filter) and the labels set
+struct OutlierRec { double mean, stddev, threshold; uint32_t n_kept, pad; };
+static_assert(sizeof(OutlierRec) == 32, "the outlier record keeps its size");
+int        outlier_sor_block(int mean_k);       // finite points per workgroup of the distance kernel that mean_k selects
+// The fixed launch sequence of ltm_search_filter_statistical for n_recs indices (dist and labels zeroed by the caller): rows, distances, moments, combine,
+// labels.  block_seg: the owner table over finite points, outlier_sor_block(mean_k) per workgroup; chunk_seg: the owner table over chunks; partials: two
+// doubles per chunk; stats4 += finite points, distance evaluations, (radius walks stopped early,) records
+hipError_t outlier_statistical(const OutlierSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, const uint32_t* chunk_seg, uint32_t n_chunks, uint32_t n_recs,
+                               int mean_k, double stddev_mul, float* dist, double* partials, OutlierRec* out, uint8_t* labels, unsigned long long* stats4,
+                               hipStream_t s);
+// ltm_search_filter_radius (counts and labels zeroed by the caller): rows, counts.  block_seg: kOutlierBlock finite points per workgroup
+hipError_t outlier_radius(const OutlierSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint32_t n_recs, float r2, uint32_t min_neighbors,
+                          uint32_t* counts, OutlierRec* out, uint8_t* labels, unsigned long long* stats4, hipStream_t s);
+
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
 // one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; 256 points per workgroup
 struct SubmapPiece { uint64_t src, dst; uint32_t n, affine; BlockSpan span; };
