@@ -296,7 +296,10 @@ int ltm_knn_split_cloud(ltm_ctx*, ltm_cloud target, ltm_cloud query, int k, floa
  *  - indices: int32 positions in the target cloud as it was given (the target must have fewer than 2^31 points);
  *  - target points with a non-finite coordinate are never returned; a query with one gets an empty row (all -1 for kNN, length 0 for radius);
  *    an empty target is valid and gives empty rows.
- * The result is exact for any distribution of points (the index is a tree of boxes over the target in Morton order, see ltm_k_search.hip).
+ * The result is exact for any distribution and any magnitude of finite points (the index is a tree of boxes over the target in Morton order, see
+ * ltm_k_search.hip): it is what a scan of all finite target points in the float arithmetic above gives, also where that arithmetic underflows (a
+ * cloud inside 1e-23 m has all distances 0 and every row is the k smallest indices), gives denormals, or overflows (a distance of +inf is a
+ * distance like any other for kNN, ordered by index behind the finite ones, and is outside every radius, radius = +inf included).
  * Everything is asynchronous on the context's stream except ltm_radius_search, which reads the total hit count back.  The index and the
  * results come from the context's pool; the index keeps its own copy of the target (the cloud may be freed or changed afterwards).  Handles
  * belong to the context that made them (another context, a lane included, gets LTM_E_INVALID); ltm_destroy releases whatever is still open. */

@@ -10,9 +10,11 @@
 // unbounded for clusters kilometres apart or queries far outside the map -- the box tree's is not.
 //
 // Exactness: the distance of a returned pair is FLANN's L2_Simple in float, ((dx*dx)+dy*dy)+dz*dz without contraction (sqdist_l2simple);
-// a box is skipped only when the lower bound of the distance to it, computed in double and shrunk by a relative 1e-6 (the float
-// evaluation is within 3e-7 relative of the exact value), is STRICTLY above the current k-th distance (kNN) or not below r2 (radius): no
-// point that could enter the result, a tie included, is ever skipped.  Ties are ordered by the smaller target index.
+// a box is skipped only when the lower bound of the distance to it (box_lower_bound, ltm_box_bound.h: computed in double, shrunk by a relative
+// 1e-6 because the float evaluation is within 3e-7 relative of the exact value, then by an absolute 2^-148 because a square that underflows
+// loses up to 2^-150 whatever its size, clamped at 0) is STRICTLY above the current k-th distance (kNN) or not below r2 (radius): no point
+// that could enter the result, a tie included, is ever skipped, down to clouds so small that every float distance is 0 and up to
+// coordinates whose distances overflow to +inf (which sort last, by index).  Ties are ordered by the smaller target index.
 #include "ltm_kernels_common.h"
 #include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves, seg_order_by_code
 #include <rocprim/device/device_radix_sort.hpp>

@@ -4,6 +4,7 @@
 // for its correspondences).  Everything has internal linkage: each unit that includes this gets its own copies, inlined into its kernels.
 #pragma once
 #include "ltm_kernels_common.h"
+#include "ltm_box_bound.h"
 namespace ltm {
 namespace {
 
@@ -21,14 +22,11 @@ __device__ __forceinline__ uint64_t search_key(const SearchFrame& f, float x, fl
 // (d, i) goes before (bd, bi): smaller distance, then smaller target index
 __device__ __forceinline__ bool pair_less(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
 
-// lower bound of the squared distance from q to the node's box (double; +inf for an empty box)
+// lower bound of the float squared distance from q to every point of the node's box (double; +inf for an empty box): ltm_box_bound.h
 __device__ __forceinline__ double box_lb(const float4* __restrict__ box, uint32_t node, float qx, float qy, float qz)
 {
     const float4 lo = box[2 * node], hi = box[2 * node + 1];
-    const double gx = fmax(fmax((double)lo.x - (double)qx, (double)qx - (double)hi.x), 0.0);
-    const double gy = fmax(fmax((double)lo.y - (double)qy, (double)qy - (double)hi.y), 0.0);
-    const double gz = fmax(fmax((double)lo.z - (double)qz, (double)qz - (double)hi.z), 0.0);
-    return (gx * gx + gy * gy + gz * gz) * (1.0 - 1.0e-6);
+    return box_lower_bound(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, qx, qy, qz);
 }
 
 // Stackless depth-first walk of the implicit tree.  skip(lb) decides with the CURRENT state of the caller's result; leaves in

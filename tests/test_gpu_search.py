@@ -124,7 +124,7 @@ def test_knn_and_radius_exact_against_brute_force(gpu_ctx, kind):
             _check_knn(idx, d2, q, t, k)
         _, bd, fin_q = _brute(q, t)
         for frac in (0.1, 0.5):      # radii that cut through the clusters: the 10 % / 50 % quantile of the 5th-neighbour distance
-            r = float(np.sqrt(np.quantile(bd[fin_q, 4].astype(np.float64), frac))) + 1e-3
+            r = float(np.float32(float(np.sqrt(np.quantile(bd[fin_q, 4].astype(np.float64), frac))) + 1e-3))      # a float: both sides square the same number
             _check_radius(s.radius(qc, r), q, t, r)
             _check_radius(s.radius(qc, r, max_nn=3), q, t, r, max_nn=3)
         _check_radius(s.radius(qc, 0.0), q, t, 0.0)
