@@ -25,24 +25,18 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
     BlockTable table;
     uint64_t total_f = 0, total_t = 0;
     out.resize(n_idx);
-    for (size_t k = 0; k < n_idx; ++k) {
+    for_listed_indices(c, n_idx, idx, table, kClusterBlock, false, "the indices of one ltm_search_cluster must have fewer than 2^31 target points in all",
+                       "too many target points in one ltm_search_cluster", [&](size_t k, const ListedIndex& L) {
         ClusterSeg& S = segs[k];
         memset(&S, 0, sizeof S);
-        SearchFrame f;
-        search_view(c, idx[k], &S.t, &f);      // refuses a handle that is not an index of this context
-        size_t nt = 0;
-        if (ltm_search_info(c, idx[k], &nt, nullptr) != LTM_OK) throw Err{LTM_E_INVALID, c->err};
-        S.n_target = (uint32_t)nt;
-        S.fbase = total_f; S.tbase = total_t;
+        S.t = L.t; S.n_target = L.n_target; S.fbase = L.fbase; S.tbase = L.tbase; S.span = L.span;
         while (((uint32_t)1 << S.logP) < S.t.P) ++S.logP;
-        if (!table.add((uint32_t)k, S.t.Mf, kClusterBlock, &S.span)) throw Err{LTM_E_UNSUPPORTED, "too many target points in one ltm_search_cluster"};
-        total_f += S.t.Mf; total_t += nt;
+        total_f += S.t.Mf; total_t += L.n_target;
         out[k].reset(new ltm_clusters);
         out[k]->owner = c;
         out[k]->batch = batch;
-        out[k]->n_target = nt;
-    }
-    if (total_t >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, "the indices of one ltm_search_cluster must have fewer than 2^31 target points in all"};
+        out[k]->n_target = L.n_target;
+    });
     const uint32_t n_blocks = table.size();
     int32_t* labels = batch->alloc<int32_t>(total_t);
     LTM_HIP(fill_u32(reinterpret_cast<uint32_t*>(labels), 0xffffffffu, total_t, c->stream));

@@ -47,22 +47,17 @@ std::unique_ptr<ltm_outliers> open_batch(ltm_ctx* c, size_t n_idx, ltm_search* c
     P->bounds.assign(n_idx + 1, 0);
     P->n_finite.assign(n_idx, 0);
     B.segs.resize(n_idx);
-    for (size_t k = 0; k < n_idx; ++k) {
+    const char* over_table = "too many target points in one outlier filter call";
+    for_listed_indices(c, n_idx, idx, B.points, per_block, true, "the indices of one outlier filter call must have fewer than 2^31 target points in all", over_table,
+                       [&](size_t k, const ListedIndex& L) {
         OutlierSeg& S = B.segs[k];
         memset(&S, 0, sizeof S);
-        SearchFrame f;
-        search_view(c, idx[k], &S.t, &f);      // refuses a handle that is not an index of this context
-        size_t nt = 0;
-        if (ltm_search_info(c, idx[k], &nt, nullptr) != LTM_OK) throw Err{LTM_E_INVALID, c->err};
-        S.n_target = (uint32_t)nt;
-        S.tbase = P->bounds[k];
-        P->bounds[k + 1] = P->bounds[k] + nt;
+        S.t = L.t; S.n_target = L.n_target; S.tbase = L.tbase; S.span = L.span;
+        P->bounds[k + 1] = L.tbase + L.n_target;
         P->n_finite[k] = S.t.Mf;
         B.total_f += S.t.Mf;
-        if (P->bounds[k + 1] >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, "the indices of one outlier filter call must have fewer than 2^31 target points in all"};
-        if (!B.points.add((uint32_t)k, S.t.Mf, per_block, &S.span) || !B.chunks.add((uint32_t)k, nt, kOutlierChunk, &S.tspan))
-            throw Err{LTM_E_UNSUPPORTED, "too many target points in one outlier filter call"};
-    }
+        if (!B.chunks.add((uint32_t)k, L.n_target, kOutlierChunk, &S.tspan)) throw Err{LTM_E_UNSUPPORTED, over_table};
+    });
     return P;
 }
 

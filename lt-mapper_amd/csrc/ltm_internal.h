@@ -719,7 +719,31 @@ void vgs_release_all(ltm_ctx* c);                                               
 int voxel_grid_scanset_ordered(ltm_ctx* c, ltm_scanset in, float leaf, int order, ltm_scanset* out);   // ltm_api_voxel.cpp: ltm_voxel_grid_scanset with the order as an argument (1 PCL, 0 input)
 void search_release_all(ltm_ctx* c);                                              // ltm_api_search.cpp: open search indices and results, at ltm_destroy
 void search_view(ltm_ctx* c, struct ltm_search* s, SearchTree* tree, SearchFrame* frame);   // ltm_api_search.cpp: tree and frame of an index OF THIS CONTEXT (throws otherwise)
-const float4* search_normals(ltm_ctx* c, struct ltm_search* s, int* k);             // ltm_api_search.cpp: the normals of an index of this context (aligned with its tree's pts; null and *k = 0: none)
+// The listed indices of one batched call (clusters, outlier filters) as its records, checked before the device is touched: each(k, L) per index in order,
+// L.span its workgroups of per_block finite points in `table`.  Throws what search_view refuses, `over_table` when the table is full and `over_2_31` when
+// the targets of the call reach 2^31: per index before its table entry (limit_first, the outlier filters) or behind the last index (clusters), as each
+// entry point always did
+struct ListedIndex { SearchTree t; uint32_t n_target; uint64_t fbase, tbase; BlockSpan span; };      // fbase, tbase: the finite / all target points before it
+template <class Each>
+void for_listed_indices(ltm_ctx* c, size_t n_idx, struct ltm_search* const* idx, BlockTable& table, uint32_t per_block, bool limit_first,
+                        const char* over_2_31, const char* over_table, Each each)
+{
+    uint64_t total_f = 0, total_t = 0;
+    for (size_t k = 0; k < n_idx; ++k) {
+        ListedIndex L{};
+        SearchFrame f;
+        size_t nt = 0;
+        search_view(c, idx[k], &L.t, &f);      // refuses a handle that is not an index of this context
+        if (ltm_search_info(c, idx[k], &nt, nullptr) != LTM_OK) throw Err{LTM_E_INVALID, c->err};
+        L.n_target = (uint32_t)nt; L.fbase = total_f; L.tbase = total_t;
+        total_f += L.t.Mf; total_t += nt;
+        if (limit_first && total_t >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, over_2_31};
+        if (!table.add((uint32_t)k, L.t.Mf, per_block, &L.span)) throw Err{LTM_E_UNSUPPORTED, over_table};
+        each(k, L);
+    }
+    if (total_t >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, over_2_31};
+}
+const float4* search_normals(ltm_ctx* c, struct ltm_search* s, int* k);            // ltm_api_search.cpp: the normals of an index of this context (aligned with its tree's pts; null and *k = 0: none)
 void sc_release_all(ltm_ctx* c);                                                  // ltm_api_scancontext.cpp: open descriptor sets, at ltm_destroy
 void cluster_release_all(ltm_ctx* c);                                             // ltm_api_cluster.cpp: open cluster sets, at ltm_destroy
 void plane_release_all(ltm_ctx* c);                                               // ltm_api_plane.cpp: open plane sets and the device counters, at ltm_destroy

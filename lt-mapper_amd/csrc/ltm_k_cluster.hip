@@ -65,13 +65,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
     return v;
 }
-// the counters' form: a thread's count fits 32 bits (fewer than 2^31 positions below it), the sum over 64 lanes need not
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 __device__ __forceinline__ uint32_t wave_min(uint32_t v)
 {
 #pragma unroll

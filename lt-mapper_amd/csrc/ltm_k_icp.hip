@@ -18,9 +18,8 @@
 // points are read in place in its own order, and the record (same layout as the plane record) holds the normal equations weighted per correspondence by
 // the inverse of the two regularised covariances the normals imply; the update kernel's plane instantiation serves it unchanged.
 #include "ltm_kernels_common.h"
-#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves, seg_order_by_code
+#include "ltm_search_walk.h"      // search_key, knn_collect, seg_order_by_code
 #include <cfloat>
-#include <climits>
 namespace ltm {
 
 namespace {
@@ -204,22 +203,11 @@ k_icp_correspond(const IcpPair* __restrict__ pairs, const IcpState* __restrict__
             // a transform that overflows float leaves no query: the point is skipped like a non-finite source point
             if (finite3(qx, qy, qz)) {
                 const SearchTree t = P.t;
-                float bd = __builtin_inff();
-                int bi = INT_MAX;
-                uint32_t bj = 0;
-                auto visit = [&](uint32_t l) {
-                    const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
-                    for (uint32_t j = a; j < b; ++j) {
-                        const float4 tp = t.pts[j];
-                        const float d = sqdist_l2simple(qx, qy, qz, tp.x, tp.y, tp.z);
-                        const int i = (int)t.idx[j];
-                        if (pair_less(d, i, bd, bi)) { bd = d; bi = i; bj = j; }
-                    }
-                };
-                uint32_t sa, sb;
-                seed_leaves(t, search_key(P.f, qx, qy, qz), 1u, sa, sb);
-                for (uint32_t l = sa; l <= sb; ++l) visit(l);
-                walk(t, qx, qy, qz, sa, sb, [&](double lb) { return lb > (double)bd; }, visit);
+                KnnListReg<1> best; best.init(1);      // the nearest target point: distance, target index (INT_MAX: none), sorted position
+                knn_collect(t, search_key(P.f, qx, qy, qz), 1u, qx, qy, qz, best.slots());
+                const float bd = best.d[0];
+                const int bi = best.w0[0];
+                const uint32_t bj = best.w1[0];
                 if constexpr (SCORE) {
                     if (bi != INT_MAX) { v[0] = 1.0; v[1] = (double)bd; }
                 } else if constexpr (MODE == kIcpPlane) {

@@ -8,9 +8,8 @@
 // ascending (d2, index) order -- in registers for k <= 16, in LDS [slot][lane] with one wavefront per workgroup above -- and the moments are summed in
 // that order in double, so a normal depends on its index alone: no atomics, nothing that depends on the walk or on the rest of the batch.
 #include "ltm_kernels_common.h"
-#include "ltm_search_walk.h"      // pair_less, walk, seed_leaves
+#include "ltm_search_walk.h"      // pair_less (ltm_knn_list.h), walk, seed_leaves
 #include "ltm_covariance.h"       // smallest_axis_from_moments: covariance, cyclic Jacobi, canonical sign
-#include <climits>
 namespace ltm {
 
 namespace {
@@ -50,7 +49,9 @@ __device__ __forceinline__ float4 nan4()
 
 } // namespace
 
-// KT in {4, 8, 16}: the lists in registers, kept sorted by the insertion network of k_knn_search_reg (sentinels of distance -1 in the first KT - kk slots)
+// (Both kernels write out the list of ltm_knn_list.h and the collect of ltm_search_walk.h: on knn_collect they ran 3 to 16 % slower)
+// KT in {4, 8, 16}: the lists in registers, kept sorted by the insertion network of KnnListReg (ltm_knn_list.h) with two payload words, written out here
+// (sentinels of distance -1 in the first KT - kk slots)
 template <int KT>
 __global__ void __launch_bounds__(kNormalsBlockReg)
 k_normals_reg(const NormalsSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, int k)
@@ -145,16 +146,17 @@ k_normals_lds(const NormalsSeg* __restrict__ segs, const uint32_t* __restrict__ 
     S.out[j0] = normal_from_moments(M, cnt, qp, S.vp);
 }
 
-int normals_block(int k) { return k > 16 ? kNormalsBlockLds : kNormalsBlockReg; }
+int normals_block(int k) { return k > kKnnListRegSlots ? kNormalsBlockLds : kNormalsBlockReg; }
 
 hipError_t estimate_normals(const NormalsSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, int k, hipStream_t s)
 {
     if (!n_blocks) return hipSuccess;
     if (k < 3 || k > kNormalsMaxK) return hipErrorInvalidValue;
-    if (k > 16) k_normals_lds<<<dim3(n_blocks), dim3(kNormalsBlockLds), 0, s>>>(segs, block_seg, k);
-    else if (k <= 4) k_normals_reg<4><<<dim3(n_blocks), dim3(kNormalsBlockReg), 0, s>>>(segs, block_seg, k);
-    else if (k <= 8) k_normals_reg<8><<<dim3(n_blocks), dim3(kNormalsBlockReg), 0, s>>>(segs, block_seg, k);
-    else k_normals_reg<16><<<dim3(n_blocks), dim3(kNormalsBlockReg), 0, s>>>(segs, block_seg, k);
+    knn_list_dispatch<false>(k, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if constexpr (KT == 0) k_normals_lds<<<dim3(n_blocks), dim3(kNormalsBlockLds), 0, s>>>(segs, block_seg, k);
+        else k_normals_reg<KT><<<dim3(n_blocks), dim3(kNormalsBlockReg), 0, s>>>(segs, block_seg, k);
+    });
     return hipGetLastError();
 }
 

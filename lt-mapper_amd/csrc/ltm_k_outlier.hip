@@ -18,32 +18,14 @@
 //                    as soon as min_neighbors are counted; count and label at the original position, n_kept as above
 // No floating-point atomics: every value is a function of its record and the parameters alone.  Non-finite positions keep the zeros of the preceding fill.
 #include "ltm_kernels_common.h"
-#include "ltm_search_walk.h"      // walk, seed_leaves
+#include "ltm_search_walk.h"      // walk, seed_leaves, for_leaf_points
 namespace ltm {
-
-namespace {
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t ballot_count(bool b) { return (uint32_t)__popcll(__ballot(b)); }
-
-// the counters of a thread into the call's: one atomic per wavefront and counter
-__device__ __forceinline__ void count_up(unsigned long long* __restrict__ stats, int slot, uint32_t v)
-{
-    const unsigned long long s = wave_sum64(v);
-    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(stats + slot, s);
-}
 
 // d_i from the ascending list: S = sum of sqrt((double)d2) past the first slot, in order; (float)(S / mean_k)
 __device__ __forceinline__ double sor_term(float d2) { return sqrt((double)d2); }
 
-} // namespace
-
-// KT in {4, 8, 16} slots of one float, kept ascending by the insertion network of k_normals_reg without its index words (sentinels of distance -1 in the
+// KT in {4, 8, 16} slots of one float, kept ascending by the insertion network of KnnListReg (ltm_knn_list.h) without its index words, written out here like the
+// LDS form below (on knn_collect: 1.1 % slower per batch, 4.6 % with one call per index) (sentinels of distance -1 in the
 // first KT - kk slots).  A candidate equal to the last slot is not inserted: it would change nothing
 template <int KT>
 __global__ void __launch_bounds__(kOutlierBlock)
@@ -94,7 +76,7 @@ k_sor_distances_reg(const OutlierSeg* __restrict__ segs, const uint32_t* __restr
     count_up(stats, 1, evals);
 }
 
-// 17 .. 64 slots: the lists in LDS, [slot][lane], one wavefront per workgroup (64 x 64 x 4 B = 16 KB)
+// 17 .. 64 slots: the lists in LDS, [slot][lane], one wavefront per workgroup (64 x 64 x 4 B = 16 KB) (on knn_collect: 1.4 % slower)
 __global__ void __launch_bounds__(kOutlierBlockLds)
 k_sor_distances_lds(const OutlierSeg* __restrict__ segs, const uint32_t* __restrict__ block_seg, int mean_k, float* __restrict__ dist,
                     unsigned long long* __restrict__ stats)
@@ -239,13 +221,12 @@ k_ror_count(const OutlierSeg* __restrict__ segs, const uint32_t* __restrict__ bl
     if (active) {
         const float4 qp = t.pts[j0];
         uint32_t cnt = 0;
-        auto visit = [&](uint32_t l) {
-            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
-            for (uint32_t j = a; j < b && cnt < min_neighbors; ++j) {
-                const float4 p = t.pts[j];
+        auto visit = [&](uint32_t l) {      // entered with cnt < min_neighbors only: the walk refuses every node once they are reached
+            for_leaf_points(t, l, qp.x, qp.y, qp.z, [&](uint32_t, const float4&, float d) {
                 ++evals;
-                if (sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z) < r2) ++cnt;
-            }
+                if (d < r2) ++cnt;
+                return cnt < min_neighbors;
+            });
         };
         const uint32_t own = j0 / kSearchLeaf;
         visit(own);      // the point itself is in it
@@ -267,7 +248,7 @@ k_ror_count(const OutlierSeg* __restrict__ segs, const uint32_t* __restrict__ bl
     count_up(stats, 2, early);
 }
 
-int outlier_sor_block(int mean_k) { return mean_k + 1 > 16 ? kOutlierBlockLds : kOutlierBlock; }
+int outlier_sor_block(int mean_k) { return mean_k + 1 > kKnnListRegSlots ? kOutlierBlockLds : kOutlierBlock; }
 
 hipError_t outlier_statistical(const OutlierSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, const uint32_t* chunk_seg, uint32_t n_chunks, uint32_t n_recs,
                                int mean_k, double stddev_mul, float* dist, double* partials, OutlierRec* out, uint8_t* labels, unsigned long long* stats4,
@@ -278,15 +259,16 @@ hipError_t outlier_statistical(const OutlierSeg* segs, const uint32_t* block_seg
     const int slots = mean_k + 1;
     k_outlier_rows<<<dim3(grid_for(n_recs, kOutlierBlock)), dim3(kOutlierBlock), 0, s>>>(n_recs, out, stats4);
     if (n_blocks) {
-        if (slots > 16) k_sor_distances_lds<<<dim3(n_blocks), dim3(kOutlierBlockLds), 0, s>>>(segs, block_seg, mean_k, dist, stats4);
-        else if (slots <= 4) k_sor_distances_reg<4><<<dim3(n_blocks), dim3(kOutlierBlock), 0, s>>>(segs, block_seg, mean_k, dist, stats4);
-        else if (slots <= 8) k_sor_distances_reg<8><<<dim3(n_blocks), dim3(kOutlierBlock), 0, s>>>(segs, block_seg, mean_k, dist, stats4);
-        else k_sor_distances_reg<16><<<dim3(n_blocks), dim3(kOutlierBlock), 0, s>>>(segs, block_seg, mean_k, dist, stats4);
+        knn_list_dispatch<false>(slots, [&](auto kt) {
+            constexpr int KT = decltype(kt)::value;
+            if constexpr (KT == 0) k_sor_distances_lds<<<dim3(n_blocks), dim3(kOutlierBlockLds), 0, s>>>(segs, block_seg, mean_k, dist, stats4);
+            else k_sor_distances_reg<KT><<<dim3(n_blocks), dim3(kOutlierBlock), 0, s>>>(segs, block_seg, mean_k, dist, stats4);
+        });
     }
     if (n_chunks) k_sor_moments<<<dim3(n_chunks), dim3(kOutlierChunk), 0, s>>>(segs, chunk_seg, dist, partials);
     k_sor_combine<<<dim3(n_recs), dim3(64), 0, s>>>(segs, stddev_mul, partials, out);
     if (n_blocks) {
-        if (slots > 16) k_sor_labels<kOutlierBlockLds><<<dim3(n_blocks), dim3(kOutlierBlockLds), 0, s>>>(segs, block_seg, dist, out, labels);
+        if (slots > kKnnListRegSlots) k_sor_labels<kOutlierBlockLds><<<dim3(n_blocks), dim3(kOutlierBlockLds), 0, s>>>(segs, block_seg, dist, out, labels);
         else k_sor_labels<kOutlierBlock><<<dim3(n_blocks), dim3(kOutlierBlock), 0, s>>>(segs, block_seg, dist, out, labels);
     }
     return hipGetLastError();

@@ -32,7 +32,6 @@ __device__ __forceinline__ uint32_t plane_mix(uint32_t seed, uint32_t h, uint32_
 __device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool finite3(const float4& p) { return finite_f(p.x) && finite_f(p.y) && finite_f(p.z); }
 __device__ __forceinline__ bool finite_d(double v) { return (((uint64_t)__double_as_longlong(v) >> 52) & 0x7ffull) != 0x7ffull; }
-__device__ __forceinline__ uint32_t ballot_count(bool b) { return (uint32_t)__popcll(__ballot(b)); }
 
 // (a, b, c, d) of the unit normal n through point c0, with the canonical sign: towards the axis if there is one and n . A != 0, else the component of
 // largest magnitude positive (the lower axis among equals)

@@ -16,12 +16,11 @@
 // that could enter the result, a tie included, is ever skipped, down to clouds so small that every float distance is 0 and up to
 // coordinates whose distances overflow to +inf (which sort last, by index).  Ties are ordered by the smaller target index.
 #include "ltm_kernels_common.h"
-#include "ltm_search_walk.h"      // search_key, pair_less, box_lb, walk, seed_leaves, seg_order_by_code
+#include "ltm_search_walk.h"      // search_key, pair_less (ltm_knn_list.h), walk, seed_leaves, for_leaf_points, seg_order_by_code
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
-#include <climits>
 namespace ltm {
 
 // ------------------------------------------------------------------------------------------------------------- build
@@ -74,7 +73,7 @@ k_search_leaf_boxes(const float4* __restrict__ pts, uint32_t Mf, uint32_t L, uin
     const float inf = __builtin_inff();
     float4 lo = make_float4(inf, inf, inf, 0.0f), hi = make_float4(-inf, -inf, -inf, 0.0f);
     if (l < L) {
-        const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, Mf);
+        uint32_t a, b; leaf_span(l, Mf, a, b);
         for (uint32_t j = a; j < b; ++j) {
             const float4 p = pts[j];
             lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
@@ -179,7 +178,7 @@ k_search_tree_boxes_seg(const SearchSeg* __restrict__ segs, const float4* __rest
     for (uint32_t l = threadIdx.x; l < P; l += kTreeBlock) {
         float4 lo = make_float4(inf, inf, inf, 0.0f), hi = make_float4(-inf, -inf, -inf, 0.0f);
         if (l < L) {
-            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, Mf);
+            uint32_t a, b; leaf_span(l, Mf, a, b);
             for (uint32_t j = a; j < b; ++j) {
                 const float4 p = pts[j];
                 lo.x = fminf(lo.x, p.x); lo.y = fminf(lo.y, p.y); lo.z = fminf(lo.z, p.z);
@@ -218,6 +217,8 @@ hipError_t search_query_order(const float4* query, size_t n, SearchFrame f, uint
 }
 
 // ----------------------------------------------------------------------------------------------------------- kNN
+// (These two kernels write out the list of ltm_knn_list.h and the collect of ltm_search_walk.h: built on knn_collect they gave the same bytes from the same
+// registers and ran 11 % (k = 8) to 15 % (k = 32) slower, DESIGN.md 4.4a.  tests/test_gpu_knn_list_consumers.py holds the copies together.)
 // KT in {1, 2, 4, 8, 16}: the KT best (d2, index) pairs live in registers, kept sorted by an insertion network.  For kk < KT the first
 // KT - kk slots hold a sentinel of distance -1 that every candidate sorts after, so slot KT-1 is always the kk-th distance.
 template <int KT>
@@ -271,7 +272,6 @@ k_knn_search_reg(const float4* __restrict__ query, size_t n, const uint32_t* __r
 
 // 16 < k <= 64: the lists in LDS, [slot][lane] (one wavefront per workgroup: 64 x 64 x 8 B = 32 KB)
 static constexpr int kLdsBlock = 64;
-static constexpr int kMaxSearchK = 64;
 __global__ void __launch_bounds__(kLdsBlock)
 k_knn_search_lds(const float4* __restrict__ query, size_t n, const uint32_t* __restrict__ order, const uint64_t* __restrict__ qkeys_sorted,
                  SearchTree t, int k, int kk, int32_t* __restrict__ out_idx, float* __restrict__ out_d2)
@@ -320,18 +320,11 @@ hipError_t knn_search(const float4* query, size_t n, const uint32_t* order, cons
     if (!n) return hipSuccess;
     if (k < 1 || k > kMaxSearchK) return hipErrorInvalidValue;
     const int kk = (int)std::min<size_t>((size_t)k, t.Mf);
-    if (k > 16) {
-        k_knn_search_lds<<<dim3(grid_for(n, kLdsBlock)), dim3(kLdsBlock), 0, s>>>(query, n, order, qkeys_sorted, t, k, kk, out_idx, out_d2);
-        return hipGetLastError();
-    }
-    auto launch = [&](auto kt) {
-        k_knn_search_reg<decltype(kt)::value><<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(query, n, order, qkeys_sorted, t, k, kk, out_idx, out_d2);
-    };
-    if (k == 1) launch(std::integral_constant<int, 1>{});
-    else if (k == 2) launch(std::integral_constant<int, 2>{});
-    else if (k <= 4) launch(std::integral_constant<int, 4>{});
-    else if (k <= 8) launch(std::integral_constant<int, 8>{});
-    else launch(std::integral_constant<int, 16>{});
+    knn_list_dispatch<true>(k, [&](auto kt) {
+        constexpr int KT = decltype(kt)::value;
+        if constexpr (KT == 0) k_knn_search_lds<<<dim3(grid_for(n, kLdsBlock)), dim3(kLdsBlock), 0, s>>>(query, n, order, qkeys_sorted, t, k, kk, out_idx, out_d2);
+        else k_knn_search_reg<KT><<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(query, n, order, qkeys_sorted, t, k, kk, out_idx, out_d2);
+    });
     return hipGetLastError();
 }
 
@@ -347,11 +340,7 @@ k_radius_count(const float4* __restrict__ query, size_t n, const uint32_t* __res
     uint32_t c = 0;
     if (t.Mf && finite3(qp.x, qp.y, qp.z)) {
         walk(t, qp.x, qp.y, qp.z, 1u, 0u, [&](double lb) { return lb >= (double)r2; }, [&](uint32_t l) {
-            const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
-            for (uint32_t j = a; j < b; ++j) {
-                const float4 p = t.pts[j];
-                c += sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z) < r2 ? 1u : 0u;
-            }
+            for_leaf_points(t, l, qp.x, qp.y, qp.z, [&](uint32_t, const float4&, float d) { c += d < r2 ? 1u : 0u; });
         });
     }
     count[qi] = c;
@@ -369,12 +358,9 @@ k_radius_fill(const float4* __restrict__ query, size_t n, const uint32_t* __rest
     const uint64_t end = offsets[qi + 1];
     if (o == end) return;
     walk(t, qp.x, qp.y, qp.z, 1u, 0u, [&](double lb) { return lb >= (double)r2; }, [&](uint32_t l) {
-        const uint32_t a = l * kSearchLeaf, b = min(a + (uint32_t)kSearchLeaf, t.Mf);
-        for (uint32_t j = a; j < b; ++j) {
-            const float4 p = t.pts[j];
-            const float d = sqdist_l2simple(qp.x, qp.y, qp.z, p.x, p.y, p.z);
+        for_leaf_points(t, l, qp.x, qp.y, qp.z, [&](uint32_t j, const float4&, float d) {
             if (d < r2 && o < end) pairs[o++] = ((uint64_t)__float_as_uint(d) << 32) | t.idx[j];
-        }
+        });
     });
 }
 // row q: the first min(count, max_nn) pairs of the sorted row -> idx / d2 at out_off[q]

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "ltm_block_table.h"      // BlockSpan
+#include "ltm_knn_list.h"         // kKnnListSlots
 
 namespace ltm {
 
@@ -263,6 +264,7 @@ hipError_t knn_query_cloud(const float4* query, size_t Q, const float4* sorted_t
 
 // ---- exact k-NN / radius search index (ltm_k_search.hip) ----
 static constexpr int kSearchLeaf = 32;          // target points per leaf of the box tree
+static constexpr int kMaxSearchK = kKnnListSlots;
 // Morton frame of the index: 21 bits per axis, q = floor((v - o) * scale) clamped to [0, 2^21)
 struct SearchFrame { double ox, oy, oz, scale; };
 // finite target points in Morton order (pts, their input indices idx, their codes keys), Mf of them, L = ceil(Mf / kSearchLeaf) leaves,
@@ -313,7 +315,7 @@ hipError_t search_tree_boxes_seg(const SearchSeg* segs, size_t n_segs, const flo
 // ---- normals of the target points of search indices (ltm_k_normals.hip; include/ltm.h "normals") ----
 static constexpr int kNormalsBlockReg = 256;    // target points per workgroup, lists in registers (k <= 16)
 static constexpr int kNormalsBlockLds = 64;     // ... lists in LDS (16 < k <= 64): one wavefront
-static constexpr int kNormalsMaxK = 64;
+static constexpr int kNormalsMaxK = kKnnListSlots;
 // one index of the batch: its tree, where its Mf normals go (aligned with t.pts), the viewpoint; normals_block(k) target points per workgroup
 struct NormalsSeg { SearchTree t; float4* out; double vp[3]; BlockSpan span; };
 int        normals_block(int k);                // target points per workgroup of the kernel that k selects
@@ -376,7 +378,7 @@ hipError_t plane_segment(const PlaneRec* recs, const uint32_t* block_rec, uint32
 // ---- outlier filters over the targets of search indices (ltm_k_outlier.hip; include/ltm.h "outlier filters") ----
 static constexpr int kOutlierBlock = 256;       // finite target points per workgroup: distance lists in registers (at most 16 slots), radius counts
 static constexpr int kOutlierBlockLds = 64;     // ... distance lists in LDS (17 .. 64 slots): one wavefront
-static constexpr int kOutlierMaxSlots = 64;     // mean_k + 1 at most: the limit of ltm_knn_search
+static constexpr int kOutlierMaxSlots = kKnnListSlots;     // mean_k + 1 at most: the limit of ltm_knn_search
 static constexpr int kOutlierChunk = 256;       // original positions per partial sum of the record statistics: the chunk of "clusters"
 // one listed index of the batch: its tree, its slice [tbase, tbase + n_target) of the call's per-position arrays (labels, distances or counts); span: its
 // workgroups over its finite points, tspan: its chunks (tspan.block0 is its first chunk among the call's partial sums)

@@ -207,4 +207,19 @@ __device__ __forceinline__ size_t find_kf(const uint64_t* __restrict__ offsets, 
     return lo;
 }
 
+// the sum over the 64 lanes in 64 bits: a lane's count fits 32 bits, the sum of 64 of them need not
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t ballot_count(bool b) { return (uint32_t)__popcll(__ballot(b)); }
+// the counters of a thread into the call's: one atomic per wavefront and counter
+__device__ __forceinline__ void count_up(unsigned long long* __restrict__ stats, int slot, uint32_t v)
+{
+    const unsigned long long s = wave_sum64(v);
+    if ((threadIdx.x & 63u) == 0u && s) atomicAdd(stats + slot, s);
+}
+
 } // namespace ltm

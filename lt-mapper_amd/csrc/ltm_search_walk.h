@@ -1,10 +1,12 @@
 // ltm_search_walk.h -- the device side of the search index that more than one kernel unit uses: the Morton code of a point under the index's frame,
-// the order of (distance, index) pairs, the lower bound of the distance to a node's box, the stackless walk of the implicit box tree, the kNN seed
-// and the segmented order by code of the batched builds (the index itself is described in ltm_k_search.hip, which builds it; ltm_k_icp.hip walks it
-// for its correspondences).  Everything has internal linkage: each unit that includes this gets its own copies, inlined into its kernels.
+// the lower bound of the distance to a node's box, the stackless walk of the implicit box tree, the scan of a leaf's points, the kNN seed and the
+// collect (seed leaves, then the walk, into a list of ltm_knn_list.h), and the segmented order by code of the batched
+// builds (the index itself is described in ltm_k_search.hip, which builds it; ltm_k_icp.hip walks it for its correspondences).  Everything has
+// internal linkage: each unit that includes this gets its own copies, inlined into its kernels.
 #pragma once
 #include "ltm_kernels_common.h"
 #include "ltm_box_bound.h"
+#include "ltm_knn_list.h"
 namespace ltm {
 namespace {
 
@@ -19,8 +21,6 @@ __device__ __forceinline__ uint64_t search_key(const SearchFrame& f, float x, fl
     if (!finite3(x, y, z)) return ~0ull;
     return morton3(quant21(x, f.ox, f.scale), quant21(y, f.oy, f.scale), quant21(z, f.oz, f.scale));
 }
-// (d, i) goes before (bd, bi): smaller distance, then smaller target index
-__device__ __forceinline__ bool pair_less(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
 
 // lower bound of the float squared distance from q to every point of the node's box (double; +inf for an empty box): ltm_box_bound.h
 __device__ __forceinline__ double box_lb(const float4* __restrict__ box, uint32_t node, float qx, float qy, float qz)
@@ -48,6 +48,23 @@ __device__ __forceinline__ void walk(const SearchTree& t, float qx, float qy, fl
     }
 }
 
+// the sorted positions [a, b) of leaf l of an index of Mf finite points
+__device__ __forceinline__ void leaf_span(uint32_t l, uint32_t Mf, uint32_t& a, uint32_t& b) { a = l * kSearchLeaf; b = min(a + (uint32_t)kSearchLeaf, Mf); }
+// The points of leaf l: f(j, p, d2) with the sorted position, the point and its float distance to q (sqdist_l2simple), in ascending position.  An f that
+// returns bool ends the scan by returning false
+template <class F>
+__device__ __forceinline__ void for_leaf_points(const SearchTree& t, uint32_t l, float qx, float qy, float qz, F f)
+{
+    uint32_t a, b;
+    leaf_span(l, t.Mf, a, b);
+    for (uint32_t j = a; j < b; ++j) {
+        const float4 p = t.pts[j];
+        const float d = sqdist_l2simple(qx, qy, qz, p.x, p.y, p.z);
+        if constexpr (std::is_void_v<decltype(f(j, p, d))>) f(j, p, d);
+        else if (!f(j, p, d)) break;
+    }
+}
+
 // first position in the sorted codes whose code is >= key
 __device__ __forceinline__ uint32_t lower_bound_key(const uint64_t* __restrict__ keys, uint32_t n, uint64_t key)
 {
@@ -67,6 +84,19 @@ __device__ __forceinline__ void seed_leaves(const SearchTree& t, uint64_t qkey, 
     if (start + kk > t.Mf) start = t.Mf - kk;
     a = start / kSearchLeaf;
     b = (start + kk - 1) / kSearchLeaf;
+}
+// The kk nearest target points of q into a KnnListReg (ltm_knn_list.h; initialised by the caller, 1 <= kk <= t.Mf), given as list.slots(): the seed leaves
+// around seed_key, the code of q under the index's frame, then the walk that skips a box only when its bound is STRICTLY above the current kk-th distance
+template <class Slots>
+__device__ __forceinline__ void knn_collect(const SearchTree& t, uint64_t seed_key, uint32_t kk, float qx, float qy, float qz, Slots s)
+{
+    auto visit = [&, s](uint32_t l) {
+        for_leaf_points(t, l, qx, qy, qz, [&, s](uint32_t j, const float4&, float d) { s.push(d, (int)t.idx[j], j); });
+    };
+    uint32_t sa, sb;
+    seed_leaves(t, seed_key, kk, sa, sb);
+    for (uint32_t l = sa; l <= sb; ++l) visit(l);
+    walk(t, qx, qy, qz, sa, sb, [s](double lb) { return lb > (double)s.kth(); }, visit);
 }
 
 // ---------------------------------------------------------------------------------------- segmented order by code
