@@ -800,6 +800,65 @@ int  ltm_outliers_split_scanset(ltm_ctx*, ltm_outliers*, ltm_scanset, ltm_scanse
 int  ltm_outliers_split_cloud(ltm_ctx*, ltm_outliers*, ltm_cloud, ltm_cloud* kept, ltm_cloud* removed);
 int  ltm_outliers_free(ltm_ctx*, ltm_outliers*);
 
+/* -------------------------------------------------------------------- fpfh ---- */
+/* Fast Point Feature Histograms (Rusu, Blodow, Beetz 2009) of the target points of search indices: pcl::FPFHEstimation (setInputCloud, setInputNormals,
+ * setKSearch, compute), 33 floats per point, the local shape descriptor that feature matching and a sample-consensus initial alignment start from.  The
+ * reference does not call it and PCL is not available to compare against; this is what this library takes PCL 1.10's computeFeature, computePairFeatures,
+ * computePointSPFHSignature and weightPointSPFHSignature to do, as understood.  tools/fpfh_numpy.py restates this text in numpy and the tests compare
+ * against that, for equality.
+ *  A RECORD is one listed index (ltm_search_build or ltm_search_build_scanset, mixed freely) that has normals (ltm_search_estimate_normals); the normals
+ *   are the stored (nx, ny, nz) as floats.  A record's result is a function of its index and k alone: it depends neither on the rest of the batch nor on
+ *   the schedule, and there are no floating-point atomics.  Rows are in the target's ORIGINAL order.  2 <= k <= 64.
+ *  NEIGHBOURHOOD of a finite point p: its kk = min(k, n_finite) nearest finite target points in the order of ltm_knn_search (float L2_Simple,
+ *   ((dx*dx)+dy*dy)+dz*dz, ties to the smaller target index), as (d2_j, q_j), j = 0 .. kk - 1.  p is among them unless k or more points coincide with it.
+ *  PAIR FEATURES of (p, q) for every q of the neighbourhood with a different target index, in double with + - * / sqrt only, each rounded once (no
+ *   fused multiply-add); a dot product is (a.x b.x + a.y b.y) + a.z b.z, a cross product a x b = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x):
+ *    1. d = q - p, f4 = sqrt(d.d).  f4 == 0: the pair is skipped.  A q whose normal has a non-finite component: skipped as well.
+ *    2. a1 = (n_p.d) / f4, a2 = (n_q.d) / f4.
+ *    3. |a1| < |a2|: u = n_q, o = n_p, d = -d, phi = -a2; otherwise u = n_p, o = n_q, phi = a1.
+ *    4. v = d x u, vn = sqrt(v.v).  vn == 0: skipped.  v = v / vn (three divisions), w = u x v.
+ *    5. alpha = v.o, y = w.o, x = u.o (theta would be atan2(y, x)).
+ *  BINS, 11 per feature.  alpha and phi: floor(11 ((f + 1) 0.5)) clamped to 0 .. 10.  theta, without a transcendental: the number of boundaries
+ *   theta_j = -pi + 2 pi j / 11, j = 1 .. 10, that the direction (x, y) has reached.  With (c_j, s_j) the doubles nearest (cos theta_j, sin theta_j),
+ *     j  1  (-0.8412535328311811,  -0.5406408174555978)     j  6  ( 0.9594929736144975,   0.2817325568414295)
+ *     j  2  (-0.4154150130018863,  -0.9096319953545184)     j  7  ( 0.6548607339452851,   0.7557495743542583)
+ *     j  3  ( 0.14231483827328512, -0.9898214418809327)     j  8  ( 0.14231483827328512,  0.9898214418809327)
+ *     j  4  ( 0.6548607339452851,  -0.7557495743542583)     j  9  (-0.41541501300188616,  0.9096319953545186)
+ *     j  5  ( 0.9594929736144975,  -0.2817325568414295)     j 10  (-0.8412535328311813,   0.5406408174555974)
+ *   side_j = (c_j y - s_j x >= 0) (two products, one difference) and upper = (the sign bit of y is clear: y > 0 or y == +0).  Boundary j <= 5 is reached
+ *   iff upper or side_j; boundary j >= 6 iff upper and side_j.  x == 0 and y == 0 (either sign): bin 5.  So y == +0 with x < 0 (theta = +pi) is bin 10,
+ *   y == -0 with x < 0 (theta = -pi) is bin 0, y == +-0 with x > 0 is bin 5, as PCL's floor(11 (theta + pi) / (2 pi)), clamped, gives them.  The rule and
+ *   that expression on numpy's arctan2 differ only within 1e-15 rad of a boundary (tests/test_fpfh_cases_cpu.py measures it).
+ *  SPFH of p: 33 integer counts, count[f][b] += 1 per feature f of every pair that was not skipped (at most 63 per feature).  On the device: four 64-bit
+ *   words per point, bins 0 .. 9 of feature f as 6-bit fields of word f (bin b at bit 6 b), the number of counted pairs in word 3; bin 10 is that number
+ *   less the ten fields.  ltm_fpfh_download unpacks them to uint8 [33].
+ *  FPFH of p: S_b = SUM_j (1.0 / (double)d2_j) * (double)count_{q_j}[b], added in list order to 0.0, a j with d2_j == 0 left out (so p's own SPFH is not
+ *   in it, as in weightPointSPFHSignature).  Per group of 11 bins, T = the sum of its S_b in bin order; row[b] = (float)(100.0 * S_b / T), the product
+ *   first; a group with T == 0 stays 0.
+ *  DEGENERATE ROWS: a position with a non-finite coordinate, and a point whose normal has a non-finite component, have 33 NaN floats and zero counts.
+ *   An index with fewer than 3 finite points has NaN normals ("normals"), so a target with fewer than 2 finite points gives NaN rows throughout.
+ *  Domain: a NULL pointer, a NULL handle, a handle of another context (a lane included), an index without normals, the same index listed twice or k
+ *   outside 2 .. 64 is LTM_E_INVALID before the device is touched; no handle is returned (*out = NULL) and every index stays as it was.  An empty index and
+ *   an empty list are valid.  All indices of a call together: fewer than 2^31 target points (LTM_E_UNSUPPORTED beyond).
+ *  DEPARTURES from PCL: step 3 compares |a1| < |a2| where PCL compares acos(|a1|) > acos(|a2|) (different only where the two roundings differ); the
+ *   theta bin by sign tests as above; the SPFH holds counts where PCL adds 100 / (n - 1) in float per pair (the factor is the same for every point of an
+ *   index and cancels in the normalisation); the weighted sums and the normalisation are double, rounded to float once (PCL: float throughout); a pair
+ *   with a non-finite normal is skipped and such a point has a NaN row (PCL requires finite normals); only k neighbourhoods (no setRadiusSearch).
+ * The call handles ALL listed indices in ONE fixed sequence of launches and returns ONE handle with n_idx records; it reads nothing back from the device
+ * (small tables go up) and returns with the launches queued on the context's stream.  Memory comes from the context's pool; the handle keeps no reference
+ * to its indices (either may be freed first, and estimating normals again does not touch it); ltm_destroy releases open handles.  The neighbour lists of
+ * the first pass are kept as scratch for the second where they take at most 16 GiB (8 bytes per finite point and k) and the pool has them; otherwise, and
+ * in a context created with LTM_FPFH_LISTS=0, the second pass collects the neighbourhoods again: the same bytes either way. */
+typedef struct ltm_fpfh ltm_fpfh;
+int  ltm_search_fpfh(ltm_ctx*, size_t n_idx, ltm_search* const* idx, int k, ltm_fpfh** out /* one handle, one record per index */);
+int  ltm_fpfh_info(ltm_ctx*, ltm_fpfh*, size_t* n_records, size_t* n_points /* the records' n_target, summed */, int* k);
+/* the set's device arrays, borrowed until ltm_fpfh_free: record offsets (uint64, n_records + 1: record r has rows [off[r], off[r + 1])), the descriptors
+ * (float, n_points x 33, row-major) and the SPFH words (uint64, n_points x 4, as above).  Any pointer may be NULL */
+int  ltm_fpfh_device(ltm_ctx*, ltm_fpfh*, const uint64_t** offsets_dev, const float** desc_dev /* n_points x 33 */, const void** spfh_dev);
+/* host copies, any pointer may be NULL: per record n_target and n_finite; per position the descriptor and the unpacked counts */
+int  ltm_fpfh_download(ltm_ctx*, ltm_fpfh*, uint32_t* n_target, uint32_t* n_finite, float* desc /* n_points x 33 */, uint8_t* spfh_counts /* n_points x 33, nullable */);
+int  ltm_fpfh_free(ltm_ctx*, ltm_fpfh*);
+
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
  * central and the query session's makeGlobalMap + Step-1 chains (Removerter.cpp:213-252, :1580-1587), their HD kNN maps and static reprojections
@@ -942,6 +1001,9 @@ int ltm_debug_plane_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
 /* counters of the outlier filters since the last reset, stats[4]: finite points processed, point pairs whose distance was evaluated, radius walks that
  * refused a node because min_neighbors had been counted, records.  Counted on the device (the filters read nothing back); this call reads them. */
 int ltm_debug_outlier_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
+/* counters of ltm_search_fpfh since the last reset, stats[4]: finite points processed, point pairs whose distance was evaluated (twice as many where the
+ * second pass collects the neighbourhoods again), pairs skipped as degenerate, points that took the LDS list form (k > 16).  Counted on the device; this call reads them. */
+int ltm_debug_fpfh_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
 /* which kernel forms a Scan Context shape gets (host arithmetic only, needs no device; the launch wrappers' own expressions): *scatter_in_lds = 1 if
  * ltm_sc_from_scanset pre-reduces a block's points in LDS (up to 4096 bins), 0 if it goes straight to device memory; *pair_in_lds = 1 if the pair
  * distance of ltm_sc_distance / ltm_sc_detect stages both descriptors in LDS (up to 60 KB with the keys and norms), 0 if it reads them from device

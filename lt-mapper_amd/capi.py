@@ -218,6 +218,12 @@ SIGNATURES = {
     "ltm_outliers_split_cloud": (_i, [_vp, _vp, _u64, _pu64, _pu64]),
     "ltm_outliers_free": (_i, [_vp, _vp]),
     "ltm_debug_outlier_stats": (_i, [_vp, _pu64, _i]),
+    "ltm_search_fpfh": (_i, [_vp, _sz, C.POINTER(_vp), _i, C.POINTER(_vp)]),
+    "ltm_fpfh_info": (_i, [_vp, _vp, _psz, _psz, C.POINTER(_i)]),
+    "ltm_fpfh_device": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_fpfh_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltm_fpfh_free": (_i, [_vp, _vp]),
+    "ltm_debug_fpfh_stats": (_i, [_vp, _pu64, _i]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -800,6 +806,20 @@ class Context:
         self._ck(self.lib.ltm_debug_outlier_stats(self.h, a, int(reset)))
         return dict(zip(OUTLIER_STATS, [int(v) for v in a]))
 
+    def fpfh(self, indices, k):
+        """ltm_search_fpfh: pcl::FPFHEstimation (setKSearch(k)) over the targets of all `indices` (SearchIndex objects of this context with normals, each at
+        most once) in one sequence of launches; nothing is read back.  Returns one Fpfh with one record per index."""
+        indices, hs = self._outlier_indices(indices, "fpfh")
+        h = _vp()
+        self._ck(self.lib.ltm_search_fpfh(self.h, len(indices), hs, int(k), C.byref(h)))
+        return Fpfh(self, h.value)
+
+    def fpfh_stats(self, reset=False):
+        """ltm_debug_fpfh_stats: dict of the four counters since the last reset"""
+        a = (C.c_uint64 * 4)()
+        self._ck(self.lib.ltm_debug_fpfh_stats(self.h, a, int(reset)))
+        return dict(zip(FPFH_STATS, [int(v) for v in a]))
+
     # ---- loop submaps
     def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
         """ltm_submaps_assemble: Session::loopFindNearKeyframesLocalCoord (affines=None) / CentralCoord (affines: (n_kf, 3, 4) float32, see
@@ -1182,6 +1202,10 @@ class SearchIndex:
         """ltm_search_filter_statistical for this index alone: setMeanK(mean_k), setStddevMulThresh(stddev_mul), filter; an Outliers of one record"""
         return self.ctx.statistical_outliers([self], mean_k, stddev_mul)
 
+    def fpfh(self, k):
+        """ltm_search_fpfh for this index alone: setKSearch(k), compute; an Fpfh of one record (the index needs normals: estimate_normals)"""
+        return self.ctx.fpfh([self], k)
+
     def radius_outliers(self, radius, min_neighbors=1):
         """ltm_search_filter_radius for this index alone: setRadiusSearch(radius), setMinNeighborsInRadius(min_neighbors), filter"""
         return self.ctx.radius_outliers([self], radius, min_neighbors)
@@ -1479,6 +1503,97 @@ def ror_params(radius, min_neighbors=1):
     if m != min_neighbors or not 1 <= m < 2 ** 32:
         raise ValueError("need 1 <= min_neighbors < 2^32")
     return RorParams(r, m)
+
+
+class _DeviceBlock:
+    """a library device array as __cuda_array_interface__ (version 2): what torch.as_tensor takes without a copy (torch takes no read-only flag); keeps its owner alive"""
+
+    def __init__(self, owner, ptr, shape, typestr):
+        self.owner = owner
+        self.__cuda_array_interface__ = dict(shape=tuple(int(v) for v in shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+
+
+FPFH_STATS = ("finite_points", "distance_evaluations", "pairs_skipped", "lds_points")
+FPFH_SIZE, FPFH_MIN_K, FPFH_MAX_K = 33, 2, 64
+
+
+class Fpfh:
+    """ltm_fpfh: the FPFH descriptors of ltm_search_fpfh, one record per listed search index (semantics in include/ltm.h, "fpfh").  The rows hold the
+    records one after the other, each in its target's ORIGINAL order; offsets() says where each begins."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self.h = ctx, h
+        self._host = None
+
+    def info(self):
+        """(records, rows, k)"""
+        a, b, k = C.c_size_t(), C.c_size_t(), _i()
+        self.ctx._ck(self.ctx.lib.ltm_fpfh_info(self.ctx.h, self.h, C.byref(a), C.byref(b), C.byref(k)))
+        return a.value, b.value, k.value
+
+    def __len__(self):
+        return self.info()[0]
+
+    k = property(lambda self: self.info()[2], doc="the k of the call")
+
+    def _device(self):
+        po, pd, ps = _vp(), _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_fpfh_device(self.ctx.h, self.h, C.byref(po), C.byref(pd), C.byref(ps)))
+        return po.value, pd.value, ps.value
+
+    def _download(self):
+        if self._host is None:
+            nr = self.info()[0]
+            nt, nf = np.empty(nr, np.uint32), np.empty(nr, np.uint32)
+            self.ctx._ck(self.ctx.lib.ltm_fpfh_download(self.ctx.h, self.h, nt.ctypes.data, nf.ctypes.data, None, None))
+            self._host = (nt, nf)
+        return self._host
+
+    n_target = property(lambda self: self._download()[0], doc="uint32 [n_records]: target points of the record's index")
+    n_finite = property(lambda self: self._download()[1], doc="uint32 [n_records]: finite ones among them")
+
+    def offsets(self):
+        """uint64 [n_records + 1]: record r owns rows [offsets[r], offsets[r + 1])"""
+        return SearchIndex._out(self, self._device()[0], self.info()[0] + 1, np.uint64, False)
+
+    def descriptors(self, as_torch=False):
+        """float32 [n_points, 33] (a copy): alpha, phi and theta histograms, each summing to 100; NaN rows for non-finite points and points without a normal"""
+        n = self.info()[1]
+        return SearchIndex._out(self, self._device()[1], n * FPFH_SIZE, np.float32, as_torch).reshape(n, FPFH_SIZE)
+
+    def device_view(self):
+        """the descriptor block itself as a torch tensor [n_points, 33] on the context's device, WITHOUT a copy (torch.cdist and the like work on it): valid
+        until close(); the work queued on the context's stream is waited for first"""
+        import torch
+        n = self.info()[1]
+        if not n:
+            return torch.empty((0, FPFH_SIZE), dtype=torch.float32, device=f"cuda:{self.ctx.device}")
+        self.ctx.synchronize()
+        return torch.as_tensor(_DeviceBlock(self, self._device()[1], (n, FPFH_SIZE), "<f4"), device=f"cuda:{self.ctx.device}")
+
+    def spfh_counts(self):
+        """uint8 [n_points, 33]: the SPFH counts of every point, unpacked (ltm_fpfh_download)"""
+        n = self.info()[1]
+        out = np.zeros((n, FPFH_SIZE), np.uint8)
+        self.ctx._ck(self.ctx.lib.ltm_fpfh_download(self.ctx.h, self.h, None, None, None, out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.ltm_fpfh_free(self.ctx.h, self.h)
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Outliers:

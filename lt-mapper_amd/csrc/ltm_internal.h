@@ -334,6 +334,9 @@ struct ltm_ctx {
     unsigned long long* plane_stats_dev = nullptr;          // device, 4 counters (ltm_debug_plane_stats): the segmentation reads nothing back, so they are kept there; made on first use
     std::vector<struct ltm_outliers*> outlier_open;         // outlier sets (ltm_search_filter_statistical, ltm_search_filter_radius) not freed yet: released by ltm_destroy at the latest
     unsigned long long* outlier_stats_dev = nullptr;        // device, 4 counters (ltm_debug_outlier_stats): the filters read nothing back; made on first use
+    std::vector<struct ltm_fpfh*> fpfh_open;                // descriptor sets (ltm_search_fpfh) not freed yet: released by ltm_destroy at the latest
+    unsigned long long* fpfh_stats_dev = nullptr;           // device, 4 counters (ltm_debug_fpfh_stats); made on first use
+    int fpfh_lists = 1;                         // LTM_FPFH_LISTS=0: ltm_search_fpfh never keeps the neighbour lists of its first pass (A/B switch; the result is the same)
 };
 
 namespace ltm_detail {
@@ -748,6 +751,7 @@ void sc_release_all(ltm_ctx* c);                                                
 void cluster_release_all(ltm_ctx* c);                                             // ltm_api_cluster.cpp: open cluster sets, at ltm_destroy
 void plane_release_all(ltm_ctx* c);                                               // ltm_api_plane.cpp: open plane sets and the device counters, at ltm_destroy
 void outlier_release_all(ltm_ctx* c);                                             // ltm_api_outlier.cpp: open outlier sets and the device counters, at ltm_destroy
+void fpfh_release_all(ltm_ctx* c);                                                // ltm_api_fpfh.cpp: open descriptor sets and the device counters, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp
 

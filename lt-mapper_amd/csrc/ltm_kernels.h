@@ -397,6 +397,23 @@ hipError_t outlier_statistical(const OutlierSeg* segs, const uint32_t* block_seg
 hipError_t outlier_radius(const OutlierSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint32_t n_recs, float r2, uint32_t min_neighbors,
                           uint32_t* counts, OutlierRec* out, uint8_t* labels, unsigned long long* stats4, hipStream_t s);
 
+// ---- FPFH descriptors over the targets of search indices (ltm_k_fpfh.hip; include/ltm.h "fpfh") ----
+static constexpr int kFpfhBlock = 256;          // finite target points per workgroup: lists in registers (k <= 16), and the threads of the fill
+static constexpr int kFpfhBlockLds = 64;        // ... lists in LDS (16 < k <= 64): one wavefront
+static constexpr int kFpfhMaxK = kKnnListSlots;
+static constexpr int kFpfhWords = 4;            // 64-bit words of a point's SPFH: ten 6-bit counts (bins 0 .. 9) per feature in words 0 .. 2, the pairs counted in word 3
+static constexpr uint64_t kFpfhListBudget = 16ull << 30;      // bytes of pooled scratch the neighbour lists of one call may take (8 per finite point and slot)
+// one listed index of the batch: its tree, its normals (aligned with t.pts), its slice [tbase, tbase + n_target) of the call's rows and [fbase, fbase + Mf)
+// of the call's finite points (the stored lists)
+struct FpfhSeg { SearchTree t; const float4* nrm; uint64_t tbase, fbase; uint32_t n_target, pad; BlockSpan span; };
+int        fpfh_block(int k);                   // finite points per workgroup of the kernels that k selects
+// The fixed launch sequence of ltm_search_fpfh (spfh zeroed by the caller): fill, SPFH, weights.  block_seg: the owner table over finite points, fpfh_block(k)
+// per workgroup; spfh: kFpfhWords words per position, desc: 33 floats per position, both in the targets' original order.  list_d2 / list_idx: k x total_f
+// entries each, slot-major (slot j of the call's finite point g at j * total_f + g), written by the SPFH pass and read by the weights; both NULL: the weights
+// collect the neighbourhoods again.  stats4 += finite points, distance evaluations (of every collect), pairs skipped, points that took the LDS list form
+hipError_t fpfh_estimate(const FpfhSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint64_t n_points, int k, unsigned long long* spfh, float* desc,
+                         float* list_d2, int* list_idx, uint64_t total_f, unsigned long long* stats4, hipStream_t s);
+
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
 // one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; 256 points per workgroup
 struct SubmapPiece { uint64_t src, dst; uint32_t n, affine; BlockSpan span; };
