@@ -606,7 +606,9 @@ int ltm_search_build_scanset(ltm_ctx*, ltm_scanset, size_t kf_begin, size_t kf_e
  *  Graph: the vertices are the finite target points of the index; i and j are adjacent iff d2(i, j) < r2, with d2 the index's own distance (FLANN's
  *   L2_Simple in float, ((dx*dx)+dy*dy)+dz*dz, no fused multiply-add) and r2 = (float)((double)tolerance * tolerance), strict <: exactly the relation of
  *   ltm_radius_search.  The float expression is symmetric in its two points, so the relation is.  A cluster is a connected component; coincident points are
- *   adjacent (0 < r2).
+ *   adjacent (0 < r2).  The relation holds as stated at every finite tolerance > 0, down to r2 = 2^-149 and up to r2 = +inf: the shortcut that unites a
+ *   whole leaf of the index without testing its pairs (ltm_box_bound.h, box_is_clique) is taken only where the exact diagonal of the leaf's box, with
+ *   the float expression's relative error and the half denormal each of its three squares can gain when it underflows, stays below r2.
  *  Filter: a component is kept iff min_size <= size <= max_size (max_size = 0: no upper limit).  The points of dropped components and the points with a
  *   non-finite coordinate have label -1.
  *  Order: clusters are numbered 0 .. n_clusters - 1 by size descending; TIES GO TO THE CLUSTER WHOSE LOWEST ORIGINAL POINT INDEX IS SMALLER (PCL's extract
@@ -991,7 +993,7 @@ int ltm_debug_voxel_stats(ltm_ctx*, uint64_t* grids, uint64_t* identity_hits, in
  * with LTM_KNN_STATS=1 (lanes inherit the switch) and stay 0 otherwise; any pointer may be NULL. */
 int ltm_debug_knn_stats(ltm_ctx*, uint64_t* queries, uint64_t* undecided, uint64_t* two_phase_calls, uint64_t* unsorted_queue_calls, int reset);
 /* counters of ltm_search_cluster since the last reset, stats[6]: point pairs whose distance was evaluated, pairs found adjacent (edges, each from its higher end;
- * at most one per visited clique leaf), leaves visited by the walks, clique leaves among them (leaves whose box diagonal is below the tolerance: united
+ * at most one per visited clique leaf), leaves visited by the walks, clique leaves among them (leaves whose box diagonal is below the tolerance by the margin of box_is_clique: united
  * beforehand), walks that left a clique leaf at its first hit, compare-and-swaps of the union-find that failed and were retried.  Always counted; context
  * switch LTM_CLUSTER_CLIQUE=0 (read by ltm_create) turns the clique leaves off -- same results, the counters show which form ran. */
 int ltm_debug_cluster_stats(ltm_ctx*, uint64_t* stats /* 6 */, int reset);

@@ -14,8 +14,9 @@
 // plain stores of values it has read, which only ever touch non-roots.  The flatten pass is a launch of its own, so the kernel boundary orders it after all
 // hooks and makes every store visible: root[i] = find(i) is then the smallest sorted position of i's component, whatever the schedule was.
 //
-// Clique leaves: a leaf (kSearchLeaf consecutive points) whose box diagonal, squared in double and enlarged by a relative 1e-6 (the float distance is within
-// 3e-7 relative of the exact one), is below r2 is a clique.  The init pass points all its positions at its first one with plain stores (nothing else runs),
+// Clique leaves: a leaf (kSearchLeaf consecutive points) whose box diagonal, squared in double, enlarged by a relative 1e-6 (the float distance is within
+// 3e-7 relative of the exact one) and by 2^-148 (squares that underflow round up by half a denormal each), is below r2 is a clique: box_is_clique of
+// ltm_box_bound.h, host and device.  The init pass points all its positions at its first one with plain stores (nothing else runs),
 // a walk that finds one hit in such a leaf stops scanning it, and a thread does not scan its own clique leaf at all.
 //
 // Bookkeeping, integer atomics only: size and lowest original index per root; the roots that pass the size filter are compacted, sorted per index by
@@ -33,8 +34,7 @@ namespace {
 __device__ __forceinline__ bool leaf_is_clique(const float4* __restrict__ box, uint32_t node, float r2)
 {
     const float4 lo = box[2 * node], hi = box[2 * node + 1];
-    const double dx = (double)hi.x - (double)lo.x, dy = (double)hi.y - (double)lo.y, dz = (double)hi.z - (double)lo.z;
-    return (dx * dx + dy * dy + dz * dz) * (1.0 + 1.0e-6) < (double)r2;
+    return box_is_clique(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, r2);
 }
 
 // the walk of ltm_search_walk.h restricted to sorted positions below j: the depth-first order visits the leaves in ascending position, so the walk is

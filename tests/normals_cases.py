@@ -63,6 +63,36 @@ def well_posed(r):
     return np.isfinite(r["gap"]) & (r["gap"] >= WELL_POSED_GAP)
 
 
+# the comparison of tests/test_gpu_normals.py (its header derives the bounds), shared by every test that holds device normals against the restatement
+ULP = 2.0 ** -23
+
+
+def compare(got, r, what, reach=None):
+    """device normals (n, 4) against a restatement result on the well-posed points; curvature on every point.  reach: |viewpoint - point| per point (the
+    sum of the three magnitudes) for clouds far beyond the fixtures' 16 m; the flip's dot product carries the direction's own error of about 1e-12 times
+    that length, so the zone in which either sign is right grows with it beyond 10^6 m and is the fixtures' 1e-6 below"""
+    want = r["normals"]
+    assert got.shape == want.shape and (np.isnan(got) == np.isnan(want)).all(), what
+    ok = well_posed(r)
+    # where the flip's dot product is within 1e-6 of zero either side is right: those points are compared up to the sign
+    sure = ok & (np.abs(r["view_dot"]) > (1e-6 if reach is None else np.maximum(1e-6, 1e-12 * np.asarray(reach, np.float64))))
+    g, w = got[:, :3].astype(np.float64), want[:, :3].astype(np.float64)
+    same, flipped = np.abs(g - w).max(axis=1), np.abs(g + w).max(axis=1)
+    d = np.where(sure, same, np.minimum(same, flipped))[ok].max() if ok.any() else 0.0
+    fin = np.isfinite(want[:, 3])
+    dc = np.abs(got[fin, 3].astype(np.float64) - want[fin, 3].astype(np.float64))
+    excess = (dc - (1e-12 + ULP * want[fin, 3].astype(np.float64))).max() if fin.any() else -1.0
+    same_side = ((g * w).sum(axis=1) > 0.0)[sure]
+    print(f"{what}: {int(ok.sum())} of {len(want)} points compared, max |component difference| {d:.3e} (bound {ULP:.3e}), "
+          f"max curvature difference {dc.max() if fin.any() else 0.0:.3e}")
+    assert d <= ULP, (what, d)
+    assert excess <= 0.0, (what, excess)
+    assert same_side.all(), what
+    unit = np.abs(np.linalg.norm(got[fin, :3].astype(np.float64), axis=1) - 1.0)
+    assert (unit < 1e-6).all(), what
+    return d
+
+
 @functools.lru_cache(maxsize=None)
 def target_normals(kind, key=None):
     """the restatement's float normals (k = ICP_NORMAL_K, viewpoint_of(kind)) of an ICP fixture's target"""

@@ -3,7 +3,9 @@ contraction under the address and undefined-behaviour sanitizers and run as a ch
 the RANGE cases of tests/search_cases.py it draws 10^5 triples (box, float point inside the box, query) and checks that the bound never exceeds the float
 distance the kernels compare (FLANN's L2_Simple, restated here), that it is 0 for a query inside the box and +inf for the empty box -- and that the
 bound as it was before the absolute term, restated here, DOES exceed the float distance at the scales where squares underflow, so that the check is one
-that the defect fails."""
+that the defect fails.  The upper side likewise (box_upper_bound, box_is_clique: the clique leaves of the cluster kernels): over the same scales no
+pair of float points inside a box has a float distance at or above the smallest r2 at which the box is called a clique, a box beyond the float range is
+a clique at no r2, and the rule as it was before the absolute term, restated here, does have such pairs at the scales where squares underflow."""
 import os
 import subprocess
 
@@ -93,16 +95,105 @@ static long run(const Scale& S)
     return violations;
 }
 
+// the clique rule before the absolute term: the relative growth alone
+static bool clique_relative_only(const float* lo, const float* hi, float r2)
+{
+    double s = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        const double e = (double)hi[a] - (double)lo[a];
+        s += e * e;
+    }
+    return s * (1.0 + 1.0e-6) < (double)r2;
+}
+// the smallest float strictly above x (+inf beyond the float range)
+static float float_above(double x)
+{
+    float f = (float)x;
+    if (!((double)f > x)) f = std::nextafter(f, std::numeric_limits<float>::infinity());
+    return f;
+}
+
+// the upper side at one scale: kTriples pairs of float points inside a box; at the smallest r2 at which box_is_clique says yes (and at twice that) the
+// float distance of the pair has to be below r2.  Returns how often the rule before the absolute term, at ITS smallest r2, called a box a clique whose
+// pair has float d2 >= r2
+static long run_upper(const Scale& S)
+{
+    const int kTriples = 100000;
+    const float inf = std::numeric_limits<float>::infinity();
+    long violations = 0, cliques = 0;
+    for (int t = 0; t < kTriples; ++t) {
+        float lo[3], hi[3], p[3], q[3];
+        const bool tight = (next_u64() & 1) != 0;      // the box of the two points themselves: what a leaf of two points has
+        for (int a = 0; a < 3; ++a) {
+            float c0 = (float)(S.origin + S.side * uniform()), c1 = (float)(S.origin + S.side * uniform());
+            if (S.huge && next_u64() % 8 == 0) c0 = (next_u64() & 1) ? 3e38f : -3e38f;
+            lo[a] = std::fmin(c0, c1); hi[a] = std::fmax(c0, c1);
+            if (next_u64() % 16 == 0) hi[a] = lo[a];
+            if (tight) {
+                const bool up = (next_u64() & 1) != 0;
+                p[a] = up ? lo[a] : hi[a]; q[a] = up ? hi[a] : lo[a];
+            } else {
+                p[a] = (float)((double)lo[a] + ((double)hi[a] - (double)lo[a]) * uniform());
+                q[a] = (float)((double)lo[a] + ((double)hi[a] - (double)lo[a]) * uniform());
+                p[a] = std::fmin(std::fmax(p[a], lo[a]), hi[a]); q[a] = std::fmin(std::fmax(q[a], lo[a]), hi[a]);
+                if (next_u64() % 4 == 0) p[a] = (next_u64() & 1) ? lo[a] : hi[a];
+                if (next_u64() % 4 == 0) q[a] = (next_u64() & 1) ? lo[a] : hi[a];
+            }
+            CHECK(std::isfinite(lo[a]) && std::isfinite(hi[a]) && lo[a] <= p[a] && p[a] <= hi[a] && lo[a] <= q[a] && q[a] <= hi[a]);
+        }
+        const float d = sqdist(q[0], q[1], q[2], p[0], p[1], p[2]);
+        CHECK(!std::isnan(d));
+        const double ub = ltm::box_upper_bound(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]);
+        CHECK(ub >= 0x1p-148 && (ub > (double)std::numeric_limits<float>::max() || (double)d <= ub));
+        CHECK(!ltm::box_is_clique(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], (float)ub) || (double)(float)ub > ub);
+        CHECK(!ltm::box_is_clique(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], 0.0f));
+        const float r2 = float_above(ub);
+        if (ub > (double)std::numeric_limits<float>::max()) {
+            CHECK(r2 == inf && !ltm::box_is_clique(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], inf));      // the float distance may be +inf, below no r2
+        } else {
+            CHECK(ltm::box_is_clique(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], r2) && ltm::box_is_clique(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], inf));
+            if (!(d < r2)) { std::printf("%s: a clique at r2 = %a has a pair with float distance %a\n", S.name, (double)r2, (double)d); std::exit(1); }
+            ++cliques;
+        }
+        double diag = 0.0;
+        for (int a = 0; a < 3; ++a) diag += ((double)hi[a] - (double)lo[a]) * ((double)hi[a] - (double)lo[a]);
+        const float r2_old = float_above(diag * (1.0 + 1.0e-6));
+        if (std::isfinite(r2_old) && r2_old > 0.0f) {
+            CHECK(clique_relative_only(lo, hi, r2_old));
+            if (!(d < r2_old)) ++violations;
+        }
+    }
+    CHECK(cliques == kTriples || S.huge || S.side > 1e18);      // only boxes beyond the float range have no r2 at which they are cliques
+    return violations;
+}
+
+// the squares that round UP are those of differences from 2^-75 = 2.6e-23 on (below it a square is 0, and a distance of 0 is below every r2): the
+// relative rule alone goes wrong where the sides are a few times that
+static bool upper_must_violate(const Scale& S) { return S.side >= 1e-22 && S.side <= 2e-21; }
+
 int main()
 {
     const float inf = std::numeric_limits<float>::infinity();
+    // the upper side: the empty box and a box beyond the float range are no cliques, a point is one at any r2 above the absolute term
+    CHECK(!ltm::box_is_clique(inf, inf, inf, -inf, -inf, -inf, inf) && ltm::box_upper_bound(inf, inf, inf, -inf, -inf, -inf) == (double)inf);
+    CHECK(!ltm::box_is_clique(-3e38f, 0.0f, 0.0f, 3e38f, 0.0f, 0.0f, inf) && !ltm::box_is_clique(-3e38f, 0.0f, 0.0f, 3e38f, 0.0f, 0.0f, 3e38f));
+    CHECK(ltm::box_is_clique(1.0f, 2.0f, 3.0f, 1.0f, 2.0f, 3.0f, 0x1p-147f) && !ltm::box_is_clique(1.0f, 2.0f, 3.0f, 1.0f, 2.0f, 3.0f, 0x1p-148f));
+    CHECK(ltm::box_upper_bound(0.0f, 0.0f, 0.0f, 1.0f, 2.0f, 2.0f) == 9.0 * (1.0 + 1.0e-6) + 0x1p-148);
+    CHECK(ltm::box_is_clique(0.0f, 0.0f, 0.0f, 1.0f, 2.0f, 2.0f, 9.00001f) && !ltm::box_is_clique(0.0f, 0.0f, 0.0f, 1.0f, 2.0f, 2.0f, 9.0f));
+    {   // the pair of tests/walker_cases.py: squares of 2.6, 2.6 and 2.0 denormal units round to 3 + 3 + 2 = r2, the exact diagonal is 7.2 units
+        const float c[3] = {(float)(std::sqrt(2.6) * 0x1p-74 * std::sqrt(0.5)), (float)(std::sqrt(2.6) * 0x1p-74 * std::sqrt(0.5)), (float)(std::sqrt(2.0) * 0x1p-74 * std::sqrt(0.5))};
+        const float z[3] = {0.0f, 0.0f, 0.0f};
+        const float r2 = 8 * 0x1p-149f;
+        CHECK(sqdist(c[0], c[1], c[2], 0.0f, 0.0f, 0.0f) == r2);
+        CHECK(clique_relative_only(z, c, r2) && !ltm::box_is_clique(0.0f, 0.0f, 0.0f, c[0], c[1], c[2], r2));
+    }
     CHECK(ltm::box_lower_bound(inf, inf, inf, -inf, -inf, -inf, 1.0f, -2.0f, 3e38f) == (double)inf);
     CHECK(ltm::box_lower_bound(inf, inf, inf, -inf, -inf, -inf, 0.0f, 0.0f, 0.0f) == (double)inf);
     CHECK(ltm::box_lower_bound(1.0f, 1.0f, 1.0f, 2.0f, 2.0f, 2.0f, 1.5f, 1.0f, 2.0f) == 0.0);
     // a gap of 3 m on one axis: the relative shrink is what is left of it at this size
     CHECK(ltm::box_lower_bound(0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f, 4.0f, 0.5f, 0.5f) == 9.0 * (1.0 - 1.0e-6) - 0x1p-148);
     static char names[43][16];
-    long total = 0;
+    long total = 0, total_upper = 0;
     int n = 0;
     for (int e = -24; e <= 18; ++e, ++n) {
         std::snprintf(names[n], sizeof names[n], "1e%d", e);
@@ -111,6 +202,11 @@ int main()
         std::printf("scale %s: the relative bound alone is above the float distance in %ld of 100000 triples\n", S.name, v);
         if (S.must_violate) CHECK(v > 0);
         total += v;
+        const long w = run_upper(S);
+        std::printf("scale %s: the relative clique rule alone has a pair at or above r2 in %ld of 100000 boxes\n", S.name, w);
+        if (upper_must_violate(S)) CHECK(w > 0);
+        if (e >= -12) CHECK(w == 0);      // no box drawn at these sides has a diagonal near 2^-63: no square underflows, the relative term alone was right
+        total_upper += w;
     }
     const Scale range[] = {
         {"underflow_cube", 0.0, 1e-23, false, true}, {"partial_underflow", 0.0, 2e-22, false, true}, {"partial_underflow_1e22", 0.0, 1e-22, false, true},
@@ -120,8 +216,11 @@ int main()
         const long v = run(S);
         std::printf("case %s: the relative bound alone is above the float distance in %ld of 100000 triples\n", S.name, v);
         if (S.must_violate) CHECK(v > 0);
+        const long w = run_upper(S);
+        std::printf("case %s: the relative clique rule alone has a pair at or above r2 in %ld of 100000 boxes\n", S.name, w);
+        if (upper_must_violate(S)) CHECK(w > 0);
     }
-    CHECK(total > 0);
+    CHECK(total > 0 && total_upper > 0);
     std::printf("box bound ok\n");
     return 0;
 }

@@ -16,31 +16,7 @@ from tools import normals_numpy as nref
 
 pytestmark = pytest.mark.gpu
 
-ULP = 2.0 ** -23
-
-
-def _compare(got, r, what):
-    """device normals (n, 4) against a restatement result on the well-posed points; curvature on every point"""
-    want = r["normals"]
-    assert got.shape == want.shape and (np.isnan(got) == np.isnan(want)).all(), what
-    ok = nc.well_posed(r)
-    # where the flip's dot product is within 1e-6 of zero either side is right: those points are compared up to the sign
-    sure = ok & (np.abs(r["view_dot"]) > 1e-6)
-    g, w = got[:, :3].astype(np.float64), want[:, :3].astype(np.float64)
-    same, flipped = np.abs(g - w).max(axis=1), np.abs(g + w).max(axis=1)
-    d = np.where(sure, same, np.minimum(same, flipped))[ok].max() if ok.any() else 0.0
-    fin = np.isfinite(want[:, 3])
-    dc = np.abs(got[fin, 3].astype(np.float64) - want[fin, 3].astype(np.float64))
-    excess = (dc - (1e-12 + ULP * want[fin, 3].astype(np.float64))).max() if fin.any() else -1.0
-    same_side = ((g * w).sum(axis=1) > 0.0)[sure]
-    print(f"{what}: {int(ok.sum())} of {len(want)} points compared, max |component difference| {d:.3e} (bound {ULP:.3e}), "
-          f"max curvature difference {dc.max() if fin.any() else 0.0:.3e}")
-    assert d <= ULP, (what, d)
-    assert excess <= 0.0, (what, excess)
-    assert same_side.all(), what
-    unit = np.abs(np.linalg.norm(got[fin, :3].astype(np.float64), axis=1) - 1.0)
-    assert (unit < 1e-6).all(), what
-    return d
+_compare = nc.compare      # the comparison rule, shared with tests/test_gpu_walker_edges.py
 
 
 @pytest.mark.parametrize("name", nc.NORMALS_FIXTURES)

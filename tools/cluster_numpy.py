@@ -3,11 +3,17 @@ ltm_search_cluster against this for equality.
 
 Candidate pairs come from a k-d tree at tolerance * (1 + 1e-5): the float32 distance of the library is within 3e-7 relative of the exact one
 (ltm_k_search.hip), so no pair with float d2 < r2 lies outside that radius.  The candidates are then filtered by the float32 expression itself,
-((dx*dx)+dy*dy)+dz*dz evaluated with numpy float32 operations in that order, against r2 = float32(float64(tolerance)^2), strict <."""
+((dx*dx)+dy*dy)+dz*dz evaluated with numpy float32 operations in that order, against r2 = float32(float64(tolerance)^2), strict <.
+Where squares underflow the float distance can also lie 1.5 * 2^-149 BELOW the exact one (each of the three squares loses up to half a denormal spacing:
+three squares below 2^-150 give d2 = 0 for a pair 1.2e-22 apart), and r2 itself is rounded to a denormal, up by half a spacing at the most: the squared
+candidate radius is enlarged by 2^-147, which is nothing at any tolerance above 1e-19."""
 import numpy as np
 from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 from scipy.spatial import cKDTree
+
+
+UNDERFLOW_SLACK = 2.0 ** -147      # added to the squared candidate radius: see above
 
 
 def r2_of(tolerance):
@@ -40,7 +46,8 @@ def edges(points, tolerance):
         return np.zeros((0, 2), np.int64), fin
     q = p[fin]
     with np.errstate(over="ignore", invalid="ignore"):
-        cand = cKDTree(q.astype(np.float64)).query_pairs(float(tolerance) * (1.0 + 1e-5), output_type="ndarray")
+        reach = float(tolerance) * (1.0 + 1e-5)
+        cand = cKDTree(q.astype(np.float64)).query_pairs(float(np.sqrt(reach * reach + UNDERFLOW_SLACK)), output_type="ndarray")
         if len(cand) == 0:
             return np.zeros((0, 2), np.int64), fin
         keep = d2_float32(q[cand[:, 0]], q[cand[:, 1]]) < r2_of(tolerance)
