@@ -727,22 +727,16 @@ class Context:
     def cluster(self, indices, tolerance, min_size=1, max_size=None):
         """ltm_search_cluster: pcl::EuclideanClusterExtraction over the targets of all `indices` (SearchIndex objects of this context; the same one may be
         listed more than once) in one sequence of launches and one read-back.  Returns one Clusters per index.  max_size None: no upper limit."""
-        indices = list(indices)
         p = cluster_params(tolerance, min_size, max_size)
-        for x in indices:
-            if not isinstance(x, SearchIndex):
-                raise TypeError("cluster takes SearchIndex objects (Context.search_index)")
+        indices, hs = self._index_handles(indices, "cluster")
         n = len(indices)
-        hs = (_vp * max(n, 1))(*[x.h for x in indices])
         out = (_vp * max(n, 1))()
         self._ck(self.lib.ltm_search_cluster(self.h, n, hs, C.byref(p), out))
         return [Clusters(self, out[i]) for i in range(n)]
 
     def cluster_stats(self, reset=False):
         """ltm_debug_cluster_stats: dict of the six counters since the last reset"""
-        a = (C.c_uint64 * 6)()
-        self._ck(self.lib.ltm_debug_cluster_stats(self.h, a, int(reset)))
-        return dict(zip(CLUSTER_STATS, [int(v) for v in a]))
+        return self._stats("ltm_debug_cluster_stats", CLUSTER_STATS, reset)
 
     def segment_planes(self, scans, distance_threshold, max_iterations=128, axis=None, eps_angle=0.0, seed=0, refine=True, kf_begin=0, kf_end=None):
         """ltm_scanset_segment_planes: pcl::SACSegmentation (SACMODEL_PLANE, or SACMODEL_PERPENDICULAR_PLANE with `axis` and `eps_angle` [rad]; SAC_RANSAC)
@@ -771,11 +765,15 @@ class Context:
 
     def plane_stats(self, reset=False):
         """ltm_debug_plane_stats: dict of the four counters since the last reset"""
-        a = (C.c_uint64 * 4)()
-        self._ck(self.lib.ltm_debug_plane_stats(self.h, a, int(reset)))
-        return dict(zip(PLANE_STATS, [int(v) for v in a]))
+        return self._stats("ltm_debug_plane_stats", PLANE_STATS, reset)
 
-    def _outlier_indices(self, indices, what):
+    def _stats(self, fn_name, names, reset):
+        a = (C.c_uint64 * len(names))()
+        self._ck(getattr(self.lib, fn_name)(self.h, a, int(reset)))
+        return dict(zip(names, [int(v) for v in a]))
+
+    def _index_handles(self, indices, what):
+        """(the indices as a list, their handles as the array a batched entry point takes)"""
         indices = list(indices)
         for x in indices:
             if not isinstance(x, SearchIndex):
@@ -787,7 +785,7 @@ class Context:
         of this context; the same one may be listed more than once) in one sequence of launches; nothing is read back.  Returns one Outliers with one
         record per index."""
         p = sor_params(mean_k, stddev_mul)
-        indices, hs = self._outlier_indices(indices, "statistical_outliers")
+        indices, hs = self._index_handles(indices, "statistical_outliers")
         h = _vp()
         self._ck(self.lib.ltm_search_filter_statistical(self.h, len(indices), hs, C.byref(p), C.byref(h)))
         return Outliers(self, h.value)
@@ -795,30 +793,26 @@ class Context:
     def radius_outliers(self, indices, radius, min_neighbors=1):
         """ltm_search_filter_radius: pcl::RadiusOutlierRemoval (setRadiusSearch, setMinNeighborsInRadius) likewise"""
         p = ror_params(radius, min_neighbors)
-        indices, hs = self._outlier_indices(indices, "radius_outliers")
+        indices, hs = self._index_handles(indices, "radius_outliers")
         h = _vp()
         self._ck(self.lib.ltm_search_filter_radius(self.h, len(indices), hs, C.byref(p), C.byref(h)))
         return Outliers(self, h.value)
 
     def outlier_stats(self, reset=False):
         """ltm_debug_outlier_stats: dict of the four counters since the last reset"""
-        a = (C.c_uint64 * 4)()
-        self._ck(self.lib.ltm_debug_outlier_stats(self.h, a, int(reset)))
-        return dict(zip(OUTLIER_STATS, [int(v) for v in a]))
+        return self._stats("ltm_debug_outlier_stats", OUTLIER_STATS, reset)
 
     def fpfh(self, indices, k):
         """ltm_search_fpfh: pcl::FPFHEstimation (setKSearch(k)) over the targets of all `indices` (SearchIndex objects of this context with normals, each at
         most once) in one sequence of launches; nothing is read back.  Returns one Fpfh with one record per index."""
-        indices, hs = self._outlier_indices(indices, "fpfh")
+        indices, hs = self._index_handles(indices, "fpfh")
         h = _vp()
         self._ck(self.lib.ltm_search_fpfh(self.h, len(indices), hs, int(k), C.byref(h)))
         return Fpfh(self, h.value)
 
     def fpfh_stats(self, reset=False):
         """ltm_debug_fpfh_stats: dict of the four counters since the last reset"""
-        a = (C.c_uint64 * 4)()
-        self._ck(self.lib.ltm_debug_fpfh_stats(self.h, a, int(reset)))
-        return dict(zip(FPFH_STATS, [int(v) for v in a]))
+        return self._stats("ltm_debug_fpfh_stats", FPFH_STATS, reset)
 
     # ---- loop submaps
     def loop_submaps(self, scans, keys, search_num, leaf=0.3, affines=None, order="pcl"):
@@ -1111,22 +1105,30 @@ def _xyzi(a):
     return _np_pts(a)
 
 
-class SearchIndex:
-    """ltm_search: device-resident exact k-NN / radius search over one cloud (pcl::KdTreeFLANN's queries, semantics in include/ltm.h).
-    Queries are Clouds of the same context or (n, 3) / (n, 4) arrays.  Results are numpy arrays, or with as_torch=True CUDA tensors that
-    torch allocated and owns (the library's buffers are copied into them device to device)."""
+class _PtrHandle:
+    """a pointer handle of the library owned by a Context: close() (or leaving a `with` block, or the object going) frees it with the subclass's _free"""
+    _free = None
+    _host = None      # the per-record arrays of a set, once downloaded
 
     def __init__(self, ctx, h):
         self.ctx, self.h = ctx, h
 
-    def _query(self, query):
-        return query if isinstance(query, Cloud) else self.ctx.upload(_xyzi(query))
+    def close(self):
+        if self.h and self.ctx.h:
+            getattr(self.ctx.lib, self._free)(self.ctx.h, self.h)
+        self.h = None
 
-    def info(self):
-        """(target points, finite target points)"""
-        a, b = C.c_size_t(), C.c_size_t()
-        self.ctx._ck(self.ctx.lib.ltm_search_info(self.ctx.h, self.h, C.byref(a), C.byref(b)))
-        return a.value, b.value
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def _out(self, dev, n, dtype, as_torch):
         """n elements of a library device array -> numpy array or torch CUDA tensor (a copy either way)"""
@@ -1142,6 +1144,23 @@ class SearchIndex:
         if n:
             self.ctx._ck(self.ctx.lib.ltm_buffer_copy(self.ctx.h, a.ctypes.data, dev, a.nbytes, 1))
         return a
+
+
+class SearchIndex(_PtrHandle):
+    """ltm_search: device-resident exact k-NN / radius search over one cloud (pcl::KdTreeFLANN's queries, semantics in include/ltm.h).
+    Queries are Clouds of the same context or (n, 3) / (n, 4) arrays.  Results are numpy arrays, or with as_torch=True CUDA tensors that
+    torch allocated and owns (the library's buffers are copied into them device to device)."""
+
+    _free = "ltm_search_free"
+
+    def _query(self, query):
+        return query if isinstance(query, Cloud) else self.ctx.upload(_xyzi(query))
+
+    def info(self):
+        """(target points, finite target points)"""
+        a, b = C.c_size_t(), C.c_size_t()
+        self.ctx._ck(self.ctx.lib.ltm_search_info(self.ctx.h, self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def knn(self, query, k, as_torch=False):
         """nearestKSearch for every query point: (idx int32 [n, k], d2 float32 [n, k]); padding -1 / +inf"""
@@ -1210,22 +1229,6 @@ class SearchIndex:
         """ltm_search_filter_radius for this index alone: setRadiusSearch(radius), setMinNeighborsInRadius(min_neighbors), filter"""
         return self.ctx.radius_outliers([self], radius, min_neighbors)
 
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.lib.ltm_search_free(self.ctx.h, self.h)
-        self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 CLUSTER_STATS = ("pairs_tested", "edges_found", "leaves_visited", "clique_leaves", "clique_early_exits", "hook_retries")
@@ -1242,13 +1245,11 @@ def cluster_params(tolerance, min_size=1, max_size=None):
     return ClusterParams(tolerance, lo, hi)
 
 
-class Clusters:
+class Clusters(_PtrHandle):
     """ltm_clusters: the Euclidean clusters of one search index's target (semantics in include/ltm.h, "clusters").  Labels and point indices refer to the
     target's ORIGINAL order; clusters are numbered by size descending, ties by the lowest original index."""
 
-    def __init__(self, ctx, h):
-        self.ctx, self.h = ctx, h
-        self._host = None
+    _free = "ltm_clusters_free"
 
     def info(self):
         """(target points, clusters, clustered points)"""
@@ -1266,13 +1267,13 @@ class Clusters:
 
     def labels(self, as_torch=False):
         """int32 [n_target]: the cluster of every target point, -1 = none"""
-        return SearchIndex._out(self, self._device()[0], self.info()[0], np.int32, as_torch)
+        return self._out(self._device()[0], self.info()[0], np.int32, as_torch)
 
     def indices(self, as_torch=False):
         """CSR: (offsets uint64 [n_clusters + 1] (int64 as torch), idx int32 [clustered points]); row c = cluster c in ascending original index"""
         _, nc, npts = self.info()
         _, po, pi = self._device()
-        return SearchIndex._out(self, po, nc + 1, np.uint64, as_torch), SearchIndex._out(self, pi, npts, np.int32, as_torch)
+        return self._out(po, nc + 1, np.uint64, as_torch), self._out(pi, npts, np.int32, as_torch)
 
     def _download(self):
         if self._host is None:
@@ -1296,22 +1297,6 @@ class Clusters:
         self.ctx._ck(self.ctx.lib.ltm_clusters_extract(self.ctx.h, self.h, cloud.h, C.byref(out)))
         return ScanSet(self.ctx, out.value)
 
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.lib.ltm_clusters_free(self.ctx.h, self.h)
-        self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _icp_method(method):
@@ -1395,13 +1380,11 @@ def plane_params(distance_threshold, max_iterations=128, axis=None, eps_angle=0.
     return PlaneParams(thr, it, sd, (C.c_double * 3)(*ax.tolist()), eps, 1 if refine else 0)
 
 
-class Planes:
+class Planes(_PtrHandle):
     """ltm_planes: the RANSAC plane of every record (keyframe of a scan-set range, or one cloud); semantics in include/ltm.h, "planes".  Labels are in the order
     of the range's points."""
 
-    def __init__(self, ctx, h):
-        self.ctx, self.h = ctx, h
-        self._host = None
+    _free = "ltm_planes_free"
 
     def info(self):
         """(records, points, max_iterations)"""
@@ -1438,17 +1421,17 @@ class Planes:
 
     def labels(self, as_torch=False):
         """uint8 [n_points]: 1 = inlier of its record's final plane"""
-        return SearchIndex._out(self, self._device()[0], self.info()[1], np.uint8, as_torch)
+        return self._out(self._device()[0], self.info()[1], np.uint8, as_torch)
 
     def hypothesis_counts(self):
         """uint32 [n_records, max_iterations]: the inlier count of every hypothesis, 0 where invalid"""
         nr, _, m = self.info()
-        return SearchIndex._out(self, self._device()[1], nr * m, np.uint32, False).reshape(nr, m)
+        return self._out(self._device()[1], nr * m, np.uint32, False).reshape(nr, m)
 
     def hypothesis_valid(self):
         """uint8 [n_records, max_iterations]"""
         nr, _, m = self.info()
-        return SearchIndex._out(self, self._device()[2], nr * m, np.uint8, False).reshape(nr, m)
+        return self._out(self._device()[2], nr * m, np.uint8, False).reshape(nr, m)
 
     def split(self, scans_or_cloud):
         """ltm_planes_split_scanset / _cloud: (inliers, rest) of the ScanSet or Cloud the set was made from, input order kept"""
@@ -1460,22 +1443,6 @@ class Planes:
         self.ctx._ck(self.ctx.lib.ltm_planes_split_cloud(self.ctx.h, self.h, cloud.h, C.byref(a), C.byref(b)))
         return Cloud(self.ctx, a.value), Cloud(self.ctx, b.value)
 
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.lib.ltm_planes_free(self.ctx.h, self.h)
-        self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 OUTLIER_STATS = ("finite_points", "distance_evaluations", "radius_early_stops", "records")
@@ -1517,13 +1484,11 @@ FPFH_STATS = ("finite_points", "distance_evaluations", "pairs_skipped", "lds_poi
 FPFH_SIZE, FPFH_MIN_K, FPFH_MAX_K = 33, 2, 64
 
 
-class Fpfh:
+class Fpfh(_PtrHandle):
     """ltm_fpfh: the FPFH descriptors of ltm_search_fpfh, one record per listed search index (semantics in include/ltm.h, "fpfh").  The rows hold the
     records one after the other, each in its target's ORIGINAL order; offsets() says where each begins."""
 
-    def __init__(self, ctx, h):
-        self.ctx, self.h = ctx, h
-        self._host = None
+    _free = "ltm_fpfh_free"
 
     def info(self):
         """(records, rows, k)"""
@@ -1554,12 +1519,12 @@ class Fpfh:
 
     def offsets(self):
         """uint64 [n_records + 1]: record r owns rows [offsets[r], offsets[r + 1])"""
-        return SearchIndex._out(self, self._device()[0], self.info()[0] + 1, np.uint64, False)
+        return self._out(self._device()[0], self.info()[0] + 1, np.uint64, False)
 
     def descriptors(self, as_torch=False):
         """float32 [n_points, 33] (a copy): alpha, phi and theta histograms, each summing to 100; NaN rows for non-finite points and points without a normal"""
         n = self.info()[1]
-        return SearchIndex._out(self, self._device()[1], n * FPFH_SIZE, np.float32, as_torch).reshape(n, FPFH_SIZE)
+        return self._out(self._device()[1], n * FPFH_SIZE, np.float32, as_torch).reshape(n, FPFH_SIZE)
 
     def device_view(self):
         """the descriptor block itself as a torch tensor [n_points, 33] on the context's device, WITHOUT a copy (torch.cdist and the like work on it): valid
@@ -1578,31 +1543,13 @@ class Fpfh:
         self.ctx._ck(self.ctx.lib.ltm_fpfh_download(self.ctx.h, self.h, None, None, None, out.ctypes.data))
         return out
 
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.lib.ltm_fpfh_free(self.ctx.h, self.h)
-        self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Outliers:
+class Outliers(_PtrHandle):
     """ltm_outliers: the labels of a statistical or radius outlier filter, one record per listed search index (semantics in include/ltm.h, "outlier
     filters").  The per-position arrays hold the records one after the other, each in its target's ORIGINAL order; offsets() says where each begins."""
 
-    def __init__(self, ctx, h):
-        self.ctx, self.h = ctx, h
-        self._host = None
+    _free = "ltm_outliers_free"
 
     def info(self):
         """(kind, records, positions)"""
@@ -1639,23 +1586,23 @@ class Outliers:
 
     def offsets(self):
         """uint64 [n_records + 1]: record r owns positions [offsets[r], offsets[r + 1]) of labels / distances / counts"""
-        return SearchIndex._out(self, self._device()[0], self.info()[1] + 1, np.uint64, False)
+        return self._out(self._device()[0], self.info()[1] + 1, np.uint64, False)
 
     def labels(self, as_torch=False):
         """uint8 [n_points]: 1 = kept"""
-        return SearchIndex._out(self, self._device()[1], self.info()[2], np.uint8, as_torch)
+        return self._out(self._device()[1], self.info()[2], np.uint8, as_torch)
 
     def distances(self, as_torch=False):
         """float32 [n_points]: the mean neighbour distance of every position, 0 for a non-finite point (statistical sets only)"""
         if self.info()[0] != OUTLIERS_STATISTICAL:
             raise ValueError("a radius outlier set has no distances")
-        return SearchIndex._out(self, self._device()[2], self.info()[2], np.float32, as_torch)
+        return self._out(self._device()[2], self.info()[2], np.float32, as_torch)
 
     def counts(self):
         """uint32 [n_points]: neighbours within the radius, the point included, saturated at min_neighbors (radius sets only)"""
         if self.info()[0] != OUTLIERS_RADIUS:
             raise ValueError("a statistical outlier set has no counts")
-        return SearchIndex._out(self, self._device()[3], self.info()[2], np.uint32, False)
+        return self._out(self._device()[3], self.info()[2], np.uint32, False)
 
     def split(self, scans_or_cloud):
         """ltm_outliers_split_scanset / _cloud: (kept, removed) of a ScanSet with one keyframe per record, or of the Cloud (or array) of a one-record
@@ -1668,27 +1615,13 @@ class Outliers:
         self.ctx._ck(self.ctx.lib.ltm_outliers_split_cloud(self.ctx.h, self.h, cloud.h, C.byref(a), C.byref(b)))
         return Cloud(self.ctx, a.value), Cloud(self.ctx, b.value)
 
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.lib.ltm_outliers_free(self.ctx.h, self.h)
-        self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class ScanContexts:
+class ScanContexts(_PtrHandle):
     """ltm_sc: N device-resident Scan Context descriptors with their ring and sector keys (semantics in include/ltm.h, "scan context").  The
     parameters it was made with are the defaults of distance() / detect(); keyword arguments replace single fields for one call."""
+
+    _free = "ltm_sc_free"
 
     def __init__(self, ctx, h, params):
         self.ctx, self.h, self.params = ctx, h, params
@@ -1736,22 +1669,6 @@ class ScanContexts:
                                                                                              ("loop_id", "nn_idx", "min_dist", "nn_align", "yaw_diff_rad")]))
         return out
 
-    def close(self):
-        if self.h and self.ctx.h:
-            self.ctx.lib.ltm_sc_free(self.ctx.h, self.h)
-        self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class VgsTicket:

@@ -3,7 +3,6 @@
 #include "ltm_internal.h"
 
 struct ltm_clusters {
-    ltm_ctx* owner = nullptr;
     std::shared_ptr<PoolBlocks> batch;        // every pointer below points into the blocks that the cluster sets of one ltm_search_cluster share
     size_t n_target = 0, n_clusters = 0, n_points = 0;
     int32_t* labels = nullptr;                // n_target, the target's original order
@@ -13,8 +12,6 @@ struct ltm_clusters {
 };
 
 namespace {
-
-ltm_clusters* get_clusters(ltm_ctx* c, ltm_clusters* s) { return open_handle(c->cluster_open, s, "not a cluster set of this context"); }
 
 void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_cluster_params& p, std::vector<std::unique_ptr<ltm_clusters>>& out)
 {
@@ -33,7 +30,6 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
         while (((uint32_t)1 << S.logP) < S.t.P) ++S.logP;
         total_f += S.t.Mf; total_t += L.n_target;
         out[k].reset(new ltm_clusters);
-        out[k]->owner = c;
         out[k]->batch = batch;
         out[k]->n_target = L.n_target;
     });
@@ -112,12 +108,6 @@ void cluster_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const ltm_c
 
 } // namespace
 
-void ltm_detail::cluster_release_all(ltm_ctx* c)      // ltm_destroy: cluster sets nobody freed
-{
-    for (ltm_clusters* s : c->cluster_open) delete s;
-    c->cluster_open.clear();
-}
-
 extern "C" {
 
 void ltm_cluster_default_params(ltm_cluster_params* p)
@@ -135,24 +125,19 @@ int ltm_search_cluster(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, const l
         LTM_REQUIRE(std::isfinite(params->tolerance) && params->tolerance > 0.0, "tolerance must be finite and > 0");
         LTM_REQUIRE(params->min_size >= 1 && (params->max_size == 0 || params->max_size >= params->min_size), "need 1 <= min_size <= max_size (max_size 0: no limit)");
         if (!n_idx) return;
-        LTM_REQUIRE(idx && out, "null argument");
-        LTM_REQUIRE(n_idx < 0x7fffffffull, "too many indices");
-        for (size_t k = 0; k < n_idx; ++k) LTM_REQUIRE(idx[k], "null search index");
+        LTM_REQUIRE(out, "null argument");
+        check_listed_indices(n_idx, idx, 0x7fffffffull);
         std::vector<std::unique_ptr<ltm_clusters>> made;
         // an error leaves nothing behind: the handles die with `made`, the shared blocks with the last reference to the batch, scratch with its DevBufs
         cluster_batch(c, n_idx, idx, *params, made);
-        c->cluster_open.reserve(c->cluster_open.size() + made.size());
-        for (size_t k = 0; k < made.size(); ++k) {
-            c->cluster_open.push_back(made[k].get());
-            out[k] = made[k].release();
-        }
+        c->open.clusters.adopt(made, out);
     });
 }
 
 int ltm_clusters_info(ltm_ctx* c, ltm_clusters* h, size_t* n_target, size_t* n_clusters, size_t* n_clustered_points)
 {
     return guarded(c, [&] {
-        const ltm_clusters* s = get_clusters(c, h);
+        const ltm_clusters* s = c->open.clusters.get(h);
         if (n_target) *n_target = s->n_target;
         if (n_clusters) *n_clusters = s->n_clusters;
         if (n_clustered_points) *n_clustered_points = s->n_points;
@@ -162,7 +147,7 @@ int ltm_clusters_info(ltm_ctx* c, ltm_clusters* h, size_t* n_target, size_t* n_c
 int ltm_clusters_device(ltm_ctx* c, ltm_clusters* h, const int32_t** labels_dev, const uint64_t** offsets_dev, const int32_t** idx_dev)
 {
     return guarded(c, [&] {
-        const ltm_clusters* s = get_clusters(c, h);
+        const ltm_clusters* s = c->open.clusters.get(h);
         if (labels_dev) *labels_dev = s->labels;
         if (offsets_dev) *offsets_dev = s->offsets;
         if (idx_dev) *idx_dev = s->idx;
@@ -172,7 +157,7 @@ int ltm_clusters_device(ltm_ctx* c, ltm_clusters* h, const int32_t** labels_dev,
 int ltm_clusters_download(ltm_ctx* c, ltm_clusters* h, int32_t* labels, uint32_t* sizes, int32_t* first_idx, float* box6, double* centroid3)
 {
     return guarded(c, [&] {
-        const ltm_clusters* s = get_clusters(c, h);
+        const ltm_clusters* s = c->open.clusters.get(h);
         if (labels) d2h(c, labels, s->labels, s->n_target * 4);
         if (sizes) d2h(c, sizes, s->sizes, s->n_clusters * 4);
         if (first_idx) d2h(c, first_idx, s->first, s->n_clusters * 4);
@@ -184,7 +169,7 @@ int ltm_clusters_download(ltm_ctx* c, ltm_clusters* h, int32_t* labels, uint32_t
 int ltm_clusters_extract(ltm_ctx* c, ltm_clusters* h, ltm_cloud hcloud, ltm_scanset* out)
 {
     return guarded(c, [&] {
-        const ltm_clusters* s = get_clusters(c, h);
+        const ltm_clusters* s = c->open.clusters.get(h);
         LTM_REQUIRE(out, "null argument");
         const Cloud cloud = get_cloud(c, hcloud);
         LTM_REQUIRE(cloud.n == s->n_target, "the cloud is not the one the index was built over (point counts differ)");
@@ -204,11 +189,7 @@ int ltm_clusters_extract(ltm_ctx* c, ltm_clusters* h, ltm_cloud hcloud, ltm_scan
 
 int ltm_clusters_free(ltm_ctx* c, ltm_clusters* h)
 {
-    return guarded(c, [&] {
-        get_clusters(c, h);
-        forget_handle(c->cluster_open, h);
-        delete h;
-    });
+    return guarded(c, [&] { c->open.clusters.free(h); });
 }
 
 int ltm_debug_cluster_stats(ltm_ctx* c, uint64_t* stats, int reset)

@@ -294,12 +294,8 @@ void ltm_destroy(ltm_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     vgs_release_all(c);      // before the pinned blocks and the pool go: a coordinator thread of an abandoned ticket reads and writes them
-    search_release_all(c);
-    sc_release_all(c);
-    cluster_release_all(c);
-    plane_release_all(c);
-    outlier_release_all(c);
-    fpfh_release_all(c);
+    c->open.release_all();      // the pointer handles nobody freed
+    c->plane_stats.release(); c->outlier_stats.release(); c->fpfh_stats.release();
     for (Pending& p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }

@@ -74,15 +74,13 @@ struct KnnIndex {
     }
 };
 
-// split pts[0..n) by flag (1 -> first output) keeping order; per-keyframe offsets from `bounds` (n_b+1 point positions)
+// split pts[0..n) by flag (1 -> the set half) keeping order; per-keyframe offsets from `bounds` (n_b+1 point positions)
 // offsets_dev[kf0 + j] - first are the same boundaries on the device (the scan set's own offset table)
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
-                   size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset)
+                   size_t kf0, uint64_t first, FlagSplit& out)
 {
     const size_t nb = bounds.size() - 1;
-    off_set->assign(nb + 1, 0); off_unset->assign(nb + 1, 0);
-    *d_set = nullptr; *d_unset = nullptr;
-    size_t nset = 0;
+    out.off_set.assign(nb + 1, 0); out.off_unset.assign(nb + 1, 0);
     if (n) {
         DevBuf pos(c, n * 4);
         scan_flags(c, flag, n, pos);
@@ -90,14 +88,14 @@ void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n,
         LTM_HIP(flag_bounds(pos.as<uint32_t>(), flag, n, offsets_dev, kf0, first, nb, bout.as<uint32_t>(), c->stream));
         std::vector<uint32_t> b(nb + 1);
         d2h(c, b.data(), bout.p, (nb + 1) * 4);
-        nset = b[nb];
-        for (size_t j = 0; j <= nb; ++j) { (*off_set)[j] = b[j]; (*off_unset)[j] = bounds[j] - b[j]; }
-        *d_set = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(nset, 1) * sizeof(float4)));
-        *d_unset = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(n - nset, 1) * sizeof(float4)));
-        LTM_HIP(partition_scatter(pts, flag, pos.as<uint32_t>(), n, *d_unset, *d_set, c->stream));
+        const size_t nset = b[nb];
+        for (size_t j = 0; j <= nb; ++j) { out.off_set[j] = b[j]; out.off_unset[j] = bounds[j] - b[j]; }
+        out.d_set = out.blocks.alloc<float4>(std::max<size_t>(nset, 1));
+        out.d_unset = out.blocks.alloc<float4>(std::max<size_t>(n - nset, 1));
+        LTM_HIP(partition_scatter(pts, flag, pos.as<uint32_t>(), n, out.d_unset, out.d_set, c->stream));
     } else {
-        *d_set = reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
-        *d_unset = reinterpret_cast<float4*>(c->pool.alloc(sizeof(float4)));
+        out.d_set = out.blocks.alloc<float4>(1);
+        out.d_unset = out.blocks.alloc<float4>(1);
     }
 }
 
@@ -115,11 +113,9 @@ int ltm_preclean(ltm_ctx* c, ltm_scanset hin, float radius, ltm_scanset* out)
         const ScanSet& s = get_ss(c, hin);
         DevBuf drop(c, std::max<size_t>(s.n_pts, 1));
         LTM_HIP(preclean_flags(s.d, s.n_pts, radius, drop.as<uint8_t>(), c->stream));
-        float4 *d_drop, *d_keep;
-        std::vector<uint64_t> off_drop, off_keep;
-        split_by_flag(c, s.d, drop.as<uint8_t>(), s.n_pts, s.off, s.off_dev, 0, 0, &d_drop, &off_drop, &d_keep, &off_keep);
-        c->pool.free(d_drop);
-        *out = new_scanset(c, d_keep, std::move(off_keep));
+        FlagSplit split(c);
+        split_by_flag(c, s.d, drop.as<uint8_t>(), s.n_pts, s.off, s.off_dev, 0, 0, split);
+        split.hand_over(nullptr, out);      // the dropped points go back to the pool
     });
 }
 
@@ -196,11 +192,9 @@ int ltm_knn_partition(ltm_ctx* c, ltm_cloud htarget, ltm_scanset hs, ltm_poses h
         }
         std::vector<uint64_t> bounds(kf_end - kf_begin + 1);
         for (size_t j = 0; j < bounds.size(); ++j) bounds[j] = s.off[kf_begin + j] - first;
-        float4 *d_co, *d_di;
-        std::vector<uint64_t> off_co, off_di;
-        split_by_flag(c, local.as<float4>(), flag.as<uint8_t>(), n, bounds, s.off_dev, kf_begin, first, &d_co, &off_co, &d_di, &off_di);
-        if (coexist) *coexist = new_scanset(c, d_co, std::move(off_co)); else c->pool.free(d_co);
-        if (diff) *diff = new_scanset(c, d_di, std::move(off_di)); else c->pool.free(d_di);
+        FlagSplit split(c);
+        split_by_flag(c, local.as<float4>(), flag.as<uint8_t>(), n, bounds, s.off_dev, kf_begin, first, split);
+        split.hand_over(coexist, diff);
     });
 }
 

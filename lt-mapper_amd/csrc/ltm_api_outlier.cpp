@@ -3,35 +3,16 @@
 // do_partition).
 #include "ltm_internal.h"
 
-struct ltm_outliers {
-    ltm_ctx* owner = nullptr;
-    PoolBlocks blocks;                        // offsets, labels, distances or counts and the records' rows: back in the pool with the handle
+struct ltm_outliers : IndexRecordSet {        // blocks: offsets, labels, distances or counts and the records' rows
     int kind = LTM_OUTLIERS_STATISTICAL;
-    std::vector<uint64_t> bounds;             // n_records + 1 positions of the records' targets, from 0
-    std::vector<uint32_t> n_finite;           // per record
-    uint64_t* offsets = nullptr;              // n_records + 1, the device copy of bounds
     uint8_t* labels = nullptr;                // n_points, every record in its target's original order
     float* dist = nullptr;                    // n_points (statistical)
     uint32_t* counts = nullptr;               // n_points (radius)
     OutlierRec* out = nullptr;                // n_records
-    explicit ltm_outliers(ltm_ctx* c) : owner(c), blocks(c) {}
-    size_t n_records() const { return bounds.size() - 1; }
-    size_t n_points() const { return bounds.back(); }
+    using IndexRecordSet::IndexRecordSet;
 };
 
 namespace {
-
-ltm_outliers* get_outliers(ltm_ctx* c, ltm_outliers* s) { return open_handle(c->outlier_open, s, "not an outlier set of this context"); }
-
-// the device counters of ltm_debug_outlier_stats: outside the pool (they live as long as the context), made on first use
-unsigned long long* outlier_stats_dev(ltm_ctx* c)
-{
-    if (!c->outlier_stats_dev) {
-        LTM_HIP(hipMalloc(reinterpret_cast<void**>(&c->outlier_stats_dev), 4 * sizeof(unsigned long long)));
-        LTM_HIP(hipMemsetAsync(c->outlier_stats_dev, 0, 4 * sizeof(unsigned long long), c->stream));
-    }
-    return c->outlier_stats_dev;
-}
 
 // The listed indices as the records of one call, checked before the device is touched, and the owner tables: per_block finite points per workgroup,
 // kOutlierChunk original positions per chunk
@@ -42,10 +23,9 @@ struct Batch {
 };
 std::unique_ptr<ltm_outliers> open_batch(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, int kind, uint32_t per_block, Batch& B)
 {
-    std::unique_ptr<ltm_outliers> P(new ltm_outliers(c));
+    check_listed_indices(n_idx, idx, 0x7fffffffull / 16);
+    std::unique_ptr<ltm_outliers> P(new ltm_outliers(c, n_idx));
     P->kind = kind;
-    P->bounds.assign(n_idx + 1, 0);
-    P->n_finite.assign(n_idx, 0);
     B.segs.resize(n_idx);
     const char* over_table = "too many target points in one outlier filter call";
     for_listed_indices(c, n_idx, idx, B.points, per_block, true, "the indices of one outlier filter call must have fewer than 2^31 target points in all", over_table,
@@ -53,8 +33,7 @@ std::unique_ptr<ltm_outliers> open_batch(ltm_ctx* c, size_t n_idx, ltm_search* c
         OutlierSeg& S = B.segs[k];
         memset(&S, 0, sizeof S);
         S.t = L.t; S.n_target = L.n_target; S.tbase = L.tbase; S.span = L.span;
-        P->bounds[k + 1] = L.tbase + L.n_target;
-        P->n_finite[k] = S.t.Mf;
+        P->set_record(k, L);
         B.total_f += S.t.Mf;
         if (!B.chunks.add((uint32_t)k, L.n_target, kOutlierChunk, &S.tspan)) throw Err{LTM_E_UNSUPPORTED, over_table};
     });
@@ -77,28 +56,7 @@ void* alloc_arrays(ltm_ctx* c, ltm_outliers* P)
     return values;
 }
 
-ltm_outliers* adopt(ltm_ctx* c, std::unique_ptr<ltm_outliers>& P)
-{
-    c->outlier_open.push_back(P.get());
-    return P.release();
-}
-
-void check_indices(size_t n_idx, ltm_search* const* idx)
-{
-    LTM_REQUIRE(n_idx < 0x7fffffffull / 16, "too many indices");
-    LTM_REQUIRE(!n_idx || idx, "null argument");
-    for (size_t k = 0; k < n_idx; ++k) LTM_REQUIRE(idx[k], "null search index");
-}
-
 } // namespace
-
-void ltm_detail::outlier_release_all(ltm_ctx* c)      // ltm_destroy: outlier sets nobody freed, and the counters
-{
-    for (ltm_outliers* s : c->outlier_open) delete s;
-    c->outlier_open.clear();
-    if (c->outlier_stats_dev) (void)hipFree(c->outlier_stats_dev);
-    c->outlier_stats_dev = nullptr;
-}
 
 extern "C" {
 
@@ -123,21 +81,20 @@ int ltm_search_filter_statistical(ltm_ctx* c, size_t n_idx, ltm_search* const* i
         LTM_REQUIRE(params && out, "null argument");
         LTM_REQUIRE(params->mean_k >= 1 && params->mean_k <= (uint32_t)(kOutlierMaxSlots - 1), "need 1 <= mean_k <= 63");
         LTM_REQUIRE(std::isfinite(params->stddev_mul), "stddev_mul must be finite");
-        check_indices(n_idx, idx);
         const int mean_k = (int)params->mean_k;
         Batch B;
         // an error leaves nothing behind: the handle dies with `made`, its blocks with it, scratch with its DevBufs
         std::unique_ptr<ltm_outliers> made = open_batch(c, n_idx, idx, LTM_OUTLIERS_STATISTICAL, (uint32_t)outlier_sor_block(mean_k), B);
         made->dist = static_cast<float*>(alloc_arrays(c, made.get()));
         if (n_idx) {
-            unsigned long long* stats = outlier_stats_dev(c);
+            unsigned long long* stats = c->outlier_stats.get(c);
             ProfScope ps(c, "outliers_sor", (double)B.total_f * (double)(mean_k + 1), 24.0 * (double)B.total_f + 5.0 * (double)made->n_points());
             DevBuf d_segs = to_device(c, B.segs), d_points = to_device(c, B.points.owner()), d_chunks = to_device(c, B.chunks.owner());      // uploads: nothing is read back
             DevBuf partials(c, std::max<size_t>(B.chunks.size(), 1) * 2 * sizeof(double));
             LTM_HIP(outlier_statistical(d_segs.as<OutlierSeg>(), d_points.as<uint32_t>(), B.points.size(), d_chunks.as<uint32_t>(), B.chunks.size(), (uint32_t)n_idx,
                                         mean_k, params->stddev_mul, made->dist, partials.as<double>(), made->out, made->labels, stats, c->stream));
         }
-        *out = adopt(c, made);
+        *out = c->open.outliers.adopt(made);
     });
 }
 
@@ -148,26 +105,25 @@ int ltm_search_filter_radius(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, c
         LTM_REQUIRE(params && out, "null argument");
         LTM_REQUIRE(std::isfinite(params->radius) && params->radius > 0.0, "radius must be finite and > 0");
         LTM_REQUIRE(params->min_neighbors >= 1, "need min_neighbors >= 1");
-        check_indices(n_idx, idx);
         const float r2 = (float)(params->radius * params->radius);
         Batch B;
         std::unique_ptr<ltm_outliers> made = open_batch(c, n_idx, idx, LTM_OUTLIERS_RADIUS, kOutlierBlock, B);
         made->counts = static_cast<uint32_t*>(alloc_arrays(c, made.get()));
         if (n_idx) {
-            unsigned long long* stats = outlier_stats_dev(c);
+            unsigned long long* stats = c->outlier_stats.get(c);
             ProfScope ps(c, "outliers_ror", (double)B.total_f, 24.0 * (double)B.total_f + 5.0 * (double)made->n_points());
             DevBuf d_segs = to_device(c, B.segs), d_points = to_device(c, B.points.owner());
             LTM_HIP(outlier_radius(d_segs.as<OutlierSeg>(), d_points.as<uint32_t>(), B.points.size(), (uint32_t)n_idx, r2, params->min_neighbors, made->counts,
                                    made->out, made->labels, stats, c->stream));
         }
-        *out = adopt(c, made);
+        *out = c->open.outliers.adopt(made);
     });
 }
 
 int ltm_outliers_info(ltm_ctx* c, ltm_outliers* h, int* kind, size_t* n_records, size_t* n_points)
 {
     return guarded(c, [&] {
-        const ltm_outliers* s = get_outliers(c, h);
+        const ltm_outliers* s = c->open.outliers.get(h);
         if (kind) *kind = s->kind;
         if (n_records) *n_records = s->n_records();
         if (n_points) *n_points = s->n_points();
@@ -178,7 +134,7 @@ int ltm_outliers_device(ltm_ctx* c, ltm_outliers* h, const uint64_t** offsets_de
                         const uint32_t** counts_dev)
 {
     return guarded(c, [&] {
-        const ltm_outliers* s = get_outliers(c, h);
+        const ltm_outliers* s = c->open.outliers.get(h);
         if (offsets_dev) *offsets_dev = s->offsets;
         if (labels_dev) *labels_dev = s->labels;
         if (distances_dev) *distances_dev = s->dist;
@@ -190,15 +146,12 @@ int ltm_outliers_download(ltm_ctx* c, ltm_outliers* h, uint32_t* n_target, uint3
                           uint8_t* labels, float* distances, uint32_t* counts)
 {
     return guarded(c, [&] {
-        const ltm_outliers* s = get_outliers(c, h);
+        const ltm_outliers* s = c->open.outliers.get(h);
         const bool sor = s->kind == LTM_OUTLIERS_STATISTICAL;
         LTM_REQUIRE(sor || !(mean || stddev || threshold || distances), "a radius outlier set has no statistics and no distances");
         LTM_REQUIRE(!sor || !counts, "a statistical outlier set has no counts");
         const size_t nr = s->n_records();
-        for (size_t k = 0; k < nr; ++k) {
-            if (n_target) n_target[k] = (uint32_t)(s->bounds[k + 1] - s->bounds[k]);
-            if (n_finite) n_finite[k] = s->n_finite[k];
-        }
+        s->record_sizes(n_target, n_finite);
         if (nr && (n_kept || mean || stddev || threshold)) {
             std::vector<OutlierRec> o(nr);
             d2h(c, o.data(), s->out, nr * sizeof(OutlierRec));
@@ -218,34 +171,22 @@ int ltm_outliers_download(ltm_ctx* c, ltm_outliers* h, uint32_t* n_target, uint3
 int ltm_outliers_split_scanset(ltm_ctx* c, ltm_outliers* h, ltm_scanset hs, ltm_scanset* kept, ltm_scanset* removed)
 {
     return guarded(c, [&] {
-        const ltm_outliers* s = get_outliers(c, h);
+        const ltm_outliers* s = c->open.outliers.get(h);
         const ScanSet& ss = get_ss(c, hs);
         const size_t nr = s->n_records();
         LTM_REQUIRE(ss.nkf() == nr, "the scan set has not one keyframe per record of the outlier set");
         for (size_t j = 0; j <= nr; ++j) LTM_REQUIRE(ss.off[j] == s->bounds[j], "a keyframe of the scan set has not as many points as its record's target");
         LTM_REQUIRE(kept && removed, "null argument");
-        float4 *d_kept, *d_removed;
-        std::vector<uint64_t> off_kept, off_removed;
-        split_by_flag(c, ss.d, s->labels, s->n_points(), s->bounds, ss.off_dev, 0, 0, &d_kept, &off_kept, &d_removed, &off_removed);
-        ltm_scanset h_kept = 0;
-        try {
-            h_kept = new_scanset(c, d_kept, std::move(off_kept));
-            d_kept = nullptr;      // the scan set owns it now
-            *removed = new_scanset(c, d_removed, std::move(off_removed));
-            *kept = h_kept;
-        } catch (...) {
-            c->pool.free(d_kept);
-            c->pool.free(d_removed);
-            if (h_kept) (void)ltm_scanset_free(c, h_kept);
-            throw;
-        }
+        FlagSplit split(c);
+        split_by_flag(c, ss.d, s->labels, s->n_points(), s->bounds, ss.off_dev, 0, 0, split);
+        split.hand_over(kept, removed);
     });
 }
 
 int ltm_outliers_split_cloud(ltm_ctx* c, ltm_outliers* h, ltm_cloud hcloud, ltm_cloud* kept, ltm_cloud* removed)
 {
     return guarded(c, [&] {
-        const ltm_outliers* s = get_outliers(c, h);
+        const ltm_outliers* s = c->open.outliers.get(h);
         LTM_REQUIRE(s->n_records() == 1, "ltm_outliers_split_cloud takes an outlier set of one record (ltm_outliers_split_scanset)");
         LTM_REQUIRE(kept && removed, "null argument");
         const Cloud cloud = get_cloud(c, hcloud);
@@ -256,24 +197,12 @@ int ltm_outliers_split_cloud(ltm_ctx* c, ltm_outliers* h, ltm_cloud hcloud, ltm_
 
 int ltm_outliers_free(ltm_ctx* c, ltm_outliers* h)
 {
-    return guarded(c, [&] {
-        get_outliers(c, h);
-        forget_handle(c->outlier_open, h);
-        delete h;
-    });
+    return guarded(c, [&] { c->open.outliers.free(h); });
 }
 
 int ltm_debug_outlier_stats(ltm_ctx* c, uint64_t* stats, int reset)
 {
-    return guarded(c, [&] {
-        if (!c->outlier_stats_dev) {      // nothing was filtered yet
-            if (stats) for (int i = 0; i < 4; ++i) stats[i] = 0;
-            return;
-        }
-        unsigned long long v[4];
-        if (stats) { d2h(c, v, c->outlier_stats_dev, sizeof v); for (int i = 0; i < 4; ++i) stats[i] = v[i]; }
-        if (reset) LTM_HIP(hipMemsetAsync(c->outlier_stats_dev, 0, sizeof v, c->stream));
-    });
+    return guarded(c, [&] { c->outlier_stats.read(c, stats, reset); });
 }
 
 } // extern "C"

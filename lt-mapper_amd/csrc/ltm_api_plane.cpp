@@ -2,10 +2,7 @@
 // pcl::SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE and SAC_RANSAC.  Kernels in ltm_k_plane.hip.
 #include "ltm_internal.h"
 
-struct ltm_planes {
-    ltm_ctx* owner = nullptr;
-    PoolBlocks blocks;                        // labels, hyp_counts, hyp_valid and the records' results: back in the pool with the handle
-    std::vector<uint64_t> bounds;             // n_records + 1 point positions of the records, from 0
+struct ltm_planes : RecordSet {               // blocks: labels, hyp_counts, hyp_valid and the records' results
     size_t kf_begin = 0;                      // the range of the scan set the handle was made from (a cloud: one record)
     bool of_cloud = false;
     uint32_t max_iterations = 0;
@@ -13,14 +10,10 @@ struct ltm_planes {
     uint32_t* counts = nullptr;               // n_records x max_iterations
     uint8_t* valid = nullptr;                 // n_records x max_iterations
     PlaneOut* out = nullptr;                  // n_records
-    explicit ltm_planes(ltm_ctx* c) : owner(c), blocks(c) {}
-    size_t n_records() const { return bounds.size() - 1; }
-    size_t n_points() const { return bounds.back(); }
+    using RecordSet::RecordSet;
 };
 
 namespace {
-
-ltm_planes* get_planes(ltm_ctx* c, ltm_planes* s) { return open_handle(c->plane_open, s, "not a plane set of this context"); }
 
 // the parameters, checked, as the kernels take them
 PlaneLaunch plane_launch(const ltm_plane_params* p)
@@ -43,16 +36,6 @@ PlaneLaunch plane_launch(const ltm_plane_params* p)
         if (L.constrained) { const double cs = cos(p->eps_angle); L.c2 = cs * cs; }
     }
     return L;
-}
-
-// the device counters of ltm_debug_plane_stats: outside the pool (they live as long as the context), made on first use
-unsigned long long* plane_stats_dev(ltm_ctx* c)
-{
-    if (!c->plane_stats_dev) {
-        LTM_HIP(hipMalloc(reinterpret_cast<void**>(&c->plane_stats_dev), 4 * sizeof(unsigned long long)));
-        LTM_HIP(hipMemsetAsync(c->plane_stats_dev, 0, 4 * sizeof(unsigned long long), c->stream));
-    }
-    return c->plane_stats_dev;
 }
 
 // records [0, bounds.size() - 1) of pts: record k holds points [bounds[k], bounds[k + 1])
@@ -79,7 +62,7 @@ std::unique_ptr<ltm_planes> segment(ltm_ctx* c, const float4* pts, std::vector<u
     P->counts = P->blocks.alloc<uint32_t>(nr * H);
     P->valid = P->blocks.alloc<uint8_t>(nr * H);
     P->out = P->blocks.alloc<PlaneOut>(nr);
-    unsigned long long* stats = plane_stats_dev(c);
+    unsigned long long* stats = c->plane_stats.get(c);
     ProfScope ps(c, "planes", (double)np * (double)H, 16.0 * (double)np + 64.0 * (double)(nr * H));
     DevBuf d_recs = to_device(c, recs), d_owner = to_device(c, table.owner());      // uploads: nothing is read back
     DevBuf hyp(c, nr * H * sizeof(PlaneHyp)), partials(c, std::max<uint64_t>(chunks, 1) * kPlaneMoments * sizeof(double));
@@ -90,21 +73,7 @@ std::unique_ptr<ltm_planes> segment(ltm_ctx* c, const float4* pts, std::vector<u
     return P;
 }
 
-ltm_planes* adopt(ltm_ctx* c, std::unique_ptr<ltm_planes>& P)
-{
-    c->plane_open.push_back(P.get());
-    return P.release();
-}
-
 } // namespace
-
-void ltm_detail::plane_release_all(ltm_ctx* c)      // ltm_destroy: plane sets nobody freed, and the counters
-{
-    for (ltm_planes* s : c->plane_open) delete s;
-    c->plane_open.clear();
-    if (c->plane_stats_dev) (void)hipFree(c->plane_stats_dev);
-    c->plane_stats_dev = nullptr;
-}
 
 extern "C" {
 
@@ -135,7 +104,7 @@ int ltm_scanset_segment_planes(ltm_ctx* c, ltm_scanset hs, size_t kf_begin, size
         // an error leaves nothing behind: the handle dies with `made`, its blocks with it, scratch with its DevBufs
         std::unique_ptr<ltm_planes> made = segment(c, s.d + first, std::move(bounds), L);
         made->kf_begin = kf_begin;
-        *out = adopt(c, made);
+        *out = c->open.planes.adopt(made);
     });
 }
 
@@ -148,14 +117,14 @@ int ltm_cloud_segment_plane(ltm_ctx* c, ltm_cloud hcloud, const ltm_plane_params
         const Cloud cloud = get_cloud(c, hcloud);
         std::unique_ptr<ltm_planes> made = segment(c, cloud.d, std::vector<uint64_t>{0, (uint64_t)cloud.n}, L);
         made->of_cloud = true;
-        *out = adopt(c, made);
+        *out = c->open.planes.adopt(made);
     });
 }
 
 int ltm_planes_info(ltm_ctx* c, ltm_planes* h, size_t* n_records, size_t* n_points, uint32_t* max_iterations)
 {
     return guarded(c, [&] {
-        const ltm_planes* s = get_planes(c, h);
+        const ltm_planes* s = c->open.planes.get(h);
         if (n_records) *n_records = s->n_records();
         if (n_points) *n_points = s->n_points();
         if (max_iterations) *max_iterations = s->max_iterations;
@@ -165,7 +134,7 @@ int ltm_planes_info(ltm_ctx* c, ltm_planes* h, size_t* n_records, size_t* n_poin
 int ltm_planes_device(ltm_ctx* c, ltm_planes* h, const uint8_t** labels_dev, const uint32_t** hyp_counts_dev, const uint8_t** hyp_valid_dev)
 {
     return guarded(c, [&] {
-        const ltm_planes* s = get_planes(c, h);
+        const ltm_planes* s = c->open.planes.get(h);
         if (labels_dev) *labels_dev = s->labels;
         if (hyp_counts_dev) *hyp_counts_dev = s->counts;
         if (hyp_valid_dev) *hyp_valid_dev = s->valid;
@@ -176,7 +145,7 @@ int ltm_planes_download(ltm_ctx* c, ltm_planes* h, uint8_t* found, int32_t* best
                         double* coeff4, double* point3, uint8_t* labels, uint32_t* hyp_counts, uint8_t* hyp_valid)
 {
     return guarded(c, [&] {
-        const ltm_planes* s = get_planes(c, h);
+        const ltm_planes* s = c->open.planes.get(h);
         const size_t nr = s->n_records(), H = s->max_iterations;
         if (nr && (found || best || consensus || n_valid || n_inliers || refined || coeff4 || point3)) {
             std::vector<PlaneOut> o(nr);
@@ -201,7 +170,7 @@ int ltm_planes_download(ltm_ctx* c, ltm_planes* h, uint8_t* found, int32_t* best
 int ltm_planes_split_scanset(ltm_ctx* c, ltm_planes* h, ltm_scanset hs, ltm_scanset* inliers, ltm_scanset* rest)
 {
     return guarded(c, [&] {
-        const ltm_planes* s = get_planes(c, h);
+        const ltm_planes* s = c->open.planes.get(h);
         LTM_REQUIRE(!s->of_cloud, "the plane set was made from a cloud (ltm_planes_split_cloud)");
         const ScanSet& ss = get_ss(c, hs);
         const size_t nr = s->n_records(), kb = s->kf_begin;
@@ -210,28 +179,16 @@ int ltm_planes_split_scanset(ltm_ctx* c, ltm_planes* h, ltm_scanset hs, ltm_scan
         for (size_t j = 0; j <= nr; ++j)
             LTM_REQUIRE(ss.off[kb + j] - first == s->bounds[j], "the scan set is not the one the plane set was made from (point counts differ)");
         LTM_REQUIRE(inliers && rest, "null argument");
-        float4 *d_in, *d_rest;
-        std::vector<uint64_t> off_in, off_rest;
-        split_by_flag(c, ss.d + first, s->labels, s->n_points(), s->bounds, ss.off_dev, kb, first, &d_in, &off_in, &d_rest, &off_rest);
-        ltm_scanset h_in = 0;
-        try {
-            h_in = new_scanset(c, d_in, std::move(off_in));
-            d_in = nullptr;      // the scan set owns it now
-            *rest = new_scanset(c, d_rest, std::move(off_rest));
-            *inliers = h_in;
-        } catch (...) {
-            c->pool.free(d_in);
-            c->pool.free(d_rest);
-            if (h_in) (void)ltm_scanset_free(c, h_in);
-            throw;
-        }
+        FlagSplit split(c);
+        split_by_flag(c, ss.d + first, s->labels, s->n_points(), s->bounds, ss.off_dev, kb, first, split);
+        split.hand_over(inliers, rest);
     });
 }
 
 int ltm_planes_split_cloud(ltm_ctx* c, ltm_planes* h, ltm_cloud hcloud, ltm_cloud* inliers, ltm_cloud* rest)
 {
     return guarded(c, [&] {
-        const ltm_planes* s = get_planes(c, h);
+        const ltm_planes* s = c->open.planes.get(h);
         LTM_REQUIRE(s->of_cloud, "the plane set was made from a scan set (ltm_planes_split_scanset)");
         LTM_REQUIRE(inliers && rest, "null argument");
         const Cloud cloud = get_cloud(c, hcloud);
@@ -242,24 +199,12 @@ int ltm_planes_split_cloud(ltm_ctx* c, ltm_planes* h, ltm_cloud hcloud, ltm_clou
 
 int ltm_planes_free(ltm_ctx* c, ltm_planes* h)
 {
-    return guarded(c, [&] {
-        get_planes(c, h);
-        forget_handle(c->plane_open, h);
-        delete h;
-    });
+    return guarded(c, [&] { c->open.planes.free(h); });
 }
 
 int ltm_debug_plane_stats(ltm_ctx* c, uint64_t* stats, int reset)
 {
-    return guarded(c, [&] {
-        if (!c->plane_stats_dev) {      // nothing was segmented yet
-            if (stats) for (int i = 0; i < 4; ++i) stats[i] = 0;
-            return;
-        }
-        unsigned long long v[4];
-        if (stats) { d2h(c, v, c->plane_stats_dev, sizeof v); for (int i = 0; i < 4; ++i) stats[i] = v[i]; }
-        if (reset) LTM_HIP(hipMemsetAsync(c->plane_stats_dev, 0, sizeof v, c->stream));
-    });
+    return guarded(c, [&] { c->plane_stats.read(c, stats, reset); });
 }
 
 } // extern "C"

@@ -3,25 +3,19 @@
 #include "ltm_internal.h"
 
 struct ltm_sc {
-    ltm_ctx* owner = nullptr;
+    PoolBlocks blocks;                // the four arrays: back in the pool with the handle
     size_t n = 0;
     int R = 0, S = 0;
     double* desc = nullptr;           // n x R x S, row-major [ring][sector]
     float* ring_keys = nullptr;       // n x R
     double* sector_keys = nullptr;    // n x S
     double* norms = nullptr;          // n x S column norms (the same at every shift)
+    explicit ltm_sc(ltm_ctx* c) : blocks(c) {}
 };
 
 namespace {
 
 constexpr int kMaxRing = 64, kMaxSector = 256, kMaxCandidates = 64;
-
-void sc_release(ltm_ctx* c, ltm_sc* s)
-{
-    c->pool.free(s->desc); c->pool.free(s->ring_keys); c->pool.free(s->sector_keys); c->pool.free(s->norms);
-    delete s;
-}
-ltm_sc* get_sc(ltm_ctx* c, ltm_sc* s) { return open_handle(c->sc_open, s, "not a scan-context set of this context"); }
 
 ltm_sc_params params_or_default(const ltm_sc_params* p)
 {
@@ -51,43 +45,22 @@ int shift_radius(const ltm_sc_params& p)
     return (int)std::min<double>(std::round(0.5 * p.search_ratio * p.num_sector), (double)p.num_sector);
 }
 
-std::unique_ptr<ltm_sc> sc_alloc(ltm_ctx* c, size_t n, int R, int S)
-{
-    std::unique_ptr<ltm_sc> s(new ltm_sc);
-    s->owner = c; s->n = n; s->R = R; s->S = S;
-    try {
-        s->desc = reinterpret_cast<double*>(c->pool.alloc(n * R * S * sizeof(double)));
-        s->ring_keys = reinterpret_cast<float*>(c->pool.alloc(n * R * sizeof(float)));
-        s->sector_keys = reinterpret_cast<double*>(c->pool.alloc(n * S * sizeof(double)));
-        s->norms = reinterpret_cast<double*>(c->pool.alloc(n * S * sizeof(double)));
-    } catch (...) {
-        sc_release(c, s.release());
-        throw;
-    }
-    return s;
-}
-
+// an error leaves nothing behind: the handle dies with `s`, its blocks with it
 template <class F>
 void sc_build(ltm_ctx* c, size_t n, const ltm_sc_params& p, ltm_sc** out, F&& fill)
 {
-    std::unique_ptr<ltm_sc> s = sc_alloc(c, n, p.num_ring, p.num_sector);
-    try {
-        fill(s.get());
-    } catch (...) {
-        sc_release(c, s.release());
-        throw;
-    }
-    c->sc_open.push_back(s.get());
-    *out = s.release();
+    std::unique_ptr<ltm_sc> s(new ltm_sc(c));
+    const size_t R = p.num_ring, S = p.num_sector;
+    s->n = n; s->R = p.num_ring; s->S = p.num_sector;
+    s->desc = s->blocks.alloc<double>(n * R * S);
+    s->ring_keys = s->blocks.alloc<float>(n * R);
+    s->sector_keys = s->blocks.alloc<double>(n * S);
+    s->norms = s->blocks.alloc<double>(n * S);
+    fill(s.get());
+    *out = c->open.sc.adopt(s);
 }
 
 } // namespace
-
-void ltm_detail::sc_release_all(ltm_ctx* c)      // ltm_destroy: descriptor sets nobody freed
-{
-    for (ltm_sc* s : c->sc_open) sc_release(c, s);
-    c->sc_open.clear();
-}
 
 extern "C" {
 
@@ -143,7 +116,7 @@ int ltm_sc_from_descriptors(ltm_ctx* c, const double* desc_host, size_t n, const
 int ltm_sc_info(ltm_ctx* c, ltm_sc* hs, size_t* n, int* num_ring, int* num_sector)
 {
     return guarded(c, [&] {
-        const ltm_sc* s = get_sc(c, hs);
+        const ltm_sc* s = c->open.sc.get(hs);
         if (n) *n = s->n;
         if (num_ring) *num_ring = s->R;
         if (num_sector) *num_sector = s->S;
@@ -153,7 +126,7 @@ int ltm_sc_info(ltm_ctx* c, ltm_sc* hs, size_t* n, int* num_ring, int* num_secto
 int ltm_sc_download(ltm_ctx* c, ltm_sc* hs, double* desc, float* ring_keys, double* sector_keys)
 {
     return guarded(c, [&] {
-        const ltm_sc* s = get_sc(c, hs);
+        const ltm_sc* s = c->open.sc.get(hs);
         if (desc) d2h(c, desc, s->desc, s->n * s->R * s->S * sizeof(double));
         if (ring_keys) d2h(c, ring_keys, s->ring_keys, s->n * s->R * sizeof(float));
         if (sector_keys) d2h(c, sector_keys, s->sector_keys, s->n * s->S * sizeof(double));
@@ -164,8 +137,8 @@ int ltm_sc_distance(ltm_ctx* c, ltm_sc* ha, ltm_sc* hb, const int32_t* pairs_hos
                     int32_t* shift_host)
 {
     return guarded(c, [&] {
-        const ltm_sc* a = get_sc(c, ha);
-        const ltm_sc* b = get_sc(c, hb);
+        const ltm_sc* a = c->open.sc.get(ha);
+        const ltm_sc* b = c->open.sc.get(hb);
         LTM_REQUIRE(a->R == b->R && a->S == b->S, "the two descriptor sets differ in num_ring / num_sector");
         const ltm_sc_params p = params_or_default(params);
         check_params(p);
@@ -190,8 +163,8 @@ int ltm_sc_detect(ltm_ctx* c, ltm_sc* hdb, ltm_sc* hq, const ltm_sc_params* para
                   float* yaw_diff_rad)
 {
     return guarded(c, [&] {
-        const ltm_sc* db = get_sc(c, hdb);
-        const ltm_sc* q = get_sc(c, hq);
+        const ltm_sc* db = c->open.sc.get(hdb);
+        const ltm_sc* q = c->open.sc.get(hq);
         LTM_REQUIRE(db->R == q->R && db->S == q->S, "the two descriptor sets differ in num_ring / num_sector");
         const ltm_sc_params p = params_or_default(params);
         check_params(p);
@@ -247,11 +220,7 @@ int ltm_debug_sc_paths(int num_ring, int num_sector, int* scatter_in_lds, int* p
 
 int ltm_sc_free(ltm_ctx* c, ltm_sc* s)
 {
-    return guarded(c, [&] {
-        get_sc(c, s);
-        forget_handle(c->sc_open, s);
-        sc_release(c, s);
-    });
+    return guarded(c, [&] { c->open.sc.free(s); });
 }
 
 } // extern "C"

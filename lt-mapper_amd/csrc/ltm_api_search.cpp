@@ -3,8 +3,7 @@
 #include "ltm_internal.h"
 
 struct ltm_search {
-    ltm_ctx* owner = nullptr;
-    std::shared_ptr<PoolBlocks> batch;    // set: pts / idx / keys / box point into the blocks that the indices of one ltm_search_build_scanset share
+    std::shared_ptr<PoolBlocks> blocks;   // what pts / idx / keys / box point into: the index's own, or shared by the indices of one ltm_search_build_scanset
     std::shared_ptr<PoolBlocks> nblock;   // set: normals points into the block of one ltm_search_estimate_normals (released with the last index, or estimated again)
     float4* normals = nullptr;            // (nx, ny, nz, curvature) of pts[j], Mf of them
     int normals_k = 0;                    // 0: none estimated
@@ -18,25 +17,13 @@ struct ltm_search {
     SearchTree tree() const { return SearchTree{pts, idx, keys, box, Mf, L, P}; }
 };
 struct ltm_search_result {
-    ltm_ctx* owner = nullptr;
+    PoolBlocks blocks;                  // off, idx, d2: back in the pool with the handle
     size_t n_query = 0, total = 0;
     uint64_t* off = nullptr; int32_t* idx = nullptr; float* d2 = nullptr;
+    explicit ltm_search_result(ltm_ctx* c) : blocks(c) {}
 };
 
 namespace {
-
-void search_release(ltm_ctx* c, ltm_search* s)
-{
-    if (!s->batch) { c->pool.free(s->pts); c->pool.free(s->idx); c->pool.free(s->keys); c->pool.free(s->box); }
-    delete s;
-}
-void result_release(ltm_ctx* c, ltm_search_result* r)
-{
-    c->pool.free(r->off); c->pool.free(r->idx); c->pool.free(r->d2);
-    delete r;
-}
-ltm_search* get_search(ltm_ctx* c, ltm_search* s) { return open_handle(c->search_open, s, "not a search index of this context"); }
-ltm_search_result* get_result(ltm_ctx* c, ltm_search_result* r) { return open_handle(c->result_open, r, "not a search result of this context"); }
 
 SearchFrame frame_of(const float mn[3], const float mx[3]);
 void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
@@ -52,20 +39,21 @@ void build_index(ltm_ctx* c, ltm_search* s, const Cloud& target)
     s->f = frame_of(mn, mx);
     // codes of every point (non-finite: ~0, sorted behind the finite ones) -> the first Mf entries of the sorted arrays are the index
     DevBuf keys(c, n * 8), idx(c, n * 4);
-    s->keys = reinterpret_cast<uint64_t*>(c->pool.alloc(n * 8));
-    s->idx = reinterpret_cast<uint32_t*>(c->pool.alloc(n * 4));
+    s->blocks = std::make_shared<PoolBlocks>(c);
+    s->keys = s->blocks->alloc<uint64_t>(n);
+    s->idx = s->blocks->alloc<uint32_t>(n);
     LTM_HIP(search_keys(target.d, n, s->f, keys.as<uint64_t>(), idx.as<uint32_t>(), c->stream));
     {
         const size_t tb = sort_temp_bytes(n);
         DevBuf temp(c, tb);
         LTM_HIP(sort_pairs_u64(keys.as<uint64_t>(), s->keys, idx.as<uint32_t>(), s->idx, n, 64, temp.p, tb, c->stream));
     }
-    s->pts = reinterpret_cast<float4*>(c->pool.alloc((size_t)s->Mf * sizeof(float4)));
+    s->pts = s->blocks->alloc<float4>(s->Mf);
     LTM_HIP(gather_points(target.d, s->idx, s->Mf, s->pts, c->stream));
     s->L = (s->Mf + kSearchLeaf - 1) / kSearchLeaf;
     s->P = 1;
     while (s->P < s->L) s->P <<= 1;
-    s->box = reinterpret_cast<float4*>(c->pool.alloc((size_t)4 * s->P * sizeof(float4)));
+    s->box = s->blocks->alloc<float4>((size_t)4 * s->P);
     LTM_HIP(search_tree_boxes(s->pts, s->Mf, s->L, s->P, s->box, c->stream));
 }
 
@@ -91,7 +79,6 @@ void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std:
     BlockTable table;
     for (size_t k = 0; k < nk; ++k) {
         out[k].reset(new ltm_search);
-        out[k]->owner = c;
         out[k]->n_target = ss.off[kb + k + 1] - ss.off[kb + k];
         SearchSeg& S = segs[k];
         memset(&S, 0, sizeof S);
@@ -142,7 +129,7 @@ void build_index_batch(ltm_ctx* c, const ScanSet& ss, size_t kb, size_t ke, std:
     for (size_t k = 0; k < nk; ++k) {
         ltm_search* s = out[k].get();
         if (!s->Mf) continue;
-        s->batch = batch;
+        s->blocks = batch;
         s->pts = pts + segs[k].first; s->idx = order + segs[k].first; s->keys = keys_sorted + segs[k].first; s->box = box + segs[k].box0;
     }
 }
@@ -161,24 +148,16 @@ struct QueryOrder {
 
 } // namespace
 
-void ltm_detail::search_release_all(ltm_ctx* c)      // ltm_destroy: indices and results nobody freed
-{
-    for (ltm_search* s : c->search_open) search_release(c, s);
-    for (ltm_search_result* r : c->result_open) result_release(c, r);
-    c->search_open.clear();
-    c->result_open.clear();
-}
-
 void ltm_detail::search_view(ltm_ctx* c, ltm_search* s, SearchTree* tree, SearchFrame* frame)
 {
-    get_search(c, s);
+    c->open.search.get(s);
     *tree = s->tree();
     *frame = s->f;
 }
 
 const float4* ltm_detail::search_normals(ltm_ctx* c, ltm_search* s, int* k)
 {
-    get_search(c, s);
+    c->open.search.get(s);
     if (k) *k = s->normals_k;
     return s->normals;
 }
@@ -194,7 +173,7 @@ int ltm_search_estimate_normals(ltm_ctx* c, size_t n_idx, ltm_search* const* idx
         LTM_REQUIRE(n_idx < 0x7fffffffull, "too many indices");
         // everything is checked before anything changes: an error leaves every index as it was
         std::vector<ltm_search*> seen(idx, idx + n_idx);
-        for (size_t i = 0; i < n_idx; ++i) get_search(c, idx[i]);
+        for (size_t i = 0; i < n_idx; ++i) c->open.search.get(idx[i]);
         std::sort(seen.begin(), seen.end());
         LTM_REQUIRE(std::adjacent_find(seen.begin(), seen.end()) == seen.end(), "an index is listed twice");
         const uint32_t block = (uint32_t)normals_block(k);
@@ -234,7 +213,7 @@ int ltm_search_estimate_normals(ltm_ctx* c, size_t n_idx, ltm_search* const* idx
 int ltm_search_normals_info(ltm_ctx* c, ltm_search* s, int* k, const void** normals_dev)
 {
     return guarded(c, [&] {
-        get_search(c, s);
+        c->open.search.get(s);
         if (k) *k = s->normals_k;
         if (normals_dev) *normals_dev = s->normals;
     });
@@ -243,7 +222,7 @@ int ltm_search_normals_info(ltm_ctx* c, ltm_search* s, int* k, const void** norm
 int ltm_search_normals_download(ltm_ctx* c, ltm_search* s, float* nxyzc_host)
 {
     return guarded(c, [&] {
-        get_search(c, s);
+        c->open.search.get(s);
         LTM_REQUIRE(s->normals_k != 0, "the index has no normals (ltm_search_estimate_normals)");
         if (!s->n_target) return;
         LTM_REQUIRE(nxyzc_host, "null argument");
@@ -266,16 +245,9 @@ int ltm_search_build(ltm_ctx* c, ltm_cloud htarget, ltm_search** out)
     return guarded(c, [&] {
         LTM_REQUIRE(out, "null argument");
         const Cloud target = get_cloud(c, htarget);
-        std::unique_ptr<ltm_search> s(new ltm_search);
-        s->owner = c;
-        try {
-            build_index(c, s.get(), target);
-        } catch (...) {
-            search_release(c, s.release());
-            throw;
-        }
-        c->search_open.push_back(s.get());
-        *out = s.release();
+        std::unique_ptr<ltm_search> s(new ltm_search);      // an error leaves nothing behind: the handle dies with `s`, its blocks with it
+        build_index(c, s.get(), target);
+        *out = c->open.search.adopt(s);
     });
 }
 
@@ -289,27 +261,19 @@ int ltm_search_build_scanset(ltm_ctx* c, ltm_scanset hss, size_t kf_begin, size_
         std::vector<std::unique_ptr<ltm_search>> made;
         // an error leaves nothing behind: the handles die with `made`, the shared blocks with the last reference to the batch, scratch with its DevBufs
         build_index_batch(c, ss, kf_begin, kf_end, made);
-        c->search_open.reserve(c->search_open.size() + made.size());
-        for (size_t k = 0; k < made.size(); ++k) {
-            c->search_open.push_back(made[k].get());
-            out[k] = made[k].release();
-        }
+        c->open.search.adopt(made, out);
     });
 }
 
 int ltm_search_free(ltm_ctx* c, ltm_search* s)
 {
-    return guarded(c, [&] {
-        get_search(c, s);
-        forget_handle(c->search_open, s);
-        search_release(c, s);
-    });
+    return guarded(c, [&] { c->open.search.free(s); });
 }
 
 int ltm_search_info(ltm_ctx* c, ltm_search* s, size_t* n_target, size_t* n_finite)
 {
     return guarded(c, [&] {
-        get_search(c, s);
+        c->open.search.get(s);
         if (n_target) *n_target = s->n_target;
         if (n_finite) *n_finite = s->Mf;
     });
@@ -318,7 +282,7 @@ int ltm_search_info(ltm_ctx* c, ltm_search* s, size_t* n_target, size_t* n_finit
 int ltm_knn_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, int k, int32_t* idx_dev, float* d2_dev)
 {
     return guarded(c, [&] {
-        const ltm_search* s = get_search(c, hs);
+        const ltm_search* s = c->open.search.get(hs);
         LTM_REQUIRE(k >= 1 && k <= 64, "k must be in [1, 64]");
         const Cloud q = get_cloud(c, hquery);
         if (!q.n) return;
@@ -334,17 +298,16 @@ int ltm_knn_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, int k, int32_t*
 int ltm_radius_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, float radius, int max_nn, ltm_search_result** out)
 {
     return guarded(c, [&] {
-        const ltm_search* s = get_search(c, hs);
+        const ltm_search* s = c->open.search.get(hs);
         LTM_REQUIRE(out, "null argument");
         LTM_REQUIRE(!std::isnan(radius), "radius is NaN");
         LTM_REQUIRE(max_nn >= 0, "max_nn must be >= 0 (0: no limit)");
         const Cloud q = get_cloud(c, hquery);
         LTM_REQUIRE(q.n < 0x80000000ull, "too many queries");
         const float r2 = (float)((double)radius * (double)radius);
-        std::unique_ptr<ltm_search_result, void (*)(ltm_search_result*)> r(new ltm_search_result, [](ltm_search_result* p) { result_release(p->owner, p); });
-        r->owner = c;
+        std::unique_ptr<ltm_search_result> r(new ltm_search_result(c));
         r->n_query = q.n;
-        r->off = reinterpret_cast<uint64_t*>(c->pool.alloc((q.n + 1) * sizeof(uint64_t)));
+        r->off = r->blocks.alloc<uint64_t>(q.n + 1);
         uint64_t tot[2] = {0, 0};      // all hits, hits kept (max_nn)
         if (q.n && s->Mf) {
             QueryOrder qo(c, s, q);
@@ -362,8 +325,8 @@ int ltm_radius_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, float radius
             d2h(c, tot, tb2.p, 16);      // the one host round trip: the sizes of the outputs
             LTM_REQUIRE(tot[0] < 0x100000000ull, "more than 2^32 hits in one radius search");
             r->total = tot[1];
-            r->idx = reinterpret_cast<int32_t*>(c->pool.alloc(std::max<size_t>(tot[1], 1) * 4));
-            r->d2 = reinterpret_cast<float*>(c->pool.alloc(std::max<size_t>(tot[1], 1) * 4));
+            r->idx = r->blocks.alloc<int32_t>(std::max<size_t>(tot[1], 1));
+            r->d2 = r->blocks.alloc<float>(std::max<size_t>(tot[1], 1));
             if (tot[0]) {
                 ProfScope ps(c, "radius_fill", (double)tot[0], (double)q.n * 20.0 + 16.0 * (double)tot[0] + 8.0 * (double)tot[1]);
                 DevBuf pairs(c, tot[0] * 8), sorted(c, tot[0] * 8);
@@ -374,11 +337,10 @@ int ltm_radius_search(ltm_ctx* c, ltm_search* hs, ltm_cloud hquery, float radius
             }
         } else {
             LTM_HIP(hipMemsetAsync(r->off, 0, (q.n + 1) * sizeof(uint64_t), c->stream));
-            r->idx = reinterpret_cast<int32_t*>(c->pool.alloc(4));
-            r->d2 = reinterpret_cast<float*>(c->pool.alloc(4));
+            r->idx = r->blocks.alloc<int32_t>(1);
+            r->d2 = r->blocks.alloc<float>(1);
         }
-        c->result_open.push_back(r.get());
-        *out = r.release();
+        *out = c->open.result.adopt(r);
     });
 }
 
@@ -386,7 +348,7 @@ int ltm_search_result_info(ltm_ctx* c, ltm_search_result* hr, size_t* n_query, s
                            const float** d2_dev)
 {
     return guarded(c, [&] {
-        const ltm_search_result* r = get_result(c, hr);
+        const ltm_search_result* r = c->open.result.get(hr);
         if (n_query) *n_query = r->n_query;
         if (total) *total = r->total;
         if (offsets_dev) *offsets_dev = r->off;
@@ -397,11 +359,7 @@ int ltm_search_result_info(ltm_ctx* c, ltm_search_result* hr, size_t* n_query, s
 
 int ltm_search_result_free(ltm_ctx* c, ltm_search_result* r)
 {
-    return guarded(c, [&] {
-        get_result(c, r);
-        forget_handle(c->result_open, r);
-        result_release(c, r);
-    });
+    return guarded(c, [&] { c->open.result.free(r); });
 }
 
 int ltm_debug_pool_live(ltm_ctx* c, uint64_t* live_blocks, uint64_t* live_bytes)

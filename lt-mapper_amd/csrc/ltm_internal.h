@@ -1,4 +1,4 @@
-// ltm_internal.h -- what the translation units of the C ABI (ltm_api_*.cpp) share: error type, the stream-ordered pool, handle tables, the context,
+// ltm_internal.h -- what the translation units of the C ABI (ltm_api_*.cpp) share: error type, the stream-ordered pool, handle tables, the open lists of the pointer handles, the context,
 // scratch / profiling / transfer helpers and the entry-point guard.  Internal to libltm_hip.so (include/ltm.h is the interface).  No CPU fallback: every
 // stage runs on the device or fails with an error code.  One stage has a host HALF by design: ltm_voxel_grid_scanset's default order -- the permutation
 // pcl::VoxelGrid's std::sort leaves the points of a voxel in is a property of libstdc++'s introsort, reproduced on host threads (ltm_pclsort.h, which
@@ -203,6 +203,67 @@ struct PinnedBlock { void* p; size_t bytes; bool in_use; };
 // staging buffers before a DMA is issued; one hipMemcpyAsync + event per 54 k-point scan cost ~0.1 ms of fixed overhead each, 55 ms per 500-keyframe session)
 struct UploadState { float4* d = nullptr; size_t cap = 0, n = 0; std::vector<uint64_t> off{0}; void* stage[2] = {nullptr, nullptr}; size_t stage_sz[2] = {0, 0}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; int next = 0; size_t fill = 0, flushed = 0; };
 
+
+// ---- the pointer handles of the C ABI (ltm_search, ltm_search_result, ltm_sc, ltm_clusters, ltm_planes, ltm_outliers, ltm_fpfh); the rule: DESIGN.md 4.4b
+// A handle holds its device arrays in PoolBlocks (below): a member, or a std::shared_ptr where the handles of one batch share blocks.  Its destructor
+// returns them, so `delete` is the only way a handle's memory goes back and a half-built handle in a std::unique_ptr cleans up after itself.
+// OpenHandles<H>: the handles of ONE type that a context has given out and not got back.  A freed handle, one of another type, of another context or of
+// a lane is not in the list and is refused with `what` before it is dereferenced.
+template <class H>
+struct OpenHandles {
+    const char* what;
+    std::vector<H*> open;
+    void (*destroy)(H*) = nullptr;      // set by adopt, where H is a complete type: release_all (ltm_destroy) needs no definition of H
+    H* get(H* h) const
+    {
+        LTM_REQUIRE(h && std::find(open.begin(), open.end(), h) != open.end(), what);
+        return h;
+    }
+    // the list takes the handle over: the LAST thing an entry point does that can throw
+    H* adopt(std::unique_ptr<H>& made)
+    {
+        destroy = [](H* h) { delete h; };
+        open.push_back(made.get());
+        return made.release();
+    }
+    // the handles of one batch: room for all of them first, so that no push_back can throw half-way
+    void adopt(std::vector<std::unique_ptr<H>>& made, H** out)
+    {
+        open.reserve(open.size() + made.size());
+        for (size_t k = 0; k < made.size(); ++k) out[k] = adopt(made[k]);
+    }
+    void free(H* h)
+    {
+        get(h);
+        open.erase(std::remove(open.begin(), open.end(), h), open.end());
+        delete h;
+    }
+    void release_all()      // ltm_destroy: what nobody freed
+    {
+        for (H* h : open) destroy(h);
+        open.clear();
+    }
+};
+// one list per handle type (the type check is the list); released in this order: the indices before the sets computed from them
+struct OpenLists {
+    OpenHandles<ltm_search> search{"not a search index of this context"};
+    OpenHandles<ltm_search_result> result{"not a search result of this context"};
+    OpenHandles<ltm_sc> sc{"not a scan-context set of this context"};
+    OpenHandles<ltm_clusters> clusters{"not a cluster set of this context"};
+    OpenHandles<ltm_planes> planes{"not a plane set of this context"};
+    OpenHandles<ltm_outliers> outliers{"not an outlier set of this context"};
+    OpenHandles<ltm_fpfh> fpfh{"not a descriptor set of this context"};
+    void release_all() { search.release_all(); result.release_all(); sc.release_all(); clusters.release_all(); planes.release_all(); outliers.release_all(); fpfh.release_all(); }
+};
+// The four device counters of a feature whose entry points read nothing back (ltm_debug_plane_stats, _outlier_stats, _fpfh_stats): outside the pool (they
+// live as long as the context), made and zeroed on first use
+struct DevCounters {
+    unsigned long long* d = nullptr;
+    unsigned long long* get(ltm_ctx* c);                        // what the kernels count into
+    void read(ltm_ctx* c, uint64_t* stats, int reset);          // never made: zeros, nothing is touched
+    void release() { if (d) (void)hipFree(d); d = nullptr; }    // ltm_destroy
+};
+
 } // namespace ltm_detail
 using namespace ltm_detail;
 
@@ -324,18 +385,10 @@ struct ltm_ctx {
     std::vector<PinnedBlock> pinned;
     std::unordered_map<uint64_t, UploadState> uploads;
     std::vector<struct ltm_vgs*> vgs_open;      // ltm_voxel_grid_scanset_begin tickets not ended yet: joined and released by ltm_destroy at the latest
-    std::vector<struct ltm_search*> search_open;            // search indices and radius results not freed yet: released by ltm_destroy at the latest
-    std::vector<struct ltm_search_result*> result_open;
-    std::vector<struct ltm_sc*> sc_open;                    // scan-context descriptor sets not freed yet: released by ltm_destroy at the latest
-    std::vector<struct ltm_clusters*> cluster_open;         // cluster sets (ltm_search_cluster) not freed yet: released by ltm_destroy at the latest
+    OpenLists open;                             // the pointer handles not freed yet: released by ltm_destroy at the latest
     int cluster_clique = 1;                     // LTM_CLUSTER_CLIQUE=0: no clique leaves in ltm_search_cluster (A/B switch; the result is the same)
     uint64_t cluster_stats[6] = {0, 0, 0, 0, 0, 0};      // ltm_debug_cluster_stats: pairs tested, edges found, leaves visited, clique leaves, clique early exits, hook retries
-    std::vector<struct ltm_planes*> plane_open;             // plane sets (ltm_scanset_segment_planes, ltm_cloud_segment_plane) not freed yet: released by ltm_destroy at the latest
-    unsigned long long* plane_stats_dev = nullptr;          // device, 4 counters (ltm_debug_plane_stats): the segmentation reads nothing back, so they are kept there; made on first use
-    std::vector<struct ltm_outliers*> outlier_open;         // outlier sets (ltm_search_filter_statistical, ltm_search_filter_radius) not freed yet: released by ltm_destroy at the latest
-    unsigned long long* outlier_stats_dev = nullptr;        // device, 4 counters (ltm_debug_outlier_stats): the filters read nothing back; made on first use
-    std::vector<struct ltm_fpfh*> fpfh_open;                // descriptor sets (ltm_search_fpfh) not freed yet: released by ltm_destroy at the latest
-    unsigned long long* fpfh_stats_dev = nullptr;           // device, 4 counters (ltm_debug_fpfh_stats); made on first use
+    DevCounters plane_stats, outlier_stats, fpfh_stats;
     int fpfh_lists = 1;                         // LTM_FPFH_LISTS=0: ltm_search_fpfh never keeps the neighbour lists of its first pass (A/B switch; the result is the same)
 };
 
@@ -474,7 +527,8 @@ inline DevBuf to_device(ltm_ctx* c, const std::vector<T>& v)
     return d;
 }
 
-// Pool blocks with one owner that several handles may share through a std::shared_ptr: back in the pool with the last of them
+// Pool blocks with one owner, back in the pool with it: a member of the handle that owns them alone, or shared by several handles through a
+// std::shared_ptr and back with the last of them
 struct PoolBlocks {
     ltm_ctx* c;
     std::vector<void*> blocks;
@@ -486,16 +540,21 @@ struct PoolBlocks {
     void release(void* p) { blocks.erase(std::remove(blocks.begin(), blocks.end(), p), blocks.end()); }      // p has another owner now
 };
 
-// The open-handle lists of a context (search_open, result_open, ...): a handle of THIS context, or throw `what` -- a freed one, one of another context
-// or a lane's is refused before it is dereferenced; and the list forgetting one
-template <class H>
-inline H* open_handle(const std::vector<H*>& open, H* h, const char* what)
+inline unsigned long long* DevCounters::get(ltm_ctx* c)
 {
-    LTM_REQUIRE(h && std::find(open.begin(), open.end(), h) != open.end(), what);
-    return h;
+    if (!d) {
+        LTM_HIP(hipMalloc(reinterpret_cast<void**>(&d), 4 * sizeof(unsigned long long)));
+        LTM_HIP(hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), c->stream));
+    }
+    return d;
 }
-template <class H>
-inline void forget_handle(std::vector<H*>& open, H* h) { open.erase(std::remove(open.begin(), open.end(), h), open.end()); }
+inline void DevCounters::read(ltm_ctx* c, uint64_t* stats, int reset)
+{
+    unsigned long long v[4] = {0, 0, 0, 0};
+    if (d && stats) d2h(c, v, d, sizeof v);
+    if (stats) for (int i = 0; i < 4; ++i) stats[i] = v[i];
+    if (d && reset) LTM_HIP(hipMemsetAsync(d, 0, sizeof v, c->stream));
+}
 
 // min / max corners of a box of six ordered keys
 inline void decode_box(const uint32_t* enc, float mn[3], float mx[3])
@@ -559,13 +618,44 @@ inline ltm_cloud alloc_cloud(ltm_ctx* c, size_t n, float4** d)
 inline ltm_scanset new_scanset(ltm_ctx* c, float4* d, std::vector<uint64_t> off)
 {
     ScanSet s;
+    PoolBlocks own(c);      // the offset table until the scan set is in the context's map: a throw leaves nothing behind (d stays the caller's)
     s.d = d; s.n_pts = off.back(); s.off = std::move(off);
-    s.off_dev = reinterpret_cast<uint64_t*>(c->pool.alloc(s.off.size() * sizeof(uint64_t)));
+    s.off_dev = own.alloc<uint64_t>(s.off.size());
     h2d(c, s.off_dev, s.off.data(), s.off.size() * sizeof(uint64_t));
     const uint64_t h = c->next_handle++;
     c->scansets[h] = std::move(s);
+    own.release(s.off_dev);      // (a pointer: the move left it as it was)
     return h;
 }
+// What split_by_flag (ltm_api_knn.cpp) leaves: the two halves of a flagged point range with their per-keyframe offsets, owned here until handed over
+struct FlagSplit {
+    PoolBlocks blocks;
+    float4 *d_set = nullptr, *d_unset = nullptr;
+    std::vector<uint64_t> off_set, off_unset;
+    explicit FlagSplit(ltm_ctx* c) : blocks(c) {}
+    // The halves become scan sets: *set and *unset; a null output is not wanted and its half goes back to the pool.  On any throw neither block and
+    // neither handle is left behind, and no output is written.
+    void hand_over(ltm_scanset* set, ltm_scanset* unset)
+    {
+        ltm_ctx* c = blocks.c;
+        auto one = [&](float4* d, std::vector<uint64_t>& off, bool wanted) {
+            const ltm_scanset h = wanted ? new_scanset(c, d, std::move(off)) : 0;
+            if (!wanted) c->pool.free(d);
+            blocks.release(d);      // the scan set owns it now, or the pool has it back
+            return h;
+        };
+        const ltm_scanset h_set = one(d_set, off_set, set != nullptr);
+        ltm_scanset h_unset = 0;
+        try {
+            h_unset = one(d_unset, off_unset, unset != nullptr);
+        } catch (...) {
+            if (h_set) (void)ltm_scanset_free(c, h_set);
+            throw;
+        }
+        if (set) *set = h_set;
+        if (unset) *unset = h_unset;
+    }
+};
 
 inline bool mat_is_identity(const double* m16)
 {
@@ -720,7 +810,6 @@ void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
 void vgs_release_all(ltm_ctx* c);                                                 // ltm_api_voxel.cpp: open ltm_voxel_grid_scanset tickets, at ltm_destroy
 int voxel_grid_scanset_ordered(ltm_ctx* c, ltm_scanset in, float leaf, int order, ltm_scanset* out);   // ltm_api_voxel.cpp: ltm_voxel_grid_scanset with the order as an argument (1 PCL, 0 input)
-void search_release_all(ltm_ctx* c);                                              // ltm_api_search.cpp: open search indices and results, at ltm_destroy
 void search_view(ltm_ctx* c, struct ltm_search* s, SearchTree* tree, SearchFrame* frame);   // ltm_api_search.cpp: tree and frame of an index OF THIS CONTEXT (throws otherwise)
 // The listed indices of one batched call (clusters, outlier filters) as its records, checked before the device is touched: each(k, L) per index in order,
 // L.span its workgroups of per_block finite points in `table`.  Throws what search_view refuses, `over_table` when the table is full and `over_2_31` when
@@ -746,14 +835,38 @@ void for_listed_indices(ltm_ctx* c, size_t n_idx, struct ltm_search* const* idx,
     }
     if (total_t >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, over_2_31};
 }
+// the list itself, before anything looks at an entry: fewer than `limit` indices (the caller's own), a list where there are any, no null entry
+inline void check_listed_indices(size_t n_idx, struct ltm_search* const* idx, size_t limit)
+{
+    LTM_REQUIRE(n_idx < limit, "too many indices");
+    LTM_REQUIRE(!n_idx || idx, "null argument");
+    for (size_t k = 0; k < n_idx; ++k) LTM_REQUIRE(idx[k], "null search index");
+}
+// What the record sets share.  ltm_planes: records are ranges of points
+struct RecordSet {
+    PoolBlocks blocks;                        // every device array of the set: back in the pool with the handle
+    std::vector<uint64_t> bounds{0};          // n_records + 1 point positions of the records, from 0
+    explicit RecordSet(ltm_ctx* c) : blocks(c) {}
+    size_t n_records() const { return bounds.size() - 1; }
+    size_t n_points() const { return bounds.back(); }
+};
+// ltm_outliers, ltm_fpfh: one record per listed index, every record in its target's original order
+struct IndexRecordSet : RecordSet {
+    std::vector<uint32_t> n_finite;           // per record
+    uint64_t* offsets = nullptr;              // n_records + 1, the device copy of bounds
+    IndexRecordSet(ltm_ctx* c, size_t n_idx) : RecordSet(c), n_finite(n_idx, 0) { bounds.assign(n_idx + 1, 0); }
+    void set_record(size_t k, const ListedIndex& L) { bounds[k + 1] = L.tbase + L.n_target; n_finite[k] = L.t.Mf; }
+    void record_sizes(uint32_t* n_target, uint32_t* n_fin) const      // the caller's per-record arrays, either may be null
+    {
+        for (size_t k = 0; k < n_records(); ++k) {
+            if (n_target) n_target[k] = (uint32_t)(bounds[k + 1] - bounds[k]);
+            if (n_fin) n_fin[k] = n_finite[k];
+        }
+    }
+};
 const float4* search_normals(ltm_ctx* c, struct ltm_search* s, int* k);            // ltm_api_search.cpp: the normals of an index of this context (aligned with its tree's pts; null and *k = 0: none)
-void sc_release_all(ltm_ctx* c);                                                  // ltm_api_scancontext.cpp: open descriptor sets, at ltm_destroy
-void cluster_release_all(ltm_ctx* c);                                             // ltm_api_cluster.cpp: open cluster sets, at ltm_destroy
-void plane_release_all(ltm_ctx* c);                                               // ltm_api_plane.cpp: open plane sets and the device counters, at ltm_destroy
-void outlier_release_all(ltm_ctx* c);                                             // ltm_api_outlier.cpp: open outlier sets and the device counters, at ltm_destroy
-void fpfh_release_all(ltm_ctx* c);                                                // ltm_api_fpfh.cpp: open descriptor sets and the device counters, at ltm_destroy
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
-                   size_t kf0, uint64_t first, float4** d_set, std::vector<uint64_t>* off_set, float4** d_unset, std::vector<uint64_t>* off_unset);   // ltm_api_knn.cpp
+                   size_t kf0, uint64_t first, FlagSplit& out);   // ltm_api_knn.cpp
 
 } // namespace ltm_detail
 using namespace ltm_detail;
