@@ -267,6 +267,18 @@ int ltm_visibility_partition(ltm_ctx*, ltm_cloud map, ltm_scanset scans, ltm_pos
 /* parseProjectedPoints / Session::parseScansViaProjection (utility.cpp:74-89, Session.cpp:348-360):
  * out has (kf_end-kf_begin) keyframes of local-frame points, row-major pixel order, ptidx==0 dropped. */
 int ltm_reproject(ltm_ctx*, ltm_cloud map, ltm_poses poses, size_t kf_begin, size_t kf_end, float res_alpha, ltm_scanset* out);
+/* Two maps at once: out_a / out_b are exactly what ltm_reproject(map_a) and ltm_reproject(map_b) return.  Meant for two voxel grids of clouds that share
+ * nearly all their points (map_global_updated_ and its "strong" twin, Removerter.cpp:1483-1524): where both maps carry the frame of their grid and the frames
+ * and leaves are equal, the points that are bit-identical in both (all four floats; -0.0 and +0.0 differ) are projected ONCE by the exact-image kernel, the image's
+ * point indices are replaced through two increasing tables, and the few points each map has alone are added with their own indices (the image is
+ * a minimum, and both maps list the shared points in the same order).  Two plain reprojections instead when a cloud is empty or has no frame, the frames
+ * differ, the shared points are fewer than LTM_REPROJECT_TWIN_MIN_SHARED (default 0.75) of the larger map, or the context was created with
+ * LTM_REPROJECT_TWIN=0 (A/B switch).  ltm_debug_reproject_twin_stats counts which way the calls went. */
+int ltm_reproject_twin(ltm_ctx*, ltm_cloud map_a, ltm_cloud map_b, ltm_poses poses, size_t kf_begin, size_t kf_end, float res_alpha, ltm_scanset* out_a,
+                       ltm_scanset* out_b);
+/* *applicable = 1 when ltm_reproject_twin would look for shared points (switch on, both clouds hold points and the frame of their grid, frames and leaves equal),
+ * 0 when it is two plain reprojections from the start.  Host side only, nothing is launched: a caller with two lanes keeps the two maps on two lanes then. */
+int ltm_reproject_twin_applicable(ltm_ctx*, ltm_cloud map_a, ltm_cloud map_b, int* applicable);
 
 /* extractLowDynPointsViaKnnDiff / extractHighDynPointsViaKnnDiff (Session.cpp:393-427, 487-504, 537-642):
  * exact k-NN of every scan point (moved to the global frame) in `target`; coexist iff mean of the k squared
@@ -987,6 +999,10 @@ int ltm_debug_occlusion_stats(ltm_ctx*, uint64_t* pairs, uint64_t* first_shell, 
  * input an order-preserving subset of an earlier grid's output, still in octree order and one point per voxel under the frame this
  * call derives: output = copy of the input, bit for bit what the sort + centroid path gives) */
 int ltm_debug_voxel_stats(ltm_ctx*, uint64_t* grids, uint64_t* identity_hits, int reset);
+/* ltm_reproject_twin since the last reset, stats[8]: calls, calls that projected the shared points once, calls that ran two plain reprojections instead,
+ * those plain reprojections, joins whose shared points did not pair up in order (counted among the fallbacks), and the points of map_a, of map_b and of
+ * their shared part as the last join saw them */
+int ltm_debug_reproject_twin_stats(ltm_ctx*, uint64_t* stats /* 8 */, int reset);
 /* ltm_knn_partition's two-phase query (k <= 4, more than 64 target points, LTM_KNN_FAST != 0) since the last reset: scan queries it served,
  * queries its bucket test (phase 1) left undecided for the exact search, calls that took the two-phase path, and calls among them whose
  * cell id + query index did not fit 64 bits so that phase 2 walked its queue in scan order.  All four are counted only in a context created

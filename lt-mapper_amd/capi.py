@@ -159,6 +159,9 @@ SIGNATURES = {
     "ltm_scanset_lend": (_i, [_vp, _u64, _vp, _pu64]),
     "ltm_scanset_give": (_i, [_vp, _u64, _vp, _pu64]),
     "ltm_reproject": (_i, [_vp, _u64, _u64, _sz, _sz, _f, _pu64]),
+    "ltm_reproject_twin": (_i, [_vp, _u64, _u64, _u64, _sz, _sz, _f, _pu64, _pu64]),
+    "ltm_reproject_twin_applicable": (_i, [_vp, _u64, _u64, C.POINTER(_i)]),
+    "ltm_debug_reproject_twin_stats": (_i, [_vp, _pu64, _i]),
     "ltm_knn_partition": (_i, [_vp, _u64, _u64, _u64, _sz, _sz, _i, _f, _pu64, _pu64]),
     "ltm_knn_split_cloud": (_i, [_vp, _u64, _u64, _i, _f, _pu64, _pu64]),
     "ltm_search_build": (_i, [_vp, _u64, C.POINTER(_vp)]),
@@ -674,6 +677,27 @@ class Context:
         out = _u64()
         self._ck(self.lib.ltm_reproject(self.h, cmap.h, poses.h, kf_begin, poses.n if kf_end is None else kf_end, alpha, C.byref(out)))
         return ScanSet(self, out.value)
+
+    def reproject_twin(self, cmap_a, cmap_b, poses, alpha=3.0, kf_begin=0, kf_end=None):
+        """ltm_reproject_twin: (reproject(cmap_a), reproject(cmap_b)), the points that two grids of one frame share projected once"""
+        a, b = _u64(), _u64()
+        self._ck(self.lib.ltm_reproject_twin(self.h, cmap_a.h, cmap_b.h, poses.h, kf_begin, poses.n if kf_end is None else kf_end, alpha,
+                                             C.byref(a), C.byref(b)))
+        return ScanSet(self, a.value), ScanSet(self, b.value)
+
+    def reproject_twin_applicable(self, cmap_a, cmap_b):
+        """ltm_reproject_twin_applicable: True when reproject_twin would look for shared points (two grids of one frame), known without touching the device"""
+        yes = _i()
+        self._ck(self.lib.ltm_reproject_twin_applicable(self.h, cmap_a.h, cmap_b.h, C.byref(yes)))
+        return bool(yes.value)
+
+    def reproject_twin_stats(self, reset=False):
+        """ltm_debug_reproject_twin_stats as a dict: calls, hits (shared points projected once), fallbacks (two plain reprojections), plain_passes,
+        unordered (joins whose shared points did not pair up in order), and last_a / last_b / last_shared, the sizes the last join saw"""
+        v = (_u64 * 8)()
+        self._ck(self.lib.ltm_debug_reproject_twin_stats(self.h, v, 1 if reset else 0))
+        names = ("calls", "hits", "fallbacks", "plain_passes", "unordered", "last_a", "last_b", "last_shared")
+        return {k: int(x) for k, x in zip(names, v)}
 
     def knn_partition(self, target, scans, poses, k, thr, kf_begin=0, kf_end=None):
         co, di = _u64(), _u64()

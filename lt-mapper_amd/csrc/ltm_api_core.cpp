@@ -276,6 +276,8 @@ int ltm_create(const ltm_config* cfg, ltm_ctx** out)
         if (const char* v = getenv("LTM_KNN_STATS")) c->knn_stats_on = atoi(v);
         if (const char* v = getenv("LTM_CLUSTER_CLIQUE")) c->cluster_clique = atoi(v);
         if (const char* v = getenv("LTM_FPFH_LISTS")) c->fpfh_lists = atoi(v);
+        if (const char* v = getenv("LTM_REPROJECT_TWIN")) c->reproject_twin = atoi(v);
+        if (const char* v = getenv("LTM_REPROJECT_TWIN_MIN_SHARED")) { const float f = (float)atof(v); if (f >= 0.0f && f <= 1.0f) c->kopts.reproject_twin_min_shared = f; }
         if (const char* v = getenv("LTM_CULL_SELFCHECK")) c->cull_selfcheck = atoi(v);
         if (const char* v = getenv("LTM_CULL_EPS_SCALE")) c->cull_eps_scale = (float)atof(v);
         if (const char* v = getenv("LTM_CULL_EPS_FLOOR")) c->cull_eps_floor = (float)atof(v);
@@ -1022,6 +1024,7 @@ int ltm_lane_create(ltm_ctx* parent, ltm_ctx** out)
         c->occlusion_subtile = parent->occlusion_subtile; c->occlusion_stats_on = parent->occlusion_stats_on;
         c->voxel_key_compress = parent->voxel_key_compress; c->voxel_fused_tail = parent->voxel_fused_tail; c->voxel_identity = parent->voxel_identity;
         c->knn_two_phase = parent->knn_two_phase; c->knn_stats_on = parent->knn_stats_on; c->cluster_clique = parent->cluster_clique; c->fpfh_lists = parent->fpfh_lists;
+        c->reproject_twin = parent->reproject_twin;
         c->cull_eps_scale = parent->cull_eps_scale; c->cull_eps_floor = parent->cull_eps_floor;
         c->cull_selfcheck = parent->cull_selfcheck; c->cull_geom_ok = parent->cull_geom_ok;      // shapes the parent has checked already (same device, field of view, extrinsic)
         c->el_fit = parent->el_fit; for (int i = 0; i < 4; ++i) c->el_c[i] = parent->el_c[i]; c->el_fit_err = parent->el_fit_err;

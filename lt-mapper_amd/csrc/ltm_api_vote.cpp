@@ -394,57 +394,220 @@ int ltm_visibility_partition(ltm_ctx* c, ltm_cloud hmap, ltm_scanset hs, ltm_pos
     });
 }
 
+} // extern "C"
+
+namespace ltm_detail {
+
+// The per-keyframe clouds of a reprojection while its keyframe chunks are being made: the chunks' points and the offsets, then one scan set
+struct ReprojectOut {
+    ltm_ctx* c;
+    size_t kf_begin;
+    std::vector<uint64_t> off;
+    struct Piece { float4* d; size_t n; };
+    std::vector<Piece> pieces;
+    ReprojectOut(ltm_ctx* c_, size_t kf_begin_, size_t nk) : c(c_), kf_begin(kf_begin_), off(nk + 1, 0) {}
+    ReprojectOut(const ReprojectOut&) = delete; ReprojectOut& operator=(const ReprojectOut&) = delete;
+    ~ReprojectOut() { for (Piece& pc : pieces) c->pool.free(pc.d); }      // (only what finish() has not handed over)
+    // parseProjectedPoints of the finished images of keyframes [kb, kb + nb) against `map` (utility.cpp:74-89): scan, one round trip for the boundaries, gather
+    void tail(const Cloud& map, const Poses& p, size_t kb, size_t nb, size_t npx, const uint64_t* img, DevBuf& pos, DevBuf& temp, size_t tb, DevBuf& bout)
+    {
+        ProfScope ps(c, "reproject_gather", (double)(nb * npx), (double)(nb * npx) * 12);
+        LTM_HIP(exclusive_scan_img_valid(img, pos.as<uint32_t>(), nb * npx, temp.p, tb, c->stream));
+        // per-keyframe boundaries = scan value at each image start, the total = the scan past the end: one small array, one round trip
+        LTM_HIP(image_bounds(pos.as<uint32_t>(), img, npx, nb, bout.as<uint32_t>(), c->stream));
+        std::vector<uint32_t> b(nb + 1);
+        d2h(c, b.data(), bout.p, (nb + 1) * 4);
+        const size_t total = b[nb];
+        const uint64_t base = off[kb - kf_begin];
+        for (size_t j = 1; j <= nb; ++j) off[kb - kf_begin + j] = base + b[j];
+        pieces.reserve(pieces.size() + 1);
+        float4* d = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(total, 1) * 16));
+        pieces.push_back(Piece{d, total});
+        LTM_HIP(reproject_gather(img, pos.as<uint32_t>(), npx, nb, map.d, p.inv_dev, kb, c->B2L, c->b2l_identity, d, c->stream));
+    }
+    ltm_scanset finish()
+    {
+        float4* d = nullptr;
+        if (pieces.size() == 1) d = pieces[0].d;
+        else {
+            d = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(off.back(), 1) * 16));
+            size_t at = 0;
+            try {
+                for (Piece& pc : pieces) { d2d(c, d + at, pc.d, pc.n * 16); at += pc.n; }
+                sync(c);
+            } catch (...) { c->pool.free(d); throw; }
+            for (Piece& pc : pieces) c->pool.free(pc.d);
+        }
+        pieces.clear();
+        try {
+            return new_scanset(c, d, std::move(off));
+        } catch (...) { c->pool.free(d); throw; }
+    }
+};
+
+struct ReprojectArgs { Geom g; size_t npx, nk; };
+static ReprojectArgs reproject_args(ltm_ctx* c, const Poses& p, size_t kf_begin, size_t kf_end, float alpha)
+{
+    LTM_REQUIRE(kf_begin <= kf_end && kf_end <= p.n, "keyframe range out of bounds");
+    ReprojectArgs a;
+    a.g = geom_for(c, alpha);
+    LTM_REQUIRE(a.g.rows > 0 && a.g.cols > 0, "empty range image");
+    a.npx = (size_t)a.g.rows * a.g.cols;
+    a.nk = kf_end - kf_begin;
+    return a;
+}
+
+static ltm_scanset reproject_plain(ltm_ctx* c, const Cloud& map, const Poses& p, size_t kf_begin, size_t kf_end, float alpha)
+{
+    const ReprojectArgs a = reproject_args(c, p, kf_begin, kf_end, alpha);
+    LTM_REQUIRE(map.n < 0xffffffffull, "map too large for 32-bit point indices");
+    const size_t npx = a.npx;
+    ReprojectOut ro(c, kf_begin, a.nk);
+    if (a.nk && map.n) {
+        const size_t KB = std::min(c->kf_batch, a.nk);
+        DevBuf img(c, KB * npx * 8), pos(c, KB * npx * 4);
+        const size_t tb = scan_temp_bytes(KB * npx);
+        DevBuf temp(c, tb), bout(c, (KB + 1) * 4);
+        for (size_t kb = kf_begin; kb < kf_end; kb += KB) {
+            const size_t nb = std::min(KB, kf_end - kb);
+            LTM_HIP(fill_u64(img.as<uint64_t>(), (uint64_t)kNoPointBits << 32, nb * npx, c->stream));
+            {
+                ProfScope ps(c, "reproject_map", (double)map.n * nb, (double)nb * (16.0 * map.n + 8.0 * npx), 16.0 * map.n + (double)nb * 8.0 * npx);
+                exact_map_images(c, map, p, kb, nb, a.g, img.as<uint64_t>());
+            }
+            ro.tail(map, p, kb, nb, npx, img.as<uint64_t>(), pos, temp, tb, bout);
+        }
+    }
+    return ro.finish();
+}
+
+// What two grids of one octree frame share (k_twin_join and its neighbours, ltm_k_voxel.hip): the compacted shared cloud, its index tables into A and B,
+// and the indices of the points each map has alone.  ok: the shared points pair up in order, which is what makes relabelling exact.
+struct TwinJoin {
+    bool ok = false;
+    size_t n_shared = 0, n_a_only = 0, n_b_only = 0;
+    std::unique_ptr<DevBuf> shared, s2a, s2b, a_only, b_only;
+};
+// what the host knows without touching the device: the switch is on and both clouds are grids of one frame and leaf
+static bool twin_applicable(const ltm_ctx* c, const Cloud& A, const Cloud& B)
+{
+    return c->reproject_twin != 0 && A.n && B.n && A.vf_ok && B.vf_ok && A.vleaf == B.vleaf && same_frame(A.vf, B.vf);
+}
+static TwinJoin twin_join_clouds(ltm_ctx* c, const Cloud& A, const Cloud& B, float min_shared)
+{
+    TwinJoin j;
+    const OctreeFrame& f = A.vf;
+    DevBuf codes_b(c, B.n * 8), flag_a(c, A.n), flag_b(c, B.n), match(c, A.n * 4), pos_a(c, A.n * 4), pos_b(c, B.n * 4), counts(c, 12);
+    LTM_HIP(octree_codes(B.d, B.n, f, codes_b.as<uint64_t>(), c->stream));
+    LTM_HIP(hipMemsetAsync(flag_b.p, 0, B.n, c->stream));
+    LTM_HIP(hipMemsetAsync(counts.p, 0, 12, c->stream));
+    LTM_HIP(twin_join(A.d, A.n, B.d, codes_b.as<uint64_t>(), B.n, f, flag_a.as<uint8_t>(), match.as<uint32_t>(), flag_b.as<uint8_t>(), c->stream));
+    scan_flags(c, flag_a.as<uint8_t>(), A.n, pos_a);
+    scan_flags(c, flag_b.as<uint8_t>(), B.n, pos_b);
+    LTM_HIP(twin_join_check(flag_a.as<uint8_t>(), pos_a.as<uint32_t>(), match.as<uint32_t>(), A.n, flag_b.as<uint8_t>(), pos_b.as<uint32_t>(), B.n,
+                            counts.as<uint32_t>(), c->stream));
+    uint32_t n3[3] = {0, 0, 0};
+    d2h(c, n3, counts.p, 12);      // the one round trip of the join
+    j.n_shared = n3[0]; j.n_a_only = A.n - n3[0]; j.n_b_only = B.n - n3[1];
+    j.ok = n3[0] == n3[1] && n3[2] == 0;
+    if (!j.ok || (double)j.n_shared < (double)min_shared * (double)std::max(A.n, B.n) || j.n_shared == 0) return j;
+    j.shared.reset(new DevBuf(c, j.n_shared * 16));
+    j.s2a.reset(new DevBuf(c, j.n_shared * 4)); j.s2b.reset(new DevBuf(c, j.n_shared * 4));
+    j.a_only.reset(new DevBuf(c, std::max<size_t>(j.n_a_only, 1) * 4)); j.b_only.reset(new DevBuf(c, std::max<size_t>(j.n_b_only, 1) * 4));
+    LTM_HIP(twin_tables(A.d, flag_a.as<uint8_t>(), pos_a.as<uint32_t>(), A.n, j.shared->as<float4>(), j.s2a->as<uint32_t>(), j.a_only->as<uint32_t>(), c->stream));
+    LTM_HIP(twin_tables(B.d, flag_b.as<uint8_t>(), pos_b.as<uint32_t>(), B.n, nullptr, j.s2b->as<uint32_t>(), j.b_only->as<uint32_t>(), c->stream));
+    return j;
+}
+
+} // namespace ltm_detail
+
+extern "C" {
+
 int ltm_reproject(ltm_ctx* c, ltm_cloud hmap, ltm_poses hp, size_t kf_begin, size_t kf_end, float alpha, ltm_scanset* out)
 {
     return guarded(c, [&] {
         LTM_REQUIRE(out, "null argument");
         const Cloud map = get_cloud(c, hmap);
+        *out = reproject_plain(c, map, get_poses(c, hp), kf_begin, kf_end, alpha);
+    });
+}
+
+int ltm_reproject_twin(ltm_ctx* c, ltm_cloud hmap_a, ltm_cloud hmap_b, ltm_poses hp, size_t kf_begin, size_t kf_end, float alpha, ltm_scanset* out_a,
+                       ltm_scanset* out_b)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(out_a && out_b, "null argument");
+        const Cloud A = get_cloud(c, hmap_a), B = get_cloud(c, hmap_b);
         const Poses& p = get_poses(c, hp);
-        LTM_REQUIRE(kf_begin <= kf_end && kf_end <= p.n, "keyframe range out of bounds");
-        LTM_REQUIRE(map.n < 0xffffffffull, "map too large for 32-bit point indices");
-        const Geom g = geom_for(c, alpha);
-        LTM_REQUIRE(g.rows > 0 && g.cols > 0, "empty range image");
-        const size_t npx = (size_t)g.rows * g.cols;
-        const size_t nk = kf_end - kf_begin;
-        std::vector<uint64_t> off(nk + 1, 0);
-        struct Piece { float4* d; size_t n; };
-        std::vector<Piece> pieces;
-        if (nk && map.n) {
-            const size_t KB = std::min(c->kf_batch, nk);
-            DevBuf img(c, KB * npx * 8), pos(c, KB * npx * 4);
-            const size_t tb = scan_temp_bytes(KB * npx);
-            DevBuf temp(c, tb), bout(c, (KB + 1) * 4);
-            for (size_t kb = kf_begin; kb < kf_end; kb += KB) {
-                const size_t nb = std::min(KB, kf_end - kb);
-                LTM_HIP(fill_u64(img.as<uint64_t>(), (uint64_t)kNoPointBits << 32, nb * npx, c->stream));
-                {
-                    ProfScope ps(c, "reproject_map", (double)map.n * nb, (double)nb * (16.0 * map.n + 8.0 * npx), 16.0 * map.n + (double)nb * 8.0 * npx);
-                    exact_map_images(c, map, p, kb, nb, g, img.as<uint64_t>());
-                }
-                ProfScope ps(c, "reproject_gather", (double)(nb * npx), (double)(nb * npx) * 12);
-                LTM_HIP(exclusive_scan_img_valid(img.as<uint64_t>(), pos.as<uint32_t>(), nb * npx, temp.p, tb, c->stream));
-                // per-keyframe boundaries = scan value at each image start, the total = the scan past the end: one small array, one round trip
-                LTM_HIP(image_bounds(pos.as<uint32_t>(), img.as<uint64_t>(), npx, nb, bout.as<uint32_t>(), c->stream));
-                std::vector<uint32_t> b(nb + 1);
-                d2h(c, b.data(), bout.p, (nb + 1) * 4);
-                const size_t total = b[nb];
-                const uint64_t base = off[kb - kf_begin];
-                for (size_t j = 1; j <= nb; ++j) off[kb - kf_begin + j] = base + b[j];
-                float4* d = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(total, 1) * 16));
-                LTM_HIP(reproject_gather(img.as<uint64_t>(), pos.as<uint32_t>(), npx, nb, map.d, p.inv_dev, kb, c->B2L, c->b2l_identity, d, c->stream));
-                pieces.push_back(Piece{d, total});
+        const ReprojectArgs a = reproject_args(c, p, kf_begin, kf_end, alpha);
+        LTM_REQUIRE(A.n < 0xffffffffull && B.n < 0xffffffffull, "map too large for 32-bit point indices");
+        ++c->twin.calls;
+        // two plain passes: the switch, a cloud without points or without the frame of its grid, two grids of different frames or leaves, nothing to project
+        TwinJoin j;
+        bool twin = a.nk && twin_applicable(c, A, B);
+        if (twin) {
+            j = twin_join_clouds(c, A, B, c->kopts.reproject_twin_min_shared);
+            c->twin.last_a = A.n; c->twin.last_b = B.n; c->twin.last_shared = j.n_shared;
+            if (!j.ok) ++c->twin.unordered;
+            twin = j.shared != nullptr;      // ... the shared points not pairing up in order, or too few of them
+        }
+        if (!twin) {
+            ++c->twin.fallbacks;
+            c->twin.plain_passes += 2;
+            const ltm_scanset sa = reproject_plain(c, A, p, kf_begin, kf_end, alpha);
+            try {
+                *out_b = reproject_plain(c, B, p, kf_begin, kf_end, alpha);
+            } catch (...) { (void)ltm_scanset_free(c, sa); throw; }
+            *out_a = sa;
+            return;
+        }
+        ++c->twin.hits;
+        const size_t npx = a.npx;
+        Cloud S;      // a view of the join's compacted cloud; the exact-image kernel needs no frame
+        S.d = j.shared->as<float4>(); S.n = j.n_shared;
+        ReprojectOut ra(c, kf_begin, a.nk), rb(c, kf_begin, a.nk);
+        const size_t KB = std::min(c->kf_batch, a.nk);
+        DevBuf img_a(c, KB * npx * 8), img_b(c, KB * npx * 8), pos(c, KB * npx * 4);
+        const size_t tb = scan_temp_bytes(KB * npx);
+        DevBuf temp(c, tb), bout(c, (KB + 1) * 4);
+        for (size_t kb = kf_begin; kb < kf_end; kb += KB) {
+            const size_t nb = std::min(KB, kf_end - kb);
+            LTM_HIP(fill_u64(img_a.as<uint64_t>(), (uint64_t)kNoPointBits << 32, nb * npx, c->stream));
+            {
+                const double pts = (double)(S.n + j.n_a_only + j.n_b_only);
+                ProfScope ps(c, "reproject_map", pts * nb, (double)nb * (16.0 * pts + 24.0 * npx), 16.0 * pts + (double)nb * 24.0 * npx);
+                exact_map_images(c, S, p, kb, nb, a.g, img_a.as<uint64_t>());
+                LTM_HIP(image_relabel2(img_a.as<uint64_t>(), img_b.as<uint64_t>(), nb * npx, j.s2a->as<uint32_t>(), j.s2b->as<uint32_t>(), c->stream));
+                LTM_HIP(project_points_indexed(A.d, j.a_only->as<uint32_t>(), j.n_a_only, p.inv_dev, kb, nb, c->B2L, c->b2l_identity, a.g, img_a.as<uint64_t>(), c->stream));
+                LTM_HIP(project_points_indexed(B.d, j.b_only->as<uint32_t>(), j.n_b_only, p.inv_dev, kb, nb, c->B2L, c->b2l_identity, a.g, img_b.as<uint64_t>(), c->stream));
             }
+            ra.tail(A, p, kb, nb, npx, img_a.as<uint64_t>(), pos, temp, tb, bout);
+            rb.tail(B, p, kb, nb, npx, img_b.as<uint64_t>(), pos, temp, tb, bout);
         }
-        float4* d = nullptr;
-        if (pieces.size() == 1) d = pieces[0].d;
-        else {
-            d = reinterpret_cast<float4*>(c->pool.alloc(std::max<size_t>(off[nk], 1) * 16));
-            size_t at = 0;
-            for (Piece& pc : pieces) { d2d(c, d + at, pc.d, pc.n * 16); at += pc.n; }
-            sync(c);
-            for (Piece& pc : pieces) c->pool.free(pc.d);
-        }
-        *out = new_scanset(c, d, std::move(off));
+        const ltm_scanset sa = ra.finish();
+        try {
+            *out_b = rb.finish();
+        } catch (...) { (void)ltm_scanset_free(c, sa); throw; }
+        *out_a = sa;
+    });
+}
+
+int ltm_reproject_twin_applicable(ltm_ctx* c, ltm_cloud hmap_a, ltm_cloud hmap_b, int* applicable)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(applicable, "null argument");
+        *applicable = twin_applicable(c, get_cloud(c, hmap_a), get_cloud(c, hmap_b)) ? 1 : 0;
+    });
+}
+
+int ltm_debug_reproject_twin_stats(ltm_ctx* c, uint64_t* stats8, int reset)
+{
+    return guarded(c, [&] {
+        LTM_REQUIRE(stats8, "null argument");
+        const TwinStats& t = c->twin;
+        const uint64_t v[8] = {t.calls, t.hits, t.fallbacks, t.plain_passes, t.unordered, t.last_a, t.last_b, t.last_shared};
+        memcpy(stats8, v, sizeof v);
+        if (reset) c->twin = TwinStats();
     });
 }
 

@@ -264,6 +264,10 @@ struct DevCounters {
     void release() { if (d) (void)hipFree(d); d = nullptr; }    // ltm_destroy
 };
 
+// ltm_reproject_twin: calls, calls that projected the shared points once, calls that ran two plain passes instead and those passes, joins whose shared
+// points did not pair up in order (a fallback too), and the sizes the last join saw
+struct TwinStats { uint64_t calls = 0, hits = 0, fallbacks = 0, plain_passes = 0, unordered = 0, last_a = 0, last_b = 0, last_shared = 0; };
+
 } // namespace ltm_detail
 using namespace ltm_detail;
 
@@ -390,6 +394,8 @@ struct ltm_ctx {
     uint64_t cluster_stats[6] = {0, 0, 0, 0, 0, 0};      // ltm_debug_cluster_stats: pairs tested, edges found, leaves visited, clique leaves, clique early exits, hook retries
     DevCounters plane_stats, outlier_stats, fpfh_stats;
     int fpfh_lists = 1;                         // LTM_FPFH_LISTS=0: ltm_search_fpfh never keeps the neighbour lists of its first pass (A/B switch; the result is the same)
+    int reproject_twin = 1;                     // LTM_REPROJECT_TWIN=0: ltm_reproject_twin is two plain reprojections (A/B switch; the result is the same)
+    TwinStats twin;                             // ltm_debug_reproject_twin_stats
 };
 
 namespace ltm_detail {
@@ -808,6 +814,7 @@ inline Segments sorted_segments(ltm_ctx* c, const uint64_t* keys, size_t n)
 }
 void do_partition(ltm_ctx* c, const Cloud& map, const uint8_t* labels, ltm_cloud* kept, ltm_cloud* flagged);   // ltm_api_vote.cpp
 void bbox_of(ltm_ctx* c, const float4* pts, size_t n, float mn[3], float mx[3]);  // ltm_api_voxel.cpp
+bool same_frame(const OctreeFrame& a, const OctreeFrame& b);                      // ltm_api_voxel.cpp
 void vgs_release_all(ltm_ctx* c);                                                 // ltm_api_voxel.cpp: open ltm_voxel_grid_scanset tickets, at ltm_destroy
 int voxel_grid_scanset_ordered(ltm_ctx* c, ltm_scanset in, float leaf, int order, ltm_scanset* out);   // ltm_api_voxel.cpp: ltm_voxel_grid_scanset with the order as an argument (1 PCL, 0 input)
 void search_view(ltm_ctx* c, struct ltm_search* s, SearchTree* tree, SearchFrame* frame);   // ltm_api_search.cpp: tree and frame of an index OF THIS CONTEXT (throws otherwise)

@@ -1779,6 +1779,59 @@ hipError_t single_range_image(const float4* pts, size_t n, const HostMat34* T1, 
     return hipGetLastError();
 }
 
+// ---- the two small passes of ltm_reproject_twin around one exact-image launch over the points that two maps share
+// img_a holds the image of the shared cloud S (words carry S indices).  Every pixel with a point gets its index replaced through the two tables: in place
+// for map A, into img_b for map B.  Both tables are strictly increasing, so the minimum over S is the same point under any of the three labellings.  The
+// empty word (no point has written the pixel) stays as it is.
+__global__ void __launch_bounds__(kBlock)
+k_image_relabel2(uint64_t* __restrict__ img_a, uint64_t* __restrict__ img_b, size_t n, const uint32_t* __restrict__ s2a, const uint32_t* __restrict__ s2b)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t v = img_a[i];
+    if (v == ((uint64_t)kNoPointBits << 32)) { img_b[i] = v; return; }
+    const uint32_t s = (uint32_t)v;
+    const uint64_t r = v & 0xffffffff00000000ull;
+    img_a[i] = r | s2a[s];
+    img_b[i] = r | s2b[s];
+}
+hipError_t image_relabel2(uint64_t* img_a, uint64_t* img_b, size_t n, const uint32_t* s2a, const uint32_t* s2b, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_image_relabel2<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(img_a, img_b, n, s2a, s2b);
+    return hipGetLastError();
+}
+// The listed points of a map into the images of keyframes [kb, kb + gridDim.y): k_map_rimg's arithmetic and word (the point's own map index), one global
+// minimum per (point, keyframe).  For the few points of a map that its twin does not share.
+template <bool B2L_IDENTITY>
+__global__ void __launch_bounds__(kBlock)
+k_project_points_indexed(const float4* __restrict__ map, const uint32_t* __restrict__ list, size_t n_list, const double* __restrict__ inv_poses, size_t kb,
+                         HostMat34 b2l_h, ProjLaunch pl, uint64_t* __restrict__ img)
+{
+    const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_list) return;
+    const uint32_t i = list[j];
+    const size_t kf = kb + blockIdx.y;
+    const Mat34 Tinv = load_mat(inv_poses + 12 * kf);
+    const RimgGeom& g = pl.g;
+    const float4 p4 = map[i];
+    float3 p = xform(Tinv, make_float3(p4.x, p4.y, p4.z));
+    if (B2L_IDENTITY) p = xform_identity(p); else p = xform(to_dev(b2l_h), p);
+    const Sph s = cart2sph(p.x, p.y, p.z);
+    const int px = pixel_index(g, s.az, s.el);
+    img_min_u64(img + (size_t)blockIdx.y * (size_t)pl.npx + px, ((uint64_t)f2u(s.r) << 32) | (uint64_t)i);
+}
+hipError_t project_points_indexed(const float4* map, const uint32_t* list, size_t n_list, const double* inv_poses_dev, size_t kb, size_t nb, HostMat34 b2l,
+                                  int b2l_identity, Geom g, uint64_t* map_img, hipStream_t s)
+{
+    if (!n_list || !nb) return hipSuccess;
+    const ProjLaunch pl = make_proj_launch(g, b2l, b2l_identity, n_list);
+    dim3 grid(grid_for(n_list), (unsigned)nb);
+    if (b2l_identity) k_project_points_indexed<true><<<grid, dim3(kBlock), 0, s>>>(map, list, n_list, inv_poses_dev, kb, b2l, pl, map_img);
+    else k_project_points_indexed<false><<<grid, dim3(kBlock), 0, s>>>(map, list, n_list, inv_poses_dev, kb, b2l, pl, map_img);
+    return hipGetLastError();
+}
+
 __global__ void k_decode_image(const uint64_t* img, size_t npx, float* rimg, int32_t* ptidx)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -494,4 +494,96 @@ hipError_t voxel_centroids(const float4* pts, const uint32_t* sorted_idx, const 
     return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------- join of two grids of one frame (ltm_reproject_twin)
+// Two clouds that came out of voxel grids under the SAME octree frame hold one centroid per voxel in Morton order.  S = the points that are bit-identical
+// (all four floats) in both.  The join finds them by the points' codes under the frame: per point of A a binary search in B's codes, then the bit compare.
+// Nothing below RELIES on the order of the codes: a point whose search goes astray in a stretch of B that is not sorted simply counts as not shared, and
+// twin_join_check then proves what the caller needs -- the k-th shared point of A is the k-th shared point of B -- from the two scans.
+__global__ void __launch_bounds__(kBlock)
+k_octree_codes(const float4* __restrict__ pts, size_t n, OctreeFrame f, uint64_t* __restrict__ codes)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) codes[i] = octree_code(pts[i], f);
+}
+hipError_t octree_codes(const float4* pts, size_t n, OctreeFrame f, uint64_t* codes, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_octree_codes<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(pts, n, f, codes);
+    return hipGetLastError();
+}
+// flag_a[i] = 1 and match[i] = j iff B[j] has A[i]'s code and A[i]'s bits (-0.0 and +0.0, and NaNs of different payloads, are different points);
+// flag_b[j] = 1 for every j that was matched (zeroed by the caller)
+__global__ void __launch_bounds__(kBlock)
+k_twin_join(const float4* __restrict__ a, uint32_t na, const float4* __restrict__ b, const uint64_t* __restrict__ codes_b, uint32_t nb, OctreeFrame f,
+            uint8_t* __restrict__ flag_a, uint32_t* __restrict__ match, uint8_t* __restrict__ flag_b)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= na) return;
+    const float4 p = a[i];
+    const uint64_t code = octree_code(p, f);
+    uint32_t lo = 0, hi = nb;      // first j with codes_b[j] >= code
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (codes_b[mid] < code) lo = mid + 1; else hi = mid;
+    }
+    bool hit = false;
+    if (lo < nb && codes_b[lo] == code) {
+        const float4 q = b[lo];
+        hit = __builtin_bit_cast(uint32_t, p.x) == __builtin_bit_cast(uint32_t, q.x) && __builtin_bit_cast(uint32_t, p.y) == __builtin_bit_cast(uint32_t, q.y) &&
+              __builtin_bit_cast(uint32_t, p.z) == __builtin_bit_cast(uint32_t, q.z) && __builtin_bit_cast(uint32_t, p.w) == __builtin_bit_cast(uint32_t, q.w);
+    }
+    flag_a[i] = hit ? 1 : 0;
+    match[i] = hit ? lo : 0xffffffffu;
+    if (hit) flag_b[lo] = 1;
+}
+hipError_t twin_join(const float4* a, size_t na, const float4* b, const uint64_t* codes_b, size_t nb, OctreeFrame f, uint8_t* flag_a, uint32_t* match,
+                     uint8_t* flag_b, hipStream_t s)
+{
+    if (!na) return hipSuccess;
+    k_twin_join<<<dim3(grid_for(na)), dim3(kBlock), 0, s>>>(a, (uint32_t)na, b, codes_b, (uint32_t)nb, f, flag_a, match, flag_b);
+    return hipGetLastError();
+}
+// counts[0] = shared points of A, counts[1] = matched points of B, counts[2] (zeroed by the caller) = shared points of A whose rank among A's shared points
+// is not the rank of their partner among B's matched points.  counts[0] == counts[1] and counts[2] == 0: the shared points pair up in order.
+__global__ void __launch_bounds__(kBlock)
+k_twin_join_check(const uint8_t* __restrict__ flag_a, const uint32_t* __restrict__ pos_a, const uint32_t* __restrict__ match, uint32_t na,
+                  const uint8_t* __restrict__ flag_b, const uint32_t* __restrict__ pos_b, uint32_t nb, uint32_t* __restrict__ counts)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        counts[0] = pos_a[na - 1] + (flag_a[na - 1] ? 1u : 0u);
+        counts[1] = pos_b[nb - 1] + (flag_b[nb - 1] ? 1u : 0u);
+    }
+    const bool bad = i < na && flag_a[i] && pos_a[i] != pos_b[match[i]];
+    const uint32_t n_bad = ballot_count(bad);
+    if ((threadIdx.x & 63u) == 0u && n_bad) atomicAdd(counts + 2, n_bad);
+}
+hipError_t twin_join_check(const uint8_t* flag_a, const uint32_t* pos_a, const uint32_t* match, size_t na, const uint8_t* flag_b, const uint32_t* pos_b,
+                           size_t nb, uint32_t* counts3, hipStream_t s)
+{
+    if (!na || !nb) return hipMemsetAsync(counts3, 0, 12, s);
+    k_twin_join_check<<<dim3(grid_for(na)), dim3(kBlock), 0, s>>>(flag_a, pos_a, match, (uint32_t)na, flag_b, pos_b, (uint32_t)nb, counts3);
+    return hipGetLastError();
+}
+// The tables of the join from a cloud's flags and their exclusive scan: the shared point of rank s = pos[i] goes to shared[s] with s2own[s] = i (both
+// nullable: B's points are A's), the others' indices to only[i - pos[i]] in ascending order
+__global__ void __launch_bounds__(kBlock)
+k_twin_tables(const float4* __restrict__ pts, const uint8_t* __restrict__ flag, const uint32_t* __restrict__ pos, uint32_t n, float4* __restrict__ shared,
+              uint32_t* __restrict__ s2own, uint32_t* __restrict__ only)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = pos[i];
+    if (flag[i]) {
+        s2own[s] = i;
+        if (shared) shared[s] = pts[i];
+    } else only[i - s] = i;
+}
+hipError_t twin_tables(const float4* pts, const uint8_t* flag, const uint32_t* pos, size_t n, float4* shared, uint32_t* s2own, uint32_t* only, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    k_twin_tables<<<dim3(grid_for(n)), dim3(kBlock), 0, s>>>(pts, flag, pos, (uint32_t)n, shared, s2own, only);
+    return hipGetLastError();
+}
+
 } // namespace ltm

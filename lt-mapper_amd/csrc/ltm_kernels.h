@@ -82,6 +82,7 @@ struct KernelOpts {
     int map_tile_persist = 1;     // LTM_MAP_TILE_PERSIST  0: that kernel's tables (pixel owners, range bounds, minima) are flushed and reset behind every tile of a run (A/B form: 9.06 against 8.55 ms)
     int map_tile_barrier = 0;     // LTM_MAP_TILE_BARRIER  1: a barrier between a tile's phase 1a and 1b in that kernel (A/B form: 8.55 against 8.34 ms per full-map launch)
     int stats_blockmin = 0;      // LTM_STATS_BLOCKMIN  ltm_debug_cull_stats reports the exact-image kernel's survivor counts instead of the vote kernel's
+    float reproject_twin_min_shared = 0.75f;   // LTM_REPROJECT_TWIN_MIN_SHARED  ltm_reproject_twin projects the shared points once when they are at least this share of the larger map (break-even is near 0.5: the twin costs about (shared + both rests) / one map plain passes)
 };
 // transformGlobalMapToLocal + map2RangeImg: map_img[(kf-kb)*npx+px] = min (range_bits<<32 | idx)
 // inv_poses_dev: 12 doubles per keyframe (3x4 row-major).  b2l: 12 doubles, b2l_identity skips the arithmetic.
@@ -130,6 +131,11 @@ hipError_t cull_probe_points(Geom g, size_t n, const HostMat34* pose, float* xyz
 hipError_t single_range_image(const float4* pts, size_t n, const HostMat34* T1, const HostMat34* T2, Geom g,
                               uint64_t* img, hipStream_t s);
 hipError_t decode_image(const uint64_t* img, size_t npx, float* rimg, int32_t* ptidx, hipStream_t s);
+// ltm_reproject_twin: img_a holds the exact image of the shared cloud (S indices); afterwards img_a carries map A's indices (s2a) and img_b map B's (s2b)
+hipError_t image_relabel2(uint64_t* img_a, uint64_t* img_b, size_t n_px_total, const uint32_t* s2a, const uint32_t* s2b, hipStream_t s);
+// ... and the points map[list[0 .. n_list)] into the images of keyframes [kb, kb + nb) with their own map indices (the plain kernel's arithmetic)
+hipError_t project_points_indexed(const float4* map, const uint32_t* list, size_t n_list, const double* inv_poses_dev, size_t kb, size_t nb, HostMat34 b2l,
+                                  int b2l_identity, Geom g, uint64_t* map_img, hipStream_t s);
 // RViz images: diff of a scan image (float bits) and a decoded map image; JET colour mapping of float / int32 images (BGR8)
 hipError_t viz_diff(const uint32_t* scan_bits, const float* map_r, size_t n, int mode, float* out, hipStream_t s);
 hipError_t viz_colormap_f32(const float* src, size_t n, float a, float b, const uint8_t* lut, uint8_t* bgr, hipStream_t s);
@@ -218,6 +224,14 @@ hipError_t compact_pairs(const uint64_t* keys, const uint32_t* idx, const uint8_
 hipError_t segment_starts(const uint8_t* heads, const uint32_t* pos, size_t n, uint32_t* starts, hipStream_t s);
 hipError_t voxel_centroids(const float4* pts, const uint32_t* sorted_idx, const uint32_t* starts, size_t n_vox, size_t n,
                            float4* out, hipStream_t s);
+// join of two grids of one frame (ltm_reproject_twin; see ltm_k_voxel.hip): codes of a cloud, the match of A's points in B (flag_b zeroed by the caller),
+// the check of the pairing after both flag arrays were scanned (counts3 zeroed by the caller: shared in A, matched in B, out-of-order pairs), the tables
+hipError_t octree_codes(const float4* pts, size_t n, OctreeFrame f, uint64_t* codes, hipStream_t s);
+hipError_t twin_join(const float4* a, size_t na, const float4* b, const uint64_t* codes_b, size_t nb, OctreeFrame f, uint8_t* flag_a, uint32_t* match,
+                     uint8_t* flag_b, hipStream_t s);
+hipError_t twin_join_check(const uint8_t* flag_a, const uint32_t* pos_a, const uint32_t* match, size_t na, const uint8_t* flag_b, const uint32_t* pos_b,
+                           size_t nb, uint32_t* counts3, hipStream_t s);
+hipError_t twin_tables(const float4* pts, const uint8_t* flag, const uint32_t* pos, size_t n, float4* shared, uint32_t* s2own, uint32_t* only, hipStream_t s);
 
 // ---- kNN ----
 struct KnnGrid { double ox, oy, oz, inv_cell; long long nx, ny, nz; };

@@ -214,6 +214,10 @@ class ShardedOps:
         kb, ke = self._range(poses)
         return LazyScans(self, self.ops.reproject_range(cmap, poses, alpha, kb, ke), kb, ke, self.ops.n_keyframes(poses))
 
+    def reproject_twin(self, cmap_a, cmap_b, poses, alpha):
+        # the sharded path keeps two plain reprojections of this rank's keyframes: the same scan sets as ltm_reproject_twin, which one GPU uses
+        return self.reproject(cmap_a, poses, alpha), self.reproject(cmap_b, poses, alpha)
+
     def knn_partition(self, target, scans, poses, k, thr):
         n = self.ops.n_keyframes(poses)
         if isinstance(scans, LazyScans):
@@ -348,6 +352,13 @@ class CommMeter:
         return self.ops.vote_partition(cmap, scans, poses, alpha, thr, mode)
 
     def reproject(self, cmap, poses, alpha): return self._mark(self.ops.reproject(cmap, poses, alpha))
+
+    def reproject_twin(self, cmap_a, cmap_b, poses, alpha):
+        twin = getattr(self.ops, "reproject_twin", None)      # (ops without it, the CPU oracle's: two plain calls)
+        if twin is None:
+            return self.reproject(cmap_a, poses, alpha), self.reproject(cmap_b, poses, alpha)
+        a, b = twin(cmap_a, cmap_b, poses, alpha)
+        return self._mark(a), self._mark(b)
 
     def knn_partition(self, target, scans, poses, k, thr):
         co, di = self.ops.knn_partition(target, scans, poses, k, thr)

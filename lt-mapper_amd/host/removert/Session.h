@@ -141,7 +141,9 @@ public:
     void mergeScansWithinGlobalCoord(void);                                                        // :186-202
 
     void parseStaticScansViaProjection(void);
-    void parseUpdatedStaticScansViaProjection(void);
+    void parseUpdatedStaticScansViaProjection(void);                                               // the updated map and its strong twin (ltm_reproject_twin)
+    bool updatedTwinApplicable(void) const;                                                        // the two are grids of one frame: the call above shares work
+    void parseUpdatedOnlyStaticScansViaProjection(void);                                           // else, with two lanes: one map each
     void parseUpdatedStrongStaticScansViaProjection(void);
     void parsePDScansViaProjection(void);
     void parseStrongPDScansViaProjection(void);

@@ -521,8 +521,7 @@ void Removerter::updateScansScanwise(Session& _sess) { _sess.updateScansScanwise
 void Removerter::parseUpdatedStaticScansViaProjection() { parseUpdatedStaticScansViaProjection(central_sess_); }
 void Removerter::parseUpdatedStaticScansViaProjection(Session& _sess)
 {
-    _sess.parseUpdatedStaticScansViaProjection();
-    _sess.parseUpdatedStrongStaticScansViaProjection();
+    _sess.parseUpdatedStaticScansViaProjection();      // both maps
     LTM_INFO(" parse updated scans via projection: " << _sess.sess_type_);
 }
 void Removerter::parseLDScansViaProjection() { parseLDScansViaProjection(central_sess_); }
@@ -1018,11 +1017,17 @@ void Removerter::runStagesTwoLanes(bool write_outputs)
     if (!C.map_global_nd_strong_) { ltm_cloud h = 0; PointType none{}; ltmCheck(M.ctx, ltm_cloud_upload(M.ctx, &none, 0, 16, &h), "ltm_cloud_upload"); C.map_global_nd_strong_ = C.wrap(h); }
     Cl.map_global_pd_strong_ = lendCloud(C.map_global_pd_strong_, LD);
     Cl.map_global_nd_strong_ = lendCloud(C.map_global_nd_strong_, LD);
-    Cl.map_global_updated_strong_ = lendCloud(C.map_global_updated_strong_, LD);
+    // the updated map and its strong twin in one call on the main lane where they are grids of one frame (what they share is projected once); where they
+    // are not, that call would be two plain passes and the strong map goes to the lane as before
+    const bool twin = C.updatedTwinApplicable();
+    if (!twin) Cl.map_global_updated_strong_ = lendCloud(C.map_global_updated_strong_, LD);
     const bool early = write_outputs && gpu_async_io_;
     forkLanes(M.ctx, LD.ctx,
         [&] {
-            C.parseUpdatedStaticScansViaProjection();
+            if (twin) {
+                C.parseUpdatedStaticScansViaProjection();
+                if (early) saveScans(C, C.keyframe_scans_updated_strong_, updated_strong_scans_save_dir_, false);
+            } else C.parseUpdatedOnlyStaticScansViaProjection();
             C.parsePDScansViaProjection();
             if (early) savePDScans(C);
             C.parseWeakNDScansViaProjection();
@@ -1033,8 +1038,10 @@ void Removerter::runStagesTwoLanes(bool write_outputs)
             if (early) L.saveStrongPDScans(Cl);
             Cl.parseStrongNDScansViaProjection();
             if (early) L.saveStrongNDScans(Cl);
-            Cl.parseUpdatedStrongStaticScansViaProjection();
-            if (early) L.saveScans(Cl, Cl.keyframe_scans_updated_strong_, L.updated_strong_scans_save_dir_, false);
+            if (!twin) {
+                Cl.parseUpdatedStrongStaticScansViaProjection();
+                if (early) L.saveScans(Cl, Cl.keyframe_scans_updated_strong_, L.updated_strong_scans_save_dir_, false);
+            }
         });
     lap("stage C (Step 3)");
     LTM_INFO(" parse updated scans via projection: " << C.sess_type_);
@@ -1042,7 +1049,7 @@ void Removerter::runStagesTwoLanes(bool write_outputs)
     Cl.map_global_pd_strong_.reset(); Cl.map_global_nd_strong_.reset(); Cl.map_global_updated_strong_.reset();
     C.keyframe_scans_strong_pd_ = giveScans(Cl.keyframe_scans_strong_pd_, M);
     C.keyframe_scans_strong_nd_ = giveScans(Cl.keyframe_scans_strong_nd_, M);
-    C.keyframe_scans_updated_strong_ = giveScans(Cl.keyframe_scans_updated_strong_, M);
+    if (!twin) C.keyframe_scans_updated_strong_ = giveScans(Cl.keyframe_scans_updated_strong_, M);
     Ql.keyframe_scans_.reset();      // the view of the query session's scans
     if (write_outputs && !gpu_async_io_) { /* the synchronous path writes everything after the stages (run()) */ }
 }

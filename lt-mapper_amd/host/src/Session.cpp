@@ -629,7 +629,23 @@ void Session::parseScansViaProjection(const CloudPtr& _map, ScansPtr& _vec_to_st
     _vec_to_store = wrap_shard(h);
 }
 void Session::parseStaticScansViaProjection(void) { parseScansViaProjection(map_global_curr_, keyframe_scans_static_projected_); }
-void Session::parseUpdatedStaticScansViaProjection(void) { parseScansViaProjection(map_global_updated_, keyframe_scans_updated_); }
+// Removerter.cpp:1551-1562, both maps in one call: they are grids of one frame that differ by the PD sliver, and what they share is projected once
+void Session::parseUpdatedStaticScansViaProjection(void)
+{
+    ltm_scanset h = 0, h_strong = 0;
+    ltmCheck(dev_->ctx, ltm_reproject_twin(dev_->ctx, map_global_updated_->h, map_global_updated_strong_->h, poses_h_, kf_begin_, kf_end_, kReprojectionAlpha, &h, &h_strong),
+             "ltm_reproject_twin");
+    keyframe_scans_updated_ = wrap_shard(h);
+    keyframe_scans_updated_strong_ = wrap_shard(h_strong);
+}
+// ... unless the two maps are not grids of one frame: the call above is two plain passes then, which two lanes rather run side by side
+bool Session::updatedTwinApplicable(void) const
+{
+    int yes = 0;
+    ltmCheck(dev_->ctx, ltm_reproject_twin_applicable(dev_->ctx, map_global_updated_->h, map_global_updated_strong_->h, &yes), "ltm_reproject_twin_applicable");
+    return yes != 0;
+}
+void Session::parseUpdatedOnlyStaticScansViaProjection(void) { parseScansViaProjection(map_global_updated_, keyframe_scans_updated_); }
 void Session::parseUpdatedStrongStaticScansViaProjection(void) { parseScansViaProjection(map_global_updated_strong_, keyframe_scans_updated_strong_); }
 void Session::parsePDScansViaProjection(void) { parseScansViaProjection(map_global_pd_orig_, keyframe_scans_pd_); }
 void Session::parseStrongPDScansViaProjection(void) { parseScansViaProjection(map_global_pd_strong_, keyframe_scans_strong_pd_); }

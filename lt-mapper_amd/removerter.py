@@ -67,6 +67,8 @@ class HipOps:
     def vote_partition(self, cmap, scans, poses, alpha, thr, mode): return self.ctx.visibility_partition(cmap, scans, poses, alpha, thr, mode)
     def prepare_scan_images(self, scans, alphas, thr=-1.0): self.ctx.prepare_vote_images(scans, alphas, thr)
     def reproject(self, cmap, poses, alpha): return self.ctx.reproject(cmap, poses, alpha)
+    def reproject_twin(self, cmap_a, cmap_b, poses, alpha): return self.ctx.reproject_twin(cmap_a, cmap_b, poses, alpha)   # both, shared points projected once
+    def reproject_twin_applicable(self, cmap_a, cmap_b): return self.ctx.reproject_twin_applicable(cmap_a, cmap_b)          # ... if they are grids of one frame
     def knn_partition(self, target, scans, poses, k, thr): return self.ctx.knn_partition(target, scans, poses, k, thr)
     def knn_split(self, target, query, k, thr): return self.ctx.knn_split_cloud(target, query, k, thr)
     def zip_concat(self, a, b, c): return self.ctx.zip_concat(a, b, c)
@@ -430,9 +432,17 @@ class Removerter:
     def parseUpdatedStaticScansViaProjection(self):     # Removerter.cpp:1551-1562
         t0 = time.perf_counter()
         C = self.central_sess_
-        C.keyframe_scans_updated_ = self.ops.reproject(C.map_global_updated_, C.keyframe_poses, self.kReprojectionAlpha)
-        C.keyframe_scans_updated_strong_ = self.ops.reproject(C.map_global_updated_strong_, C.keyframe_poses, self.kReprojectionAlpha)
+        C.keyframe_scans_updated_, C.keyframe_scans_updated_strong_ = self._reprojectTwin(
+            self.ops, C.map_global_updated_, C.map_global_updated_strong_, C.keyframe_poses)
         self._tick("reproject_updated", t0)
+
+    def _reprojectTwin(self, ops, map_a, map_b, poses):
+        """(reproject(map_a), reproject(map_b)) of two grids of one frame that differ by the PD sliver: one projection of what they share
+        (ltm_reproject_twin) where the ops have it, the two plain calls otherwise (the CPU oracle's ops)"""
+        twin = getattr(ops, "reproject_twin", None)
+        if twin is None:
+            return ops.reproject(map_a, poses, self.kReprojectionAlpha), ops.reproject(map_b, poses, self.kReprojectionAlpha)
+        return twin(map_a, map_b, poses, self.kReprojectionAlpha)
 
     def parseLDScansViaProjection(self):                # Removerter.cpp:1564-1577
         t0 = time.perf_counter()
@@ -577,26 +587,35 @@ class Removerter:
         t0 = time.perf_counter()
         self.updateCurrentMap()
         nd_strong = C.map_global_nd_strong_ if C.map_global_nd_strong_ is not None else ops.empty_cloud()
-        views = [M.lend(x, L) for x in (C.map_global_pd_strong_, nd_strong, C.map_global_updated_strong_)]
+        # the updated map and its strong twin in one call on the main lane where they are grids of one frame (ltm_reproject_twin: what they share is projected
+        # once); where they are not -- a PD point outside the other map's box -- the twin would be two plain passes, and the strong map goes to the lane as before
+        applicable = getattr(ops, "reproject_twin_applicable", None)
+        twin = applicable is not None and applicable(C.map_global_updated_, C.map_global_updated_strong_)
+        views = [M.lend(x, L) for x in (C.map_global_pd_strong_, nd_strong) + (() if twin else (C.map_global_updated_strong_,))]
         got = {}
 
-        def main_side():         # Removerter.cpp:1551-1577 (updated, PD, weak ND) + :1540-1549
+        def main_side():         # Removerter.cpp:1551-1577 (updated and, with it, its strong twin; PD, weak ND) + :1540-1549
             a = self.kReprojectionAlpha
-            C.keyframe_scans_updated_ = ops.reproject(C.map_global_updated_, C.keyframe_poses, a)
+            if twin:
+                C.keyframe_scans_updated_, C.keyframe_scans_updated_strong_ = ops.reproject_twin(C.map_global_updated_, C.map_global_updated_strong_, C.keyframe_poses, a)
+            else:
+                C.keyframe_scans_updated_ = ops.reproject(C.map_global_updated_, C.keyframe_poses, a)
             C.keyframe_scans_pd_ = ops.reproject(C.map_global_pd_orig_, C.keyframe_poses, a)
             C.keyframe_scans_weak_nd_ = ops.reproject(C.map_global_nd_weak_, C.keyframe_poses, a)
             merged = ops.zip_concat(C.keyframe_scans_updated_, C.keyframe_scans_weak_nd_, C.keyframe_scans_pd_)
             C.keyframe_scans_updated_ = ops.voxel_scanset(merged, 0.05)
 
-        def lane_side():         # the "strong" halves of :1551-1577
+        def lane_side():         # the small "strong" halves of :1551-1577
             a = self.kReprojectionAlpha
             got["strong_pd"] = lops.reproject(views[0], Cl_poses, a)
             got["strong_nd"] = lops.reproject(views[1], Cl_poses, a)
-            got["updated_strong"] = lops.reproject(views[2], Cl_poses, a)
+            if not twin:
+                got["updated_strong"] = lops.reproject(views[2], Cl_poses, a)
         self._fork(main_side, lane_side)
         del views
         C.keyframe_scans_strong_pd_, C.keyframe_scans_strong_nd_ = to_main(got["strong_pd"]), to_main(got["strong_nd"])
-        C.keyframe_scans_updated_strong_ = to_main(got["updated_strong"])
+        if not twin:
+            C.keyframe_scans_updated_strong_ = to_main(got["updated_strong"])
         self._tick("lanes_step3", t0)
         self.outputs.update(central_map_static=C.map_global_curr_static_, central_map_dynamic=C.map_global_curr_dynamic_,
                             query_map_static=Q.map_global_curr_static_, query_map_dynamic=Q.map_global_curr_dynamic_)
