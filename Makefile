@@ -10,8 +10,8 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fno-slp-vect
 all: hip oracle host
 
 hip: $(PKG)/libltm_hip.so
-# kernels by stage (projection + vote, streaming helpers, voxel grid, kNN, search index, scan context, ICP, loop submaps, normals, clusters, planes, outlier filters, FPFH descriptors), one translation unit each, then the C ABI
-KOBJ = $(PKG)/csrc/ltm_k_projection.o $(PKG)/csrc/ltm_k_stream.o $(PKG)/csrc/ltm_k_voxel.o $(PKG)/csrc/ltm_k_knn.o $(PKG)/csrc/ltm_k_search.o $(PKG)/csrc/ltm_k_scancontext.o $(PKG)/csrc/ltm_k_icp.o $(PKG)/csrc/ltm_k_submap.o $(PKG)/csrc/ltm_k_normals.o $(PKG)/csrc/ltm_k_cluster.o $(PKG)/csrc/ltm_k_plane.o $(PKG)/csrc/ltm_k_outlier.o $(PKG)/csrc/ltm_k_fpfh.o
+# kernels by stage (projection + vote, streaming helpers, voxel grid, kNN, search index, scan context, ICP, loop submaps, normals, clusters, planes, outlier filters, FPFH descriptors, FPFH matches), one translation unit each, then the C ABI
+KOBJ = $(PKG)/csrc/ltm_k_projection.o $(PKG)/csrc/ltm_k_stream.o $(PKG)/csrc/ltm_k_voxel.o $(PKG)/csrc/ltm_k_knn.o $(PKG)/csrc/ltm_k_search.o $(PKG)/csrc/ltm_k_scancontext.o $(PKG)/csrc/ltm_k_icp.o $(PKG)/csrc/ltm_k_submap.o $(PKG)/csrc/ltm_k_normals.o $(PKG)/csrc/ltm_k_cluster.o $(PKG)/csrc/ltm_k_plane.o $(PKG)/csrc/ltm_k_outlier.o $(PKG)/csrc/ltm_k_fpfh.o $(PKG)/csrc/ltm_k_sac.o
 $(PKG)/csrc/ltm_k_%.o: $(PKG)/csrc/ltm_k_%.hip $(PKG)/csrc/ltm_kernels_common.h $(PKG)/csrc/ltm_kernels.h $(PKG)/csrc/ltm_device_math.h $(PKG)/csrc/ltm_device_prims.h $(PKG)/csrc/ltm_search_walk.h $(PKG)/csrc/ltm_box_bound.h $(PKG)/csrc/ltm_knn_list.h $(PKG)/csrc/ltm_block_table.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(PKG)/csrc/ltm_k_cluster.o: $(PKG)/csrc/ltm_unionfind.h
@@ -19,7 +19,7 @@ $(PKG)/csrc/ltm_k_cluster.o: $(PKG)/csrc/ltm_unionfind.h
 $(PKG)/csrc/ltm_k_fpfh.o $(PKG)/csrc/ltm_api_fpfh.o: $(PKG)/csrc/ltm_fpfh_bins.h
 # the smallest principal axis from moments (covariance, cyclic Jacobi, canonical sign): one copy for normals and the plane refinement
 $(PKG)/csrc/ltm_k_normals.o $(PKG)/csrc/ltm_k_plane.o: $(PKG)/csrc/ltm_covariance.h
-AOBJ = $(PKG)/csrc/ltm_api_core.o $(PKG)/csrc/ltm_api_vote.o $(PKG)/csrc/ltm_api_voxel.o $(PKG)/csrc/ltm_api_knn.o $(PKG)/csrc/ltm_api_search.o $(PKG)/csrc/ltm_api_scancontext.o $(PKG)/csrc/ltm_api_icp.o $(PKG)/csrc/ltm_api_submap.o $(PKG)/csrc/ltm_api_cluster.o $(PKG)/csrc/ltm_api_plane.o $(PKG)/csrc/ltm_api_outlier.o $(PKG)/csrc/ltm_api_fpfh.o
+AOBJ = $(PKG)/csrc/ltm_api_core.o $(PKG)/csrc/ltm_api_vote.o $(PKG)/csrc/ltm_api_voxel.o $(PKG)/csrc/ltm_api_knn.o $(PKG)/csrc/ltm_api_search.o $(PKG)/csrc/ltm_api_scancontext.o $(PKG)/csrc/ltm_api_icp.o $(PKG)/csrc/ltm_api_submap.o $(PKG)/csrc/ltm_api_cluster.o $(PKG)/csrc/ltm_api_plane.o $(PKG)/csrc/ltm_api_outlier.o $(PKG)/csrc/ltm_api_fpfh.o $(PKG)/csrc/ltm_api_sac.o
 $(PKG)/csrc/ltm_api_%.o: $(PKG)/csrc/ltm_api_%.cpp $(PKG)/csrc/ltm_internal.h $(PKG)/csrc/ltm_scan_cache.h $(PKG)/csrc/ltm_kernels.h $(PKG)/csrc/ltm_knn_list.h $(PKG)/csrc/ltm_block_table.h $(PKG)/csrc/ltm_device_prims.h $(PKG)/csrc/ltm_pclsort.h include/ltm.h
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 $(PKG)/libltm_hip.so: $(KOBJ) $(AOBJ)

@@ -872,6 +872,119 @@ int  ltm_fpfh_device(ltm_ctx*, ltm_fpfh*, const uint64_t** offsets_dev, const fl
 /* host copies, any pointer may be NULL: per record n_target and n_finite; per position the descriptor and the unpacked counts */
 int  ltm_fpfh_download(ltm_ctx*, ltm_fpfh*, uint32_t* n_target, uint32_t* n_finite, float* desc /* n_points x 33 */, uint8_t* spfh_counts /* n_points x 33, nullable */);
 int  ltm_fpfh_free(ltm_ctx*, ltm_fpfh*);
+/* A descriptor set from rows the caller supplies: n_records records, record r the rows [offsets[r], offsets[r + 1]) of desc_host (offsets[0] = 0, not
+ * decreasing, fewer than 2^31 rows in all), 33 floats per row, copied as they are (NaN and infinite components included).  Its k reads 0, its SPFH words
+ * and counts are zero, n_target of a record is its row count and n_finite the number of its rows without a NaN component; everything else behaves as for
+ * a handle of ltm_search_fpfh.  For matching any 33-float descriptor (below).  A NULL pointer or offsets outside the rule: LTM_E_INVALID, *out = NULL. */
+int  ltm_fpfh_upload(ltm_ctx*, size_t n_records, const uint64_t* offsets /* n_records + 1 */, const float* desc_host /* rows x 33 */, ltm_fpfh** out);
+
+/* ------------------------------------------------------------ fpfh matches ---- */
+/* Feature-space correspondences between records of descriptor sets: for every row of a SOURCE record its kc nearest rows of a TARGET record, the search that
+ * pcl::SampleConsensusPrerejective (setSourceFeatures, setTargetFeatures, setCorrespondenceRandomness) runs over its FPFH rows and the first half of an
+ * initial alignment from descriptors.  The reference does not call it and PCL is not available to compare against.  tools/sac_numpy.py restates this text
+ * in numpy and the tests compare against that: target rows for equality, distances bit for bit.
+ *  A RECORD of the result is one PAIR: pair i matches the rows of record source_rec[i] of source_set against the rows of record target_rec[i] of
+ *   target_set.  The two sets may be the same handle, and a record may serve any number of pairs.  A pair's result is a function of its two records and kc
+ *   alone: it depends neither on the rest of the batch nor on the schedule.  Rows are numbered within their record, 0 .. n - 1, in the record's own order
+ *   (for a set of ltm_search_fpfh: the target's ORIGINAL order).  1 <= kc <= 16.
+ *  DISTANCE of source row s and target row t, in float, no fused multiply-add, bins in order:
+ *    acc = 0;  for b = 0 .. 32:  e = s[b] - t[b];  acc = acc + e * e.
+ *  ELIGIBLE: a target row with a NaN component is not eligible; a source row with a NaN component has no matches.  (Infinite components are not tested:
+ *   their distances are +inf, or NaN where two infinities meet, and a candidate whose distance is NaN is not listed.)
+ *  LIST of a source row without NaN: the kk = min(kc, listable target rows) smallest candidates in ascending order of (distance, target row): ties go to
+ *   the smaller row.  Output per source row: kc slots of (int32 target row, float distance), slots kk .. kc - 1 holding (-1, +inf).
+ *  Output layout: the pairs' source rows one after the other, offsets (n_pairs + 1) saying where each pair's begin; indices and distances are
+ *   n_rows x kc, row-major.
+ *  Domain: a NULL pointer, a handle that is not a descriptor set of this context (a lane's included), a record number outside its set, or kc outside
+ *   1 .. 16 is LTM_E_INVALID before the device is touched, and no handle is returned (*out = NULL).  Empty records and n_pairs = 0 are valid.  All pairs of
+ *   a call together: fewer than 2^31 source rows (LTM_E_UNSUPPORTED beyond).
+ *  DEPARTURE from PCL: PCL searches a FLANN kd-tree over the 33-D rows (approximate beyond its checks, and in its own tie order); here the search is
+ *   exhaustive and therefore exact.
+ * The kernel stages LTM_MATCH_TILE_ROWS target rows at a time (ltm_match_tile_rows() returns it).  The call handles ALL pairs in ONE launch and returns ONE
+ * handle; it reads nothing back from the device (two small tables go up) and returns with the launch queued on the context's stream.  Memory comes from
+ * the context's pool; scratch is back when the call returns, on every error path too; the handle keeps no reference to the descriptor sets (either may be
+ * freed first); ltm_destroy releases open handles. */
+#define LTM_MATCH_TILE_ROWS 128
+#define LTM_MATCH_MAX_KC    16
+typedef struct ltm_matches ltm_matches;
+uint32_t ltm_match_tile_rows(void);                        /* LTM_MATCH_TILE_ROWS; host only */
+int  ltm_fpfh_match(ltm_ctx*, size_t n_pairs, ltm_fpfh* target_set, const uint32_t* target_rec, ltm_fpfh* source_set, const uint32_t* source_rec, int kc,
+                    ltm_matches** out /* one handle, one record per pair */);
+int  ltm_matches_info(ltm_ctx*, ltm_matches*, size_t* n_pairs, size_t* n_rows /* the pairs' source rows, summed */, int* kc);
+/* the set's device arrays, borrowed until ltm_matches_free: pair offsets (uint64, n_pairs + 1: pair i has rows [off[i], off[i + 1])), target rows (int32,
+ * n_rows x kc) and distances (float, n_rows x kc).  Any pointer may be NULL */
+int  ltm_matches_device(ltm_ctx*, ltm_matches*, const uint64_t** offsets_dev, const int32_t** indices_dev, const float** distances_dev);
+/* host copies, any pointer may be NULL: per pair the rows of its source and of its target record; per source row and slot the target row and distance */
+int  ltm_matches_download(ltm_ctx*, ltm_matches*, uint32_t* n_source, uint32_t* n_target, int32_t* indices, float* distances);
+int  ltm_matches_free(ltm_ctx*, ltm_matches*);
+
+/* ------------------------------------------------------- initial alignment ---- */
+/* Sample-consensus initial alignment of loop pairs from their feature matches: pcl::SampleConsensusPrerejective (setMaximumIterations,
+ * setNumberOfSamples(3), setCorrespondenceRandomness, setSimilarityThreshold, setMaxCorrespondenceDistance, setInlierFraction, align), the step that gives
+ * ltm_icp_align* an init16 inside its basin when the prior is poor.  The reference does not call it and PCL is not available to compare against; this is
+ * what this library takes PCL 1.10's computeTransformation to do, with the departures listed below.  tools/sac_numpy.py restates this text in numpy and
+ * the tests compare against that, for equality, the transform bit for bit.
+ *  A RECORD is one pair: targets[i] and sources[i] are search indices (ltm_search_build or ltm_search_build_scanset; an index may serve many pairs) and
+ *   pair i of the match handle holds, for every row of the source, target rows of the target: ROWS are positions of the index's cloud in its ORIGINAL
+ *   order (the rows of ltm_search_fpfh), so the source index has as many target points as the match record has source rows, and the target index as
+ *   many as the record's target had rows.  A record's result is a function of its two indices, its match record and the parameters alone: it depends
+ *   neither on the rest of the batch nor on the schedule, and there are no floating-point atomics.
+ *  DRAWS: hypothesis h (0 <= h < max_iterations) uses mix_j = the hash of "planes" with x = seed + 0x9E3779B9 * (6 h + j + 1), j = 0 .. 5.  Source rows
+ *   s_j = ((uint64)mix_j * n_rows) >> 32, j = 0, 1, 2, over ALL n_rows rows of the source.  Match of row s_j: m_j = ((uint64)mix_{3+j} * kk_j) >> 32 among
+ *   the kk_j filled slots of the row's list, giving the target row t_j.  The hypothesis is INVALID when two source rows coincide, a drawn row's point has
+ *   a non-finite coordinate, a drawn row has no match (kk_j = 0), two matched target rows coincide, or a matched target point is non-finite.  There is no
+ *   redraw.
+ *  PREREJECTION (CorrespondenceRejectorPoly), in double with + - x only: with a_j the source points and b_j the target points as doubles, for the edges
+ *   (0,1), (1,2), (2,0): ls = |a_i - a_k|^2 and lt = |b_i - b_k|^2, each (dx dx + dy dy) + dz dz with d the first point less the second; the hypothesis
+ *   is invalid (and counted in n_prerejected) unless  min(ls, lt) >= (thr thr) max(ls, lt)  on every edge, thr the double similarity_threshold.
+ *  TRANSFORM, in double with + - x / sqrt, each rounded once, no fused multiply-add (the discipline of "fpfh"; cross products as there).  Frame of a
+ *   triangle (a0, a1, a2): u = a1 - a0, e1 = u / sqrt(u.u) (three divisions); n = u x (a2 - a0), e3 = n / sqrt(n.n); e2 = e3 x e1.  The hypothesis is
+ *   invalid if u.u or n.n, on either side, is 0 or not finite.  With f the source's frame and g the target's:  R_rc = (g1_r f1_c + g2_r f2_c) + g3_r f3_c.
+ *   With the centroids c = ((a0 + a1) + a2) / 3.0 per component, cs of the source and ct of the target:  t_r = ct_r - ((R_r0 cs_x + R_r1 cs_y) + R_r2 cs_z).
+ *   So the rotation is exact in the first edge and in the triangle's plane, the translation at the centroids.
+ *  VOTE: the voting points are the finite source points at positions 0, eval_stride, 2 eval_stride, ... of the source index's own order (its finite points
+ *   in the code order of its own frame; among points of equal code the order is the index's own); n_eval = ceil(n_finite / eval_stride).  A voting point
+ *   is transformed as in step 1 of "icp" (double, rounded to float; a query that overflows is skipped) and is an INLIER iff some finite target point has
+ *   float L2_Simple distance d2 to the query with (double)d2 <= inlier_distance inlier_distance.  The count of an invalid hypothesis is 0.
+ *  BEST: the valid hypothesis with the largest count (its CONSENSUS), ties to the smaller h.  found = ((double)consensus >= inlier_fraction (double)n_eval
+ *   and consensus >= 3).  The record: found, best (-1: no valid hypothesis), consensus, n_valid, n_prerejected, n_eval and T (16 doubles, row-major, last
+ *   row 0 0 0 1; all NaN if best = -1).  hyp_counts and hyp_valid are kept per pair, n_pairs x max_iterations, as in "planes".
+ *  Domain: 1 <= max_iterations <= 16384; 0 <= similarity_threshold < 1; inlier_distance finite and > 0; 0 <= inlier_fraction <= 1; eval_stride >= 1.  A
+ *   NULL pointer, a handle of another context (a lane included), n_pairs different from the match handle's number of pairs, an index whose number of
+ *   target points differs from the rows of its match record, or a parameter outside its range (NaN included) is LTM_E_INVALID before the device is
+ *   touched, and no handle is returned (*out = NULL).  Empty indices and n_pairs = 0 are valid.  The distinct indices of a call together: fewer than 2^31
+ *   target points (LTM_E_UNSUPPORTED beyond).
+ *  DEPARTURES from PCL: PCL estimates the transform by the SVD of the three pairs, here it comes from the two frames; PCL draws with rand() and redraws a
+ *   degenerate or prerejected sample, here the draws come from the hash and there is no redraw; PCL ranks by the inliers' mean squared error under the
+ *   inlier-fraction gate, here by the count; PCL does not evaluate a hypothesis it has already beaten, here ALL max_iterations hypotheses are
+ *   evaluated in full; eval_stride is an addition.  The least-squares fit over the winner's inliers is not here: one ltm_icp_align
+ *   iteration started from T with max_corr_dist = inlier_distance is that fit.
+ * The vote kernel gives a workgroup LTM_SAC_BLOCK_POINTS voting points of one pair (ltm_sac_block_points() returns it).  ltm_sac_align handles ALL pairs in
+ * ONE fixed sequence of launches and returns ONE handle; it reads nothing back from the device (small tables go up) and returns with the launches queued
+ * on the context's stream.  Memory comes from the context's pool; scratch is back when the call returns, on every error path too; the handle keeps no
+ * reference to its indices or matches; ltm_destroy releases open handles. */
+#define LTM_SAC_BLOCK_POINTS 1024
+typedef struct ltm_sac ltm_sac;
+typedef struct {
+    uint32_t max_iterations;        /* 1000   setMaximumIterations: hypotheses per pair, all evaluated; 1 .. 16384 */
+    uint32_t seed;                  /* 0      of the draws */
+    double   similarity_threshold;  /* 0.9    setSimilarityThreshold, in [0, 1) */
+    double   inlier_distance;       /* 0 (must be set)  setMaxCorrespondenceDistance [m] */
+    double   inlier_fraction;       /* 0.25   setInlierFraction, in [0, 1] */
+    uint32_t eval_stride;           /* 1      every eval_stride-th finite source point, in the source index's own order, votes */
+} ltm_sac_params;
+void     ltm_sac_default_params(ltm_sac_params*);          /* host only, needs no device; NULL is a no-op */
+uint32_t ltm_sac_block_points(void);                       /* LTM_SAC_BLOCK_POINTS; host only */
+int  ltm_sac_align(ltm_ctx*, size_t n_pairs, ltm_search* const* targets, ltm_search* const* sources, ltm_matches* matches /* pair i of the handle */,
+                   const ltm_sac_params*, ltm_sac** out /* one handle, one record per pair */);
+int  ltm_sac_info(ltm_ctx*, ltm_sac*, size_t* n_pairs, uint32_t* max_iterations);
+/* the set's device arrays, borrowed until ltm_sac_free: hypothesis inlier counts (uint32, n_pairs x max_iterations, 0 where invalid) and valid bytes */
+int  ltm_sac_device(ltm_ctx*, ltm_sac*, const uint32_t** hyp_counts_dev, const uint8_t** hyp_valid_dev);
+/* host copies, any pointer may be NULL: per pair found, best, consensus, n_valid, n_prerejected, n_eval, T16 (n_pairs x 16 doubles: what ltm_icp_align*
+ * takes as init16); hyp_counts and hyp_valid n_pairs x max_iterations */
+int  ltm_sac_download(ltm_ctx*, ltm_sac*, uint8_t* found, int32_t* best, uint32_t* consensus, uint32_t* n_valid, uint32_t* n_prerejected, uint32_t* n_eval,
+                      double* T16, uint32_t* hyp_counts, uint8_t* hyp_valid);
+int  ltm_sac_free(ltm_ctx*, ltm_sac*);
 
 /* ------------------------------------------------------------------- lanes ---- */
 /* The reference runs the stages of Removerter::run() one after the other on one thread; several of them do not depend on each other: the
@@ -1022,6 +1135,9 @@ int ltm_debug_outlier_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
 /* counters of ltm_search_fpfh since the last reset, stats[4]: finite points processed, point pairs whose distance was evaluated (twice as many where the
  * second pass collects the neighbourhoods again), pairs skipped as degenerate, points that took the LDS list form (k > 16).  Counted on the device; this call reads them. */
 int ltm_debug_fpfh_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
+/* counters of ltm_sac_align since the last reset, stats[4]: point-hypothesis inlier tests (voting points x valid hypotheses; a target without a finite point has no valid hypothesis and adds none), hypotheses prerejected, walks
+ * that ended early at their first hit (the inliers found), records.  Counted on the device; this call reads them. */
+int ltm_debug_sac_stats(ltm_ctx*, uint64_t* stats /* 4 */, int reset);
 /* which kernel forms a Scan Context shape gets (host arithmetic only, needs no device; the launch wrappers' own expressions): *scatter_in_lds = 1 if
  * ltm_sc_from_scanset pre-reduces a block's points in LDS (up to 4096 bins), 0 if it goes straight to device memory; *pair_in_lds = 1 if the pair
  * distance of ltm_sc_distance / ltm_sc_detect stages both descriptors in LDS (up to 60 KB with the keys and norms), 0 if it reads them from device

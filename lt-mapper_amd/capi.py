@@ -45,6 +45,12 @@ class PlaneParams(C.Structure):
                 ("eps_angle", C.c_double), ("refine", C.c_int32)]
 
 
+class SacParams(C.Structure):
+    """ltm_sac_params"""
+    _fields_ = [("max_iterations", C.c_uint32), ("seed", C.c_uint32), ("similarity_threshold", C.c_double), ("inlier_distance", C.c_double),
+                ("inlier_fraction", C.c_double), ("eval_stride", C.c_uint32)]
+
+
 class SorParams(C.Structure):
     """ltm_sor_params"""
     _fields_ = [("mean_k", C.c_uint32), ("stddev_mul", C.c_double)]
@@ -227,6 +233,21 @@ SIGNATURES = {
     "ltm_fpfh_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "ltm_fpfh_free": (_i, [_vp, _vp]),
     "ltm_debug_fpfh_stats": (_i, [_vp, _pu64, _i]),
+    "ltm_fpfh_upload": (_i, [_vp, _sz, _vp, _vp, C.POINTER(_vp)]),
+    "ltm_match_tile_rows": (C.c_uint32, []),
+    "ltm_fpfh_match": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)]),
+    "ltm_matches_info": (_i, [_vp, _vp, _psz, _psz, C.POINTER(_i)]),
+    "ltm_matches_device": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_matches_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltm_matches_free": (_i, [_vp, _vp]),
+    "ltm_sac_default_params": (None, [C.POINTER(SacParams)]),
+    "ltm_sac_block_points": (C.c_uint32, []),
+    "ltm_sac_align": (_i, [_vp, _sz, C.POINTER(_vp), C.POINTER(_vp), _vp, C.POINTER(SacParams), C.POINTER(_vp)]),
+    "ltm_sac_info": (_i, [_vp, _vp, _psz, C.POINTER(C.c_uint32)]),
+    "ltm_sac_device": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "ltm_sac_download": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ltm_sac_free": (_i, [_vp, _vp]),
+    "ltm_debug_sac_stats": (_i, [_vp, _pu64, _i]),
     "ltm_debug_pool_live": (_i, [_vp, _pu64, _pu64]),
     "ltm_debug_range_image": (_i, [_vp, _u64, _vp, _vp, _f, _vp, _vp]),
     "ltm_debug_viz_images": (_i, [_vp, _u64, _u64, _u64, _sz, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
@@ -834,6 +855,55 @@ class Context:
         self._ck(self.lib.ltm_search_fpfh(self.h, len(indices), hs, int(k), C.byref(h)))
         return Fpfh(self, h.value)
 
+    def fpfh_from_rows(self, rows, offsets=None):
+        """ltm_fpfh_upload: an Fpfh from the caller's own rows, (n, 33) float32; offsets (n_records + 1, from 0) cut them into records, None = one record.
+        Its k reads 0; for matching any 33-float descriptor"""
+        d = np.ascontiguousarray(rows, dtype=np.float32)
+        if d.ndim != 2 or d.shape[1] != FPFH_SIZE:
+            raise ValueError("rows must be (n, 33)")
+        off = np.array([0, len(d)], np.uint64) if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if len(off) < 1 or int(off[0]) != 0 or int(off[-1]) != len(d) or (off[1:] < off[:-1]).any():
+            raise ValueError("offsets must run from 0 to the number of rows without decreasing")
+        h = _vp()
+        self._ck(self.lib.ltm_fpfh_upload(self.h, len(off) - 1, off.ctypes.data, d.ctypes.data, C.byref(h)))
+        return Fpfh(self, h.value)
+
+    def fpfh_match(self, target_set, source_set, pairs, kc):
+        """ltm_fpfh_match: for every pair (target record, source record) of `pairs` (an (n, 2) integer array) the kc nearest rows of the target record, in
+        descriptor space, of every row of the source record: exhaustive and exact, all pairs in one launch; nothing is read back.  The two sets may be
+        the same Fpfh.  Returns one Matches with one record per pair."""
+        if not isinstance(target_set, Fpfh) or not isinstance(source_set, Fpfh):
+            raise TypeError("fpfh_match takes Fpfh objects (Context.fpfh, Context.fpfh_from_rows)")
+        p = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        if (p < 0).any() or (p >= 2 ** 32).any():
+            raise ValueError("record numbers must be in [0, 2^32)")
+        k = int(kc)
+        if k != kc or not 1 <= k <= MATCH_MAX_KC:
+            raise ValueError("need 1 <= kc <= 16")
+        t, s = np.ascontiguousarray(p[:, 0], dtype=np.uint32), np.ascontiguousarray(p[:, 1], dtype=np.uint32)
+        h = _vp()
+        self._ck(self.lib.ltm_fpfh_match(self.h, len(p), target_set.h, t.ctypes.data if len(p) else None, source_set.h, s.ctypes.data if len(p) else None,
+                                         k, C.byref(h)))
+        return Matches(self, h.value)
+
+    def sac_align(self, pairs, matches, **params):
+        """ltm_sac_align: pcl::SampleConsensusPrerejective over the matches of every pair in one sequence of launches; nothing is read back.  pairs: a
+        sequence of (target SearchIndex, source SearchIndex), pair i belonging to record i of `matches` (Context.fpfh_match with pairs in the same order);
+        params: the fields of ltm_sac_params (inlier_distance must be given).  Returns one SacAlignments; its T is what icp_align takes as init."""
+        p = sac_params(**params)
+        if not isinstance(matches, Matches):
+            raise TypeError("sac_align takes the Matches of Context.fpfh_match")
+        pairs = list(pairs)
+        targets, ht = self._index_handles([t for t, _ in pairs], "sac_align")
+        sources, hs = self._index_handles([s for _, s in pairs], "sac_align")
+        h = _vp()
+        self._ck(self.lib.ltm_sac_align(self.h, len(pairs), ht, hs, matches.h, C.byref(p), C.byref(h)))
+        return SacAlignments(self, h.value)
+
+    def sac_stats(self, reset=False):
+        """ltm_debug_sac_stats: dict of the four counters since the last reset"""
+        return self._stats("ltm_debug_sac_stats", SAC_STATS, reset)
+
     def fpfh_stats(self, reset=False):
         """ltm_debug_fpfh_stats: dict of the four counters since the last reset"""
         return self._stats("ltm_debug_fpfh_stats", FPFH_STATS, reset)
@@ -856,7 +926,8 @@ class Context:
         return ScanSet(self, out.value)
 
     def verify_loops(self, target_scans, source_scans, pairs, target_affines=None, source_affines=None, search_num=25, leaf=0.3,
-                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, method="point", normal_k=_NORMAL_K_OF_METHOD, **icp):
+                     fitness_threshold=0.5, order="pcl", max_batch_points=1 << 26, method="point", normal_k=_NORMAL_K_OF_METHOD, coarse=None, fpfh_k=16,
+                     match_k=4, sac=None, **icp):
         """The body of LTslam::addSCloops' loop (LTslam.cpp:370-416) for all `pairs` = (target key, source key): the target submap (+-search_num
         keyframes) and its search index are made ONCE per distinct target key, the source submap is the source keyframe alone (searchNum = 0), every
         source is aligned to its target by icp_align, and a pair is accepted iff converged and fitness <= fitness_threshold (loopFitnessScoreThreshold,
@@ -867,12 +938,23 @@ class Context:
         indices are built with search_index_batch as well, and the normals of the batch's source and target indices are estimated in ONE call (targets
         first; the viewpoint of a source at its keyframe's translation).
         normal_k, when not given, is the method's own: 10 for "plane", 20 for "gicp" (PCL's k_correspondences_, DeviceICP's default too).
+        coarse="fpfh" gives every pair a start from its descriptors before the ICP: source indices are built as for "gicp", normals (10 neighbours, no
+        viewpoint) and FPFH descriptors (fpfh_k) of the batch's targets and sources are made in one call each, the pairs are matched (match_k lists) and
+        aligned by sac_align (sac: a dict of its parameters, inlier_distance among them), and the chosen ICP method starts from that T; a pair without
+        `found` starts from its given start (init= among **icp, one per pair; identity without one).  coarse=None, the default, is the path without any of this.
         Returns (ICP_RESULT records, accept mask), one entry per pair."""
+        if coarse not in (None, "fpfh"):
+            raise ValueError('coarse must be None or "fpfh"')
+        if coarse and (sac is None or "inlier_distance" not in sac):
+            raise ValueError('coarse="fpfh" needs sac=dict(inlier_distance=...)')
         method = _icp_method(method)
         if method != "point":
             normal_k = normals_k_of(method, normal_k)
         pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
         res = np.zeros(len(pairs), dtype=ICP_RESULT)
+        given = None      # coarse: the caller's own starts (init=, one per pair), kept for the pairs the coarse step does not find
+        if coarse and icp.get("init") is not None:
+            given = np.ascontiguousarray(icp["init"], dtype=np.float64).reshape(len(pairs), 4, 4)
         t_off = target_scans.offsets().astype(np.int64)
         s_off = source_scans.offsets().astype(np.int64)
 
@@ -900,8 +982,11 @@ class Context:
             idx = self.search_index_batch(tsub)
             sidx = []
             try:
-                if method == "gicp":
+                if coarse:
                     sidx = self.search_index_batch(ssub)
+                    starts = self._coarse_starts(idx, sidx, [slot[int(pairs[i, 0])] for i in b], fpfh_k, match_k, sac, None if given is None else given[b])
+                if method == "gicp":
+                    sidx = sidx or self.search_index_batch(ssub)
                     vp = None
                     if target_affines is not None or source_affines is not None:
                         zero = np.zeros(3, np.float32)
@@ -909,20 +994,29 @@ class Context:
                         sa = None if source_affines is None else np.asarray(source_affines, dtype=np.float32).reshape(-1, 3, 4)
                         vp = np.stack([zero if ta is None else ta[k, :, 3] for k in tkeys] + [zero if sa is None else sa[int(pairs[i, 1]), :, 3] for i in b])
                     self.estimate_normals(idx + sidx, normal_k, vp)
-                    res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], sidx[j]) for j, i in enumerate(b)], method=method, **icp)
+                    res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], sidx[j]) for j, i in enumerate(b)], method=method, **(dict(icp, init=starts) if coarse else icp))
                     continue
                 if method == "plane":
                     vp = None
                     if target_affines is not None:
                         vp = np.asarray(target_affines, dtype=np.float32).reshape(-1, 3, 4)[tkeys, :, 3]
                     self.estimate_normals(idx, normal_k, vp)
-                res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], (ssub, j)) for j, i in enumerate(b)], method=method, **icp)
+                res[b] = self.icp_align([(idx[slot[int(pairs[i, 0])]], (ssub, j)) for j, i in enumerate(b)], method=method, **(dict(icp, init=starts) if coarse else icp))
             finally:
                 for x in idx + sidx:
                     x.close()
                 tsub.free()
                 ssub.free()
         return res, (res["converged"] != 0) & (res["fitness"] <= fitness_threshold)
+
+    def _coarse_starts(self, idx, sidx, target_of, fpfh_k, match_k, sac, given):
+        """verify_loops(coarse="fpfh"): (n, 4, 4) starts of the pairs (idx[target_of[j]], sidx[j]): sac_align's T where found, elsewhere the pair's
+        given start (`given`, (n, 4, 4), None = identity)"""
+        self.estimate_normals(idx + sidx, 10)
+        with self.fpfh(idx + sidx, fpfh_k) as f, self.fpfh_match(f, f, [(t, len(idx) + j) for j, t in enumerate(target_of)], match_k) as m, \
+                self.sac_align([(idx[t], sidx[j]) for j, t in enumerate(target_of)], m, **sac) as a:
+            found, T = a.found.astype(bool), a.T
+        return np.where(found[:, None, None], T, np.eye(4)[None] if given is None else given)
 
     # ---- scan context
     def scan_contexts(self, scans, kf_begin=0, kf_end=None, **params):
@@ -1566,6 +1660,147 @@ class Fpfh(_PtrHandle):
         out = np.zeros((n, FPFH_SIZE), np.uint8)
         self.ctx._ck(self.ctx.lib.ltm_fpfh_download(self.ctx.h, self.h, None, None, None, out.ctypes.data))
         return out
+
+
+MATCH_MAX_KC = 16
+
+
+def match_tile_rows():
+    """ltm_match_tile_rows: the target rows the match kernel stages at a time (needs no device)"""
+    return int(load_library().ltm_match_tile_rows())
+
+
+class Matches(_PtrHandle):
+    """ltm_matches: the feature-space correspondences of ltm_fpfh_match, one record per pair (semantics in include/ltm.h, "fpfh matches").  The rows hold
+    the pairs' source rows one after the other; offsets() says where each pair's begin."""
+
+    _free = "ltm_matches_free"
+
+    def info(self):
+        """(pairs, source rows, kc)"""
+        a, b, k = C.c_size_t(), C.c_size_t(), _i()
+        self.ctx._ck(self.ctx.lib.ltm_matches_info(self.ctx.h, self.h, C.byref(a), C.byref(b), C.byref(k)))
+        return a.value, b.value, k.value
+
+    def __len__(self):
+        return self.info()[0]
+
+    kc = property(lambda self: self.info()[2], doc="the kc of the call")
+
+    def _device(self):
+        po, pi, pd = _vp(), _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_matches_device(self.ctx.h, self.h, C.byref(po), C.byref(pi), C.byref(pd)))
+        return po.value, pi.value, pd.value
+
+    def _download(self):
+        if self._host is None:
+            nr = self.info()[0]
+            ns, nt = np.empty(nr, np.uint32), np.empty(nr, np.uint32)
+            self.ctx._ck(self.ctx.lib.ltm_matches_download(self.ctx.h, self.h, ns.ctypes.data, nt.ctypes.data, None, None))
+            self._host = (ns, nt)
+        return self._host
+
+    n_source = property(lambda self: self._download()[0], doc="uint32 [n_pairs]: rows of the pair's source record")
+    n_target = property(lambda self: self._download()[1], doc="uint32 [n_pairs]: rows of the pair's target record")
+
+    def offsets(self):
+        """uint64 [n_pairs + 1]: pair i owns rows [offsets[i], offsets[i + 1])"""
+        return self._out(self._device()[0], self.info()[0] + 1, np.uint64, False)
+
+    def indices(self, as_torch=False):
+        """int32 [n_rows, kc] (a copy): target rows within the pair's target record, ascending by (distance, row); -1 in unused slots"""
+        _, n, k = self.info()
+        return self._out(self._device()[1], n * k, np.int32, as_torch).reshape(n, k)
+
+    def distances(self, as_torch=False):
+        """float32 [n_rows, kc] (a copy): squared descriptor distances; +inf in unused slots"""
+        _, n, k = self.info()
+        return self._out(self._device()[2], n * k, np.float32, as_torch).reshape(n, k)
+
+
+SAC_STATS = ("inlier_tests", "prerejected", "early_hits", "records")
+SAC_MAX_ITERATIONS = 16384
+
+
+def sac_block_points():
+    """ltm_sac_block_points: the voting points a workgroup of the vote kernel takes (needs no device)"""
+    return int(load_library().ltm_sac_block_points())
+
+
+def sac_params(inlier_distance=None, max_iterations=None, seed=None, similarity_threshold=None, inlier_fraction=None, eval_stride=None):
+    """ltm_sac_params from the library's defaults, checked: inlier_distance finite and > 0 (it has no usable default), 1 <= max_iterations <= 16384,
+    0 <= seed < 2^32, similarity_threshold in [0, 1), inlier_fraction in [0, 1], 1 <= eval_stride < 2^32"""
+    p = SacParams()
+    load_library().ltm_sac_default_params(C.byref(p))
+    if inlier_distance is None:
+        raise ValueError("inlier_distance must be given")
+    p.inlier_distance = float(inlier_distance)
+    if not (np.isfinite(p.inlier_distance) and p.inlier_distance > 0.0):
+        raise ValueError("inlier_distance must be finite and > 0")
+    for name, value, lo, hi in (("max_iterations", max_iterations, 1, SAC_MAX_ITERATIONS), ("seed", seed, 0, 2 ** 32 - 1),
+                                ("eval_stride", eval_stride, 1, 2 ** 32 - 1)):
+        if value is not None:
+            if int(value) != value or not lo <= int(value) <= hi:
+                raise ValueError(f"need {lo} <= {name} <= {hi}")
+            setattr(p, name, int(value))
+    if similarity_threshold is not None:
+        p.similarity_threshold = float(similarity_threshold)
+    if inlier_fraction is not None:
+        p.inlier_fraction = float(inlier_fraction)
+    if not 0.0 <= p.similarity_threshold < 1.0:
+        raise ValueError("similarity_threshold must be in [0, 1)")
+    if not 0.0 <= p.inlier_fraction <= 1.0:
+        raise ValueError("inlier_fraction must be in [0, 1]")
+    return p
+
+
+class SacAlignments(_PtrHandle):
+    """ltm_sac: the initial alignments of ltm_sac_align, one record per pair (semantics in include/ltm.h, "initial alignment")"""
+
+    _free = "ltm_sac_free"
+
+    def info(self):
+        """(pairs, max_iterations)"""
+        a, m = C.c_size_t(), C.c_uint32()
+        self.ctx._ck(self.ctx.lib.ltm_sac_info(self.ctx.h, self.h, C.byref(a), C.byref(m)))
+        return a.value, m.value
+
+    def __len__(self):
+        return self.info()[0]
+
+    def _device(self):
+        pc, pv = _vp(), _vp()
+        self.ctx._ck(self.ctx.lib.ltm_sac_device(self.ctx.h, self.h, C.byref(pc), C.byref(pv)))
+        return pc.value, pv.value
+
+    def _download(self):
+        if self._host is None:
+            nr = self.info()[0]
+            found, best = np.empty(nr, np.uint8), np.empty(nr, np.int32)
+            cons, nv, npre, ne = (np.empty(nr, np.uint32) for _ in range(4))
+            T = np.empty((nr, 4, 4), np.float64)
+            self.ctx._ck(self.ctx.lib.ltm_sac_download(self.ctx.h, self.h, found.ctypes.data, best.ctypes.data, cons.ctypes.data, nv.ctypes.data, npre.ctypes.data,
+                                                       ne.ctypes.data, T.ctypes.data, None, None))
+            self._host = (found, best, cons, nv, npre, ne, T)
+        return self._host
+
+    found = property(lambda self: self._download()[0], doc="uint8 [n_pairs]: 1 = the consensus passes the inlier-fraction gate")
+    best = property(lambda self: self._download()[1], doc="int32 [n_pairs]: the best hypothesis, -1 = no valid one")
+    consensus = property(lambda self: self._download()[2], doc="uint32 [n_pairs]: inliers of the best hypothesis")
+    n_valid = property(lambda self: self._download()[3], doc="uint32 [n_pairs]: valid hypotheses")
+    n_prerejected = property(lambda self: self._download()[4], doc="uint32 [n_pairs]: hypotheses the polygon test rejected")
+    n_eval = property(lambda self: self._download()[5], doc="uint32 [n_pairs]: voting points")
+    T = property(lambda self: self._download()[6], doc="float64 [n_pairs, 4, 4]: source -> target of the best hypothesis (NaN: none): the init of icp_align")
+
+    def hypothesis_counts(self):
+        """uint32 [n_pairs, max_iterations]: the inlier count of every hypothesis, 0 where invalid"""
+        nr, m = self.info()
+        return self._out(self._device()[0], nr * m, np.uint32, False).reshape(nr, m)
+
+    def hypothesis_valid(self):
+        """uint8 [n_pairs, max_iterations]"""
+        nr, m = self.info()
+        return self._out(self._device()[1], nr * m, np.uint8, False).reshape(nr, m)
 
 
 

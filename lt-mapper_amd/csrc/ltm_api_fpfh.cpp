@@ -10,7 +10,43 @@ struct ltm_fpfh : IndexRecordSet {            // blocks: offsets, descriptors an
     using IndexRecordSet::IndexRecordSet;
 };
 
+const std::vector<uint64_t>& ltm_detail::fpfh_rows(ltm_ctx* c, ltm_fpfh* h, const float** desc)
+{
+    const ltm_fpfh* s = c->open.fpfh.get(h);
+    *desc = s->desc;
+    return s->bounds;
+}
+
 extern "C" {
+
+int ltm_fpfh_upload(ltm_ctx* c, size_t n_records, const uint64_t* offsets, const float* desc_host, ltm_fpfh** out)
+{
+    if (out) *out = nullptr;
+    return guarded(c, [&] {
+        LTM_REQUIRE(out && offsets, "null argument");
+        LTM_REQUIRE(n_records < 0x7fffffffull / 16, "too many records");
+        LTM_REQUIRE(offsets[0] == 0, "offsets must start at 0");
+        for (size_t r = 0; r < n_records; ++r) LTM_REQUIRE(offsets[r] <= offsets[r + 1], "offsets must not decrease");
+        const uint64_t np = offsets[n_records];
+        LTM_REQUIRE(!np || desc_host, "null argument");
+        if (np >= 0x80000000ull) throw Err{LTM_E_UNSUPPORTED, "a descriptor set must have fewer than 2^31 rows in all"};
+        std::unique_ptr<ltm_fpfh> made(new ltm_fpfh(c, n_records));      // k stays 0: the rows are the caller's
+        made->bounds.assign(offsets, offsets + n_records + 1);
+        for (size_t r = 0; r < n_records; ++r)      // n_finite of an uploaded record: its rows without a NaN component
+            for (uint64_t i = offsets[r]; i < offsets[r + 1]; ++i) {
+                bool nan = false;
+                for (int b = 0; b < kFpfhSize; ++b) nan = nan || std::isnan(desc_host[i * kFpfhSize + b]);
+                made->n_finite[r] += nan ? 0u : 1u;
+            }
+        made->offsets = made->blocks.alloc<uint64_t>(n_records + 1);
+        made->desc = made->blocks.alloc<float>(np * kFpfhSize);
+        made->spfh = made->blocks.alloc<unsigned long long>(np * kFpfhWords);
+        h2d(c, made->offsets, made->bounds.data(), (n_records + 1) * sizeof(uint64_t));
+        h2d(c, made->desc, desc_host, np * kFpfhSize * sizeof(float));
+        if (np) LTM_HIP(hipMemsetAsync(made->spfh, 0, np * kFpfhWords * sizeof(unsigned long long), c->stream));
+        *out = c->open.fpfh.adopt(made);
+    });
+}
 
 int ltm_search_fpfh(ltm_ctx* c, size_t n_idx, ltm_search* const* idx, int k, ltm_fpfh** out)
 {

@@ -204,7 +204,7 @@ struct PinnedBlock { void* p; size_t bytes; bool in_use; };
 struct UploadState { float4* d = nullptr; size_t cap = 0, n = 0; std::vector<uint64_t> off{0}; void* stage[2] = {nullptr, nullptr}; size_t stage_sz[2] = {0, 0}; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy[2] = {false, false}; int next = 0; size_t fill = 0, flushed = 0; };
 
 
-// ---- the pointer handles of the C ABI (ltm_search, ltm_search_result, ltm_sc, ltm_clusters, ltm_planes, ltm_outliers, ltm_fpfh); the rule: DESIGN.md 4.4b
+// ---- the pointer handles of the C ABI (ltm_search, ltm_search_result, ltm_sc, ltm_clusters, ltm_planes, ltm_outliers, ltm_fpfh, ltm_matches, ltm_sac); the rule: DESIGN.md 4.4b
 // A handle holds its device arrays in PoolBlocks (below): a member, or a std::shared_ptr where the handles of one batch share blocks.  Its destructor
 // returns them, so `delete` is the only way a handle's memory goes back and a half-built handle in a std::unique_ptr cleans up after itself.
 // OpenHandles<H>: the handles of ONE type that a context has given out and not got back.  A freed handle, one of another type, of another context or of
@@ -253,9 +253,11 @@ struct OpenLists {
     OpenHandles<ltm_planes> planes{"not a plane set of this context"};
     OpenHandles<ltm_outliers> outliers{"not an outlier set of this context"};
     OpenHandles<ltm_fpfh> fpfh{"not a descriptor set of this context"};
-    void release_all() { search.release_all(); result.release_all(); sc.release_all(); clusters.release_all(); planes.release_all(); outliers.release_all(); fpfh.release_all(); }
+    OpenHandles<ltm_matches> matches{"not a match set of this context"};
+    OpenHandles<ltm_sac> sac{"not an alignment set of this context"};
+    void release_all() { search.release_all(); result.release_all(); sc.release_all(); clusters.release_all(); planes.release_all(); outliers.release_all(); fpfh.release_all(); matches.release_all(); sac.release_all(); }
 };
-// The four device counters of a feature whose entry points read nothing back (ltm_debug_plane_stats, _outlier_stats, _fpfh_stats): outside the pool (they
+// The four device counters of a feature whose entry points read nothing back (ltm_debug_plane_stats, _outlier_stats, _fpfh_stats, _sac_stats): outside the pool (they
 // live as long as the context), made and zeroed on first use
 struct DevCounters {
     unsigned long long* d = nullptr;
@@ -392,7 +394,7 @@ struct ltm_ctx {
     OpenLists open;                             // the pointer handles not freed yet: released by ltm_destroy at the latest
     int cluster_clique = 1;                     // LTM_CLUSTER_CLIQUE=0: no clique leaves in ltm_search_cluster (A/B switch; the result is the same)
     uint64_t cluster_stats[6] = {0, 0, 0, 0, 0, 0};      // ltm_debug_cluster_stats: pairs tested, edges found, leaves visited, clique leaves, clique early exits, hook retries
-    DevCounters plane_stats, outlier_stats, fpfh_stats;
+    DevCounters plane_stats, outlier_stats, fpfh_stats, sac_stats;
     int fpfh_lists = 1;                         // LTM_FPFH_LISTS=0: ltm_search_fpfh never keeps the neighbour lists of its first pass (A/B switch; the result is the same)
     int reproject_twin = 1;                     // LTM_REPROJECT_TWIN=0: ltm_reproject_twin is two plain reprojections (A/B switch; the result is the same)
     TwinStats twin;                             // ltm_debug_reproject_twin_stats
@@ -872,6 +874,7 @@ struct IndexRecordSet : RecordSet {
     }
 };
 const float4* search_normals(ltm_ctx* c, struct ltm_search* s, int* k);            // ltm_api_search.cpp: the normals of an index of this context (aligned with its tree's pts; null and *k = 0: none)
+const std::vector<uint64_t>& fpfh_rows(ltm_ctx* c, struct ltm_fpfh* h, const float** desc);   // ltm_api_fpfh.cpp: the row bounds of the records of a descriptor set of this context and its rows on the device (throws otherwise)
 void split_by_flag(ltm_ctx* c, const float4* pts, const uint8_t* flag, size_t n, const std::vector<uint64_t>& bounds, const uint64_t* offsets_dev,
                    size_t kf0, uint64_t first, FlagSplit& out);   // ltm_api_knn.cpp
 

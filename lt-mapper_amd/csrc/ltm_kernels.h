@@ -428,6 +428,40 @@ int        fpfh_block(int k);                   // finite points per workgroup o
 hipError_t fpfh_estimate(const FpfhSeg* segs, const uint32_t* block_seg, uint32_t n_blocks, uint64_t n_points, int k, unsigned long long* spfh, float* desc,
                          float* list_d2, int* list_idx, uint64_t total_f, unsigned long long* stats4, hipStream_t s);
 
+// ---- feature-space correspondences between descriptor records (ltm_k_sac.hip; include/ltm.h "fpfh matches") ----
+static constexpr int kMatchBlock = 256;         // source rows per workgroup, one per thread, each in 33 registers
+static constexpr int kMatchTileRows = 128;      // target rows staged in LDS at a time (LTM_MATCH_TILE_ROWS): 33 words per row and one flag
+static constexpr int kMatchRow = 33;            // floats per descriptor row
+static constexpr int kMatchMaxK = kKnnListRegSlots;
+// one pair of the batch: source rows src[0 .. n_source) matched against target rows tgt[0 .. n_target), its lists at row `obase` of the call's outputs;
+// kMatchBlock source rows per workgroup
+struct MatchPair { const float* src; const float* tgt; uint64_t obase; uint32_t n_source, n_target; BlockSpan span; };
+static_assert(sizeof(MatchPair) == 40, "the match record keeps its size");
+// ltm_fpfh_match: one launch for all pairs.  idx / dist: kc slots per source row, ascending by (distance, target row), unused slots (-1, +inf)
+hipError_t fpfh_match(const MatchPair* pairs, const uint32_t* block_pair, uint32_t n_blocks, int kc, int32_t* idx, float* dist, hipStream_t s);
+
+// ---- sample-consensus initial alignment from matches (ltm_k_sac.hip; include/ltm.h "initial alignment") ----
+static constexpr int kSacBlock = 256;                                        // threads per workgroup of the vote kernel
+static constexpr int kSacPointsPerThread = 4;                                // voting points a thread keeps in registers
+static constexpr int kSacBlockPoints = kSacBlock * kSacPointsPerThread;      // voting points of one pair per workgroup (LTM_SAC_BLOCK_POINTS)
+static constexpr int kSacMaxIterations = 16384;
+// one index of the call whose rows are looked up by ORIGINAL position: row[base + idx[j]] = j for its Mf sorted positions; kSacBlock positions per workgroup
+struct SacRows { const uint32_t* idx; uint64_t base; uint32_t Mf, pad; BlockSpan span; };
+// one pair of the batch: the two trees, their row tables (original position -> sorted position, ~0: not finite), its match lists (n_rows x kc target rows);
+// n_eval voting points (sorted positions 0, stride, 2 stride, ... of the source), kSacBlockPoints per workgroup
+struct SacPair { SearchTree tt, st; const uint32_t* trow; const uint32_t* srow; const int32_t* match; uint32_t n_rows, n_eval; BlockSpan span; };
+// one hypothesis: rows 0 .. 2 of the transform, row-major (R | t), 12 doubles
+struct SacHyp { double T[12]; };
+// what a record ends with (ltm_sac_download)
+struct SacOut { double T[16]; int32_t best; uint32_t consensus, n_valid, n_prerejected, n_eval; uint8_t found, pad[3]; };
+struct SacLaunch { double thr2, r2, inlier_fraction; uint32_t max_iterations, seed, stride; int kc; };
+static_assert(sizeof(SacRows) == 32 && sizeof(SacPair) == 136 && sizeof(SacHyp) == 96 && sizeof(SacOut) == 152, "the sac records keep their sizes");
+// The fixed launch sequence of ltm_sac_align for n_pairs pairs (rows filled with ~0, counts and out zeroed by the caller): row tables, hypotheses, votes,
+// best.  hyp / valid / counts: n_pairs x max_iterations.  stats4 += point-hypothesis tests, hypotheses prerejected, walks ended by a hit, records
+hipError_t sac_align(const SacRows* rows, const uint32_t* block_rows, uint32_t n_row_blocks, uint32_t* row, const SacPair* pairs, const uint32_t* block_pair,
+                     uint32_t n_blocks, uint32_t n_pairs, const SacLaunch& L, SacHyp* hyp, uint8_t* valid, uint32_t* counts, SacOut* out,
+                     unsigned long long* stats4, hipStream_t s);
+
 // ---- loop submaps (ltm_k_submap.hip; ltslam/src/Session.cpp:91-142, utility.cpp:80-103) ----
 // one piece of the batch: n points from scans[src ...] moved by affine `affine` (12 floats each) to out[dst ...]; 256 points per workgroup
 struct SubmapPiece { uint64_t src, dst; uint32_t n, affine; BlockSpan span; };
